@@ -9,6 +9,12 @@ A "step" is one full train step (train.py:train_step: zero_grad, forward, NaN gu
 gradient all-reduce, AdamW, scheduler, parameter-EMA hook) on one batch of 32 synthetic
 22.05 kHz clips of 145,408 samples per GPU (BASELINE.json configs[1]: codebook 1024, bf16).
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the headline line (with the dominant kernel's roofline from
+the HIP events of every --event_every-th timed step).  `--full` adds everything else the vqvae workload measures: the
+per-kernel table and the other kernels' rooflines, the mel-STFT and VQ micro-benchmarks, the ragged-length run, the
+hipGraph replay, the fp32 parity path and the CPU baseline (each can still be skipped with its --no_* option).
+`--dump-outputs DIR` writes what the last timed step returned (see dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -68,7 +74,17 @@ def parse(argv=None):
     p.add_argument("--no_micro", action="store_true", help="skip the VQ micro-benchmark and the mel-STFT kernel measurement")
     p.add_argument("--graph_leg", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--fp32_steps", type=int, default=3)
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="vqvae workload: after the headline measurement also report the per-kernel table and the other "
+                        "kernels' rooflines and run the secondary measurements (mel-STFT and VQ micro-benchmarks, ragged "
+                        "lengths, hipGraph replay, fp32 parity path, CPU baseline)")
+    p.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                   help="vqvae workload: write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                        "at most 64 MB in all)")
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def make_config(args):
@@ -658,6 +674,32 @@ def timed_fp32(args, pool, device, note):
             "note": "same workload on the fp32 parity path (conv stacks on v_mfma_f32_32x32x2_f32)"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """`--dump-outputs DIR`: one DIR/<name>.npy per array of `arrays` (tensors or numbers), float64 where the source is
+    float64 and float32 otherwise.  When they hold more than `budget` bytes in all, the budget is shared out evenly and an
+    array above its share keeps a fixed sample of its flattened elements: indices drawn once by numpy seed 0 and sorted,
+    so the same shape always keeps the same elements and two builds compare element for element.  Returns the names."""
+    import numpy as np
+    out = {}
+    for name, v in arrays.items():
+        t = v.detach().cpu() if torch.is_tensor(v) else torch.tensor(v, dtype=torch.float64)
+        out[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    left, todo = budget, sorted(out, key=lambda n: out[n].nbytes)
+    for i, name in enumerate(todo):
+        a, share = out[name], left // (len(todo) - i)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            out[name] = a = a.reshape(-1)[keep]
+        left -= a.nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
@@ -737,7 +779,7 @@ def main(argv=None):
         prof_step = (not args.no_kernel_events) and i % every == 0   # HIP events around every native call of this step
         profiler.enable(prof_step)
         n_prof += int(prof_step)
-        loss_dict, _ = step(args.warmup + i)
+        loss_dict, metrics = step(args.warmup + i)
     host_elapsed = time.perf_counter() - t0     # all launches enqueued (the host runs ahead of the GPU)
     torch.cuda.synchronize()
     if world > 1:
@@ -753,6 +795,10 @@ def main(argv=None):
         per_rank_ms = [t.item() / args.steps * 1e3 for t in every_rank]
         elapsed = max(t.item() for t in every_rank)            # MAX over ranks
         sync_ms = grad_sync.exposed_ms()
+    if rank == 0 and args.dump_outputs:
+        # what train_step handed its caller in the last timed step: losses, reconstruction `yh` and target `y`, VQ metrics
+        names = dump_outputs(args.dump_outputs, {**loss_dict, **metrics})
+        note(f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)}")
 
     if rank == 0:
         kernels = profiler.summary()
@@ -860,15 +906,16 @@ def main(argv=None):
                        "latent_rows_per_gpu": n_rows, "parallelism": f"dp{world}"},
             "loss": float(loss_dict["loss"].detach()),
             "roofline": roofline,
-            "rooflines_other": extra_rooflines,
-            "kernels": kernels,
         }
         note(f"timed region done: {line['value']:.2f} utt/s, {line['ms_per_step']:.1f} ms/step")
-        for key in ("vq_forward", "vq_ema_accumulate"):        # spread over the timed steps, not only the mean
-            rec = next((k for k in kernels if k["name"] == key), None)
-            if rec is not None and key in extra_rooflines:
-                extra_rooflines[key]["min_us"], extra_rooflines[key]["max_us"] = rec["min_us"], rec["max_us"]
-        if world == 1 and not args.no_micro:
+        if args.full:
+            line["rooflines_other"], line["kernels"] = extra_rooflines, kernels
+            for key in ("vq_forward", "vq_ema_accumulate"):    # spread over the timed steps, not only the mean
+                rec = next((k for k in kernels if k["name"] == key), None)
+                if rec is not None and key in extra_rooflines:
+                    extra_rooflines[key]["min_us"], extra_rooflines[key]["max_us"] = rec["min_us"], rec["max_us"]
+        full1 = args.full and world == 1         # the secondary measurements: rank 0 at N = 1 only
+        if full1 and not args.no_micro:
             line["rooflines_other"]["melspec"] = melspec_roofline(args, pool[0][4], device, note)
             mel_traffic = pmc.get("melspec", {}).get("hbm_bytes_per_launch")
             if mel_traffic is not None:
@@ -877,19 +924,19 @@ def main(argv=None):
             if st_traffic is not None and "stft_loss" in line["rooflines_other"]:
                 line["rooflines_other"]["stft_loss"].update(traffic=st_traffic, traffic_source=pmc_source)
             line["vq_micro"] = vq_micro(device, note)
-        if world == 1 and not args.no_ragged:
+        if full1 and not args.no_ragged:
             def factory(rpool):
                 return lambda i: trainlib.train_step(global_step=i, batch=rpool[i % len(rpool)], config=cfg, model=model, ema=ema,
                                                      optimizer=optimizer, scheduler=scheduler, device=device, rank=rank,
                                                      grad_sync=grad_sync)
             line["ragged"] = timed_ragged(args, factory, rank, device, note)
-        if world == 1 and not args.no_graph:
+        if full1 and not args.no_graph:
             line["hip_graph"] = timed_graph(args, note)
-        if world == 1 and not args.no_fp32 and m.get("compute_dtype") == "bf16":
+        if full1 and not args.no_fp32 and m.get("compute_dtype") == "bf16":
             del model, optimizer, scheduler, ema
             torch.cuda.empty_cache()
             line["fp32"] = timed_fp32(args, pool, device, note)
-        if world == 1 and not args.no_cpu_baseline:       # rank 0 at N = 1 only
+        if full1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args)
             note("cpu baseline done")
         print(json.dumps(line), flush=True)

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -32,15 +33,35 @@ def test_single_gpu_line_has_the_contract_fields():
     assert d["n_gpus"] == 1 and d["unit"] == "utterances/s" and d["data"] == "synthetic" and d["vs_baseline"] is None
     assert d["config"]["workload"].startswith("configs[1]") and d["roofline"]["bound"] in ("mfma", "hbm")
     assert abs(d["value"] - 2 * 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+    # a plain run measures the headline only: the per-kernel table and the secondary measurements need --full
+    assert not {"kernels", "rooflines_other", "vq_micro", "ragged", "hip_graph", "fp32", "cpu_baseline"} & set(d)
 
 
 def test_hip_graph_leg_runs_in_a_child_process_and_reports():
-    """The secondary `hip_graph` object: the same step with forward + backward replayed from a captured graph, measured in a
-    child process so that a failure there cannot take the headline line down."""
-    d = _run([a for a in SMALL if a != "--no_graph"])
+    """The secondary `hip_graph` object (--full): the same step with forward + backward replayed from a captured graph,
+    measured in a child process so that a failure there cannot take the headline line down."""
+    d = _run([a for a in SMALL if a != "--no_graph"] + ["--full"])
+    assert {"kernels", "rooflines_other", "vq_micro", "ragged"} <= set(d)
     g = d["hip_graph"]
     assert "error" not in g, g
     assert g["unit"] == "utterances/s" and g["value"] > 0 and g["loss"] == g["loss"]
+
+
+def test_dump_outputs_hold_the_last_timed_step_and_repeat_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: what the last timed train step returned (losses, reconstruction `yh`, target `y`, VQ metrics) as
+    float32 / float64 .npy files within 64 MB; a second run with the same arguments gets the same inputs."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = _run(SMALL + ["--dump-outputs", str(a)])
+    _run(SMALL + ["--dump-outputs", str(b)])
+    names = sorted(p.name for p in a.iterdir())
+    assert names == sorted(p.name for p in b.iterdir())
+    assert {"loss.npy", "loss_recon.npy", "loss_stft.npy", "loss_commit.npy", "yh.npy", "y.npy", "fit.npy", "usage.npy"} <= set(names)
+    assert sum((a / n).stat().st_size for n in names) <= 64 << 20
+    out = {n: np.load(a / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert out["y.npy"].shape == out["yh.npy"].shape == (2, 16384) and np.isfinite(out["yh.npy"]).all()
+    assert float(out["loss.npy"]) == d["loss"]
+    assert np.array_equal(out["y.npy"], np.load(b / "y.npy"))
 
 
 def test_two_ranks_started_by_bench_itself():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Summarise two rocprofv3 PMC passes (--pmc FETCH_SIZE and --pmc WRITE_SIZE, each with --kernel-trace only) of
-`python bench.py --steps 1 --warmup 1 --no_cpu_baseline --no_kernel_events` into per-kernel-group HBM bytes per launch.
+`python bench.py --full --steps 1 --warmup 1 --no_cpu_baseline --no_kernel_events` into per-kernel-group HBM bytes per launch.
 
     python tools/pmc_traffic.py <fetch_counter_collection.csv> <write_counter_collection.csv> <out_prefix>
 
