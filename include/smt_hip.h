@@ -450,14 +450,16 @@ int smt_glow_coupling_bwd(const float* out, const float* x, const float* dz, con
 /* Self-attention with relative-position keys and values (AttentionBlock.attention, submodules.py:463-512; window W, the
  * embeddings [2 W + 1, head_dim] shared by the heads): q, k, v, ctx [batch, t, heads * head_dim]; scores of padded queries /
  * keys are FILLED with -1e4 like the reference (a fully padded row is uniform); probs [batch, heads, t, t] = the softmax,
- * kept for the backward; dropout on the probabilities (index = linear index of probs). */
+ * kept for the backward; dropout on the probabilities (index = linear index of probs).  Rows of q / k / v at padded positions
+ * are never read where the reference's result does not depend on them (they may hold anything, NaN included): the backward
+ * takes the same lens, and the score gradient of a padded pair is 0 as masked_fill's backward makes it. */
 int smt_glow_attention_fwd(const float* q, const float* k, const float* v, const float* emb_rel_k, const float* emb_rel_v,
                            const int* lens, float* ctx, float* probs, int batch, int t, int heads, int head_dim, int window,
                            uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale,
                            smt_stream_t stream);
 size_t smt_glow_attention_bwd_workspace_bytes(int batch, int t, int heads, int head_dim, int window);
 int smt_glow_attention_bwd(const float* q, const float* k, const float* v, const float* emb_rel_k, const float* emb_rel_v,
-                           const float* probs, const float* dctx, float* dq, float* dk, float* dv, float* demb_rel_k,
+                           const float* probs, const int* lens, const float* dctx, float* dq, float* dk, float* dv, float* demb_rel_k,
                            float* demb_rel_v, int batch, int t, int heads, int head_dim, int window, uint32_t drop_key,
                            const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, void* workspace,
                            size_t workspace_bytes, smt_stream_t stream);

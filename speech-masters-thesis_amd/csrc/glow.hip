@@ -64,8 +64,8 @@ __global__ __launch_bounds__(GL_NT) void gl_actnorm_fwd_kernel(const float* __re
     const int c = (int)(e % C);
     const long long row = e / C;
     const int t = (int)(row % T), b = (int)(row / T);
-    const float m = (lens && t >= lens[b]) ? 0.f : 1.f;
-    z[e] = reverse ? (x[e] - bias[c]) * expf(-logs[c]) * m : (bias[c] + expf(logs[c]) * x[e]) * m;
+    const bool pad = lens && t >= lens[b];
+    z[e] = pad ? 0.f : reverse ? (x[e] - bias[c]) * expf(-logs[c]) : bias[c] + expf(logs[c]) * x[e];
   }
 }
 
@@ -80,8 +80,11 @@ __global__ __launch_bounds__(GL_NT) void gl_actnorm_bwd_kernel(const float* __re
     float sl = 0.f, sb = 0.f;
     for (long long r = r0; r < min(rows, r0 + GL_ROWS); ++r) {
       const int t = (int)(r % T), b = (int)(r / T);
-      const float m = (lens && t >= lens[b]) ? 0.f : 1.f;
-      const float g = dz[r * C + c] * m;
+      if (lens && t >= lens[b]) {           // padded rows are skipped, not multiplied by 0: they may hold anything, NaN included
+        if (dx) dx[r * C + c] = 0.f;
+        continue;
+      }
+      const float g = dz[r * C + c];
       if (dx) dx[r * C + c] = g * el;
       sl += g * el * x[r * C + c];
       sb += g;
@@ -105,12 +108,13 @@ __global__ __launch_bounds__(GL_NT) void gl_invconv_kernel(const float* __restri
     const int j = (int)(e % G);
     const long long row = e / G;
     const int t = (int)(row % T), b = (int)(row / T);
-    const float m = (lens && t >= lens[b]) ? 0.f : 1.f;
+    const bool pad = lens && t >= lens[b];
     const float* xr = x + row * C;
     float v[4] = {xr[2 * j], xr[2 * j + 1], xr[C / 2 + 2 * j], xr[C / 2 + 2 * j + 1]};
     float o[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) o[s] = (((ws[4 * s] * v[0] + ws[4 * s + 1] * v[1]) + ws[4 * s + 2] * v[2]) + ws[4 * s + 3] * v[3]) * m;
+    for (int s = 0; s < 4; ++s) o[s] = (((ws[4 * s] * v[0] + ws[4 * s + 1] * v[1]) + ws[4 * s + 2] * v[2]) + ws[4 * s + 3] * v[3]);
+    if (pad) o[0] = o[1] = o[2] = o[3] = 0.f;
     float* zr = z + row * C;
     zr[2 * j] = o[0]; zr[2 * j + 1] = o[1]; zr[C / 2 + 2 * j] = o[2]; zr[C / 2 + 2 * j + 1] = o[3];
   }
@@ -205,12 +209,12 @@ __global__ __launch_bounds__(GL_NT) void gl_coupling_fwd_kernel(const float* __r
   for (int e = threadIdx.x; e < (t1 - t0) * h; e += GL_NT) {
     const int t = t0 + e / h, c = e % h;
     const size_t row = ((size_t)b * T + t) * C;
-    const float m = t < len ? 1.f : 0.f;
+    z[row + c] = x[row + c];                   // x0 passes through unmasked, as in the reference
+    if (t >= len) { z[row + h + c] = 0.f; continue; }
     float lg = out[row + h + c];
     if (sigmoid_scale) lg = logf(1e-6f + gl_sigmoid(lg + 2.f));
-    z[row + c] = x[row + c];
-    z[row + h + c] = reverse ? (x[row + h + c] - out[row + c]) * expf(-lg) * m : (out[row + c] + expf(lg) * x[row + h + c]) * m;
-    s += lg * m;
+    z[row + h + c] = reverse ? (x[row + h + c] - out[row + c]) * expf(-lg) : out[row + c] + expf(lg) * x[row + h + c];
+    s += lg;
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -229,7 +233,8 @@ __global__ __launch_bounds__(GL_NT) void gl_coupling_bwd_kernel(const float* __r
     const long long r = e / h;
     const int t = (int)(r % T), b = (int)(r / T);
     const size_t row = (size_t)r * C;
-    const float m = (lens && t >= lens[b]) ? 0.f : 1.f;
+    dx[row + c] = dz[row + c];
+    if (lens && t >= lens[b]) { dout[row + c] = dout[row + h + c] = dx[row + h + c] = 0.f; continue; }
     const float raw = out[row + h + c];
     float lg = raw, dl_draw = 1.f;
     if (sigmoid_scale) {
@@ -237,10 +242,9 @@ __global__ __launch_bounds__(GL_NT) void gl_coupling_bwd_kernel(const float* __r
       lg = logf(1e-6f + sg);
       dl_draw = sg * (1.f - sg) / (1e-6f + sg);
     }
-    const float el = expf(lg), g1 = dz[row + h + c] * m;
+    const float el = expf(lg), g1 = dz[row + h + c];
     dout[row + c] = g1;
-    dout[row + h + c] = (g1 * el * x[row + h + c] + (dlogdet ? dlogdet[b] : 0.f) * m) * dl_draw;
-    dx[row + c] = dz[row + c];
+    dout[row + h + c] = (g1 * el * x[row + h + c] + (dlogdet ? dlogdet[b] : 0.f)) * dl_draw;
     dx[row + h + c] = g1 * el;
   }
 }
@@ -305,7 +309,8 @@ __global__ __launch_bounds__(GL_NT) void gl_attn_fwd_kernel(const float* __restr
   float* crow = ctx + ((size_t)b * T + i) * C + h * D;
   for (int d = threadIdx.x; d < D; d += GL_NT) {
     float o = 0.f;
-    for (int j = 0; j < T; ++j) o = fmaf(sc[j], v[((size_t)b * T + j) * C + h * D + d], o);
+    // padded keys are skipped, not weighted by their zero probability: their rows of v may hold anything (NaN: 0 * NaN = NaN)
+    for (int j = 0; j < len; ++j) o = fmaf(sc[j], v[((size_t)b * T + j) * C + h * D + d], o);
     for (int rel = max(-W, -i); rel <= min(W, T - 1 - i); ++rel) o = fmaf(sc[i + rel], ev[(size_t)(rel + W) * D + d], o);
     crow[d] = o;
   }
@@ -317,7 +322,8 @@ __global__ __launch_bounds__(GL_NT) void gl_attn_fwd_kernel(const float* __restr
 __global__ __launch_bounds__(GL_NT) void gl_attn_bwd_q_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                               const float* __restrict__ v, const float* __restrict__ ek,
                                                               const float* __restrict__ ev, const float* __restrict__ pa,
-                                                              const float* __restrict__ dctx, float* __restrict__ dq,
+                                                              const int* __restrict__ lens, const float* __restrict__ dctx,
+                                                              float* __restrict__ dq,
                                                               float* __restrict__ ds, float* __restrict__ dek_part,
                                                               float* __restrict__ dev_part, int T, int heads, int D, int W,
                                                               unsigned key, const unsigned* __restrict__ key_dev, unsigned thr, float dscale) {
@@ -328,7 +334,10 @@ __global__ __launch_bounds__(GL_NT) void gl_attn_bwd_q_kernel(const float* __res
   float* dsr = sm + 2 * D;
   __shared__ float red[GL_NT / 64];
   const int i = blockIdx.x, h = blockIdx.y % heads, b = blockIdx.y / heads;
-  const int C = heads * D;
+  const int C = heads * D, len = lens ? lens[b] : T;
+  // the scores of padded pairs (i >= len or j >= len) are masked_fill constants: dS = 0 there, and rows of q / k / v at padded
+  // positions are never read for it (they may hold anything, NaN included); kv = the keys a valid query row reads
+  const int kv = i < len ? len : 0;
   const float inv = rsqrtf((float)D);
   for (int d = threadIdx.x; d < D; d += GL_NT) {
     gs[d] = dctx[((size_t)b * T + i) * C + h * D + d];
@@ -339,6 +348,7 @@ __global__ __launch_bounds__(GL_NT) void gl_attn_bwd_q_kernel(const float* __res
   const unsigned long long e0 = (((unsigned long long)b * heads + h) * T + i) * T;
   float dot = 0.f;
   for (int j = threadIdx.x; j < T; j += GL_NT) {
+    if (j >= kv) { dsr[j] = 0.f; continue; }
     const float* vrow = v + ((size_t)b * T + j) * C + h * D;
     float dp = 0.f;
     for (int d = 0; d < D; ++d) dp = fmaf(gs[d], vrow[d], dp);
@@ -357,15 +367,15 @@ __global__ __launch_bounds__(GL_NT) void gl_attn_bwd_q_kernel(const float* __res
   dot = ((red[0] + red[1]) + red[2]) + red[3];
   float* dsrow = ds + (((size_t)b * heads + h) * T + i) * T;
   for (int j = threadIdx.x; j < T; j += GL_NT) {
-    const float g = prow[j] * (dsr[j] - dot);  // softmax backward; masked_fill entries have P = 0 up to exp(-1e4 - max) = 0
+    const float g = j < kv ? prow[j] * (dsr[j] - dot) : 0.f;   // softmax backward; masked_fill entries: 0
     dsr[j] = g;
     dsrow[j] = g;
   }
   __syncthreads();
   for (int d = threadIdx.x; d < D; d += GL_NT) {
     float o = 0.f;
-    for (int j = 0; j < T; ++j) o = fmaf(dsr[j], k[((size_t)b * T + j) * C + h * D + d], o);
-    for (int rel = max(-W, -i); rel <= min(W, T - 1 - i); ++rel) o = fmaf(dsr[i + rel], ek[(size_t)(rel + W) * D + d], o);
+    for (int j = 0; j < kv; ++j) o = fmaf(dsr[j], k[((size_t)b * T + j) * C + h * D + d], o);
+    for (int rel = max(-W, -i); rel <= min(W, kv - 1 - i); ++rel) o = fmaf(dsr[i + rel], ek[(size_t)(rel + W) * D + d], o);
     dq[((size_t)b * T + i) * C + h * D + d] = o * inv;
   }
   // per-query partials of the relative-embedding gradients: dek[r] += dS_{i,i+r} q_i / sqrt(D), dev[r] += P keep_{i,i+r} dctx_i
@@ -374,25 +384,27 @@ __global__ __launch_bounds__(GL_NT) void gl_attn_bwd_q_kernel(const float* __res
   for (int e = threadIdx.x; e < (2 * W + 1) * D; e += GL_NT) {
     const int r = e / D - W, d = e % D, j = i + r;
     const bool ok = j >= 0 && j < T;
-    dkp[e] = ok ? dsr[j] * qs[d] * inv : 0.f;
+    dkp[e] = ok && j < kv ? dsr[j] * qs[d] * inv : 0.f;
     dvp[e] = ok ? prow[j] * gl_keep(e0 + j, key, thr, dscale) * gs[d] : 0.f;
   }
 }
 // key side: dk_j = sum_i dS_ij q_i / sqrt(D), dv_j = sum_i (P keep)_ij dctx_i.  One workgroup per (batch, head, key).
 __global__ __launch_bounds__(GL_NT) void gl_attn_bwd_kv_kernel(const float* __restrict__ q, const float* __restrict__ pa,
-                                                               const float* __restrict__ ds, const float* __restrict__ dctx,
+                                                               const int* __restrict__ lens, const float* __restrict__ ds,
+                                                               const float* __restrict__ dctx,
                                                                float* __restrict__ dk, float* __restrict__ dv, int T, int heads, int D,
                                                                unsigned key, const unsigned* __restrict__ key_dev, unsigned thr, float dscale) {
   if (key_dev) key = *key_dev;
   const int j = blockIdx.x, h = blockIdx.y % heads, b = blockIdx.y / heads;
-  const int C = heads * D;
+  const int C = heads * D, len = lens ? lens[b] : T;
+  const int nq = j < len ? len : 0;            // dS_ij = 0 unless both i and j are valid: padded rows of q are not read
   const float inv = rsqrtf((float)D);
   const float* pcol = pa + (((size_t)b * heads + h) * T) * T + j;
   const float* dcol = ds + (((size_t)b * heads + h) * T) * T + j;
   for (int d = threadIdx.x; d < D; d += GL_NT) {
     float ok_ = 0.f, ov = 0.f;
     for (int i = 0; i < T; ++i) {
-      ok_ = fmaf(dcol[(size_t)i * T], q[((size_t)b * T + i) * C + h * D + d], ok_);
+      if (i < nq) ok_ = fmaf(dcol[(size_t)i * T], q[((size_t)b * T + i) * C + h * D + d], ok_);
       ov = fmaf(pcol[(size_t)i * T] * gl_keep((((unsigned long long)b * heads + h) * T + i) * T + j, key, thr, dscale),
                 dctx[((size_t)b * T + i) * C + h * D + d], ov);
     }
@@ -523,8 +535,7 @@ __global__ __launch_bounds__(1024) void gl_length_loss_kernel(const float* __res
   float s = 0.f;
   for (int e = threadIdx.x; e < B * Tx; e += 1024) {
     const int b = e / Tx, t = e % Tx;
-    const float m = (lens && t >= lens[b]) ? 0.f : 1.f;
-    const float df = (logw[e] - logf(1e-8f + dur[e])) * m;
+    const float df = (lens && t >= lens[b]) ? 0.f : logw[e] - logf(1e-8f + dur[e]);
     diff[e] = df;
     s += df * df;
   }
@@ -693,7 +704,7 @@ extern "C" size_t smt_glow_attention_bwd_workspace_bytes(int batch, int t, int h
 }
 
 extern "C" int smt_glow_attention_bwd(const float* q, const float* k, const float* v, const float* emb_rel_k, const float* emb_rel_v,
-                                      const float* probs, const float* dctx, float* dq, float* dk, float* dv, float* demb_rel_k,
+                                      const float* probs, const int* lens, const float* dctx, float* dq, float* dk, float* dv, float* demb_rel_k,
                                       float* demb_rel_v, int batch, int t, int heads, int head_dim, int window, uint32_t drop_key,
                                       const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, void* workspace,
                                       size_t workspace_bytes, smt_stream_t stream_) {
@@ -708,10 +719,10 @@ extern "C" int smt_glow_attention_bwd(const float* q, const float* k, const floa
   if (batch > 0 && t > 0) {
     const size_t lds = gl_attn_lds(t, head_dim, 2);
     SMT_CHECK_ARG(lds <= 60 * 1024, "smt_glow_attention_bwd: t = %d keys need %zu B of LDS (limit 60 KiB)", t, lds);
-    gl_attn_bwd_q_kernel<<<dim3(t, batch * heads), GL_NT, lds, stream>>>(q, k, v, emb_rel_k, emb_rel_v, probs, dctx, dq, ds, dkp, dvp, t, heads,
+    gl_attn_bwd_q_kernel<<<dim3(t, batch * heads), GL_NT, lds, stream>>>(q, k, v, emb_rel_k, emb_rel_v, probs, lens, dctx, dq, ds, dkp, dvp, t, heads,
                                                                        head_dim, window, drop_key, drop_key_dev, drop_thresh16, drop_scale);
     SMT_CHECK_LAUNCH("glow_attention_bwd_q");
-    gl_attn_bwd_kv_kernel<<<dim3(t, batch * heads), GL_NT, 0, stream>>>(q, probs, ds, dctx, dk, dv, t, heads, head_dim, drop_key, drop_key_dev,
+    gl_attn_bwd_kv_kernel<<<dim3(t, batch * heads), GL_NT, 0, stream>>>(q, probs, lens, ds, dctx, dk, dv, t, heads, head_dim, drop_key, drop_key_dev,
                                                                      drop_thresh16, drop_scale);
     SMT_CHECK_LAUNCH("glow_attention_bwd_kv");
   }

@@ -223,14 +223,15 @@ class _RelAttention(torch.autograd.Function):
             N.check(N.lib().smt_glow_attention_fwd(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(ek2), N.ptr(ev2), N.ptr(lens), N.ptr(ctxv), N.ptr(probs), b,
                                                    t, heads, d, window, drop.key, N.ptr(drop.key_dev), drop.thresh, drop.scale,
                                                    N.stream_ptr()), "smt_glow_attention_fwd")
-        ctx.save_for_backward(q, k, v, ek2, ev2, probs)
-        ctx.meta = (heads, window, drop, ek.shape, ev.shape)
+        ctx.save_for_backward(q, k, v, ek2, ev2, probs, lens if lens is not None else torch.empty(0))
+        ctx.meta = (heads, window, drop, ek.shape, ev.shape, lens is not None)
         return ctxv
 
     @staticmethod
     def backward(ctx, dctx):
-        q, k, v, ek2, ev2, probs = ctx.saved_tensors
-        heads, window, drop, ek_shape, ev_shape = ctx.meta
+        q, k, v, ek2, ev2, probs, lens = ctx.saved_tensors
+        heads, window, drop, ek_shape, ev_shape, has_lens = ctx.meta
+        lens = lens if has_lens else None
         b, t, c = q.shape
         d = c // heads
         lib = N.lib()
@@ -238,8 +239,8 @@ class _RelAttention(torch.autograd.Function):
         dek, dev = torch.empty_like(ek2), torch.empty_like(ev2)
         ws = _ws(lib.smt_glow_attention_bwd_workspace_bytes(b, t, heads, d, window), q.device)
         with profiler.region("glow_attention:bwd", flops=10.0 * b * heads * t * t * d, bound="mfma", dtype="f32"):
-            N.check(lib.smt_glow_attention_bwd(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(ek2), N.ptr(ev2), N.ptr(probs), N.ptr(_f(dctx)), N.ptr(dq),
-                                               N.ptr(dk), N.ptr(dv), N.ptr(dek), N.ptr(dev), b, t, heads, d, window, drop.key,
+            N.check(lib.smt_glow_attention_bwd(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(ek2), N.ptr(ev2), N.ptr(probs), N.ptr(lens), N.ptr(_f(dctx)),
+                                               N.ptr(dq), N.ptr(dk), N.ptr(dv), N.ptr(dek), N.ptr(dev), b, t, heads, d, window, drop.key,
                                                N.ptr(drop.key_dev), drop.thresh, drop.scale, N.ptr(ws), ws.numel(), N.stream_ptr()),
                     "smt_glow_attention_bwd")
         return dq, dk, dv, dek.view(ek_shape), dev.view(ev_shape), None, None, None, None

@@ -9,7 +9,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SMT_HIP_LIB: an alternative build of the same ABI (tools/ablate_*.sh link their -D ablation builds to libsmt_hip_abl.so)
 LIB_PATH = os.environ.get("SMT_HIP_LIB") or os.path.join(_HERE, "libsmt_hip.so")
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 _lib = None
 _lock = threading.Lock()
@@ -108,7 +108,7 @@ _SIGNATURES = {
     "smt_glow_attention_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int,
                                        c_u32, c_ptr, c_u32, c_f32, c_ptr]),
     "smt_glow_attention_bwd_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int, c_int]),
-    "smt_glow_attention_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int,
+    "smt_glow_attention_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int,
                                        c_int, c_int, c_int, c_u32, c_ptr, c_u32, c_f32, c_ptr, c_size, c_ptr]),
     "smt_glow_prior_logp": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "smt_glow_align_index": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr]),
