@@ -314,10 +314,6 @@ __global__ __launch_bounds__(NT) void conv_gemm_kernel(ConvArgs p) {
 //   weights    : pre-swizzled in global memory by smt_pack_weight(swizzle = 1), copied linearly.
 // Rows outside [0, len) are fetched from a zero page.
 constexpr int DMA_BM = 128, DMA_BN = 128, DMA_KC = 128, DMA_NT = 512;
-#ifndef SMT_ABL
-#define SMT_ABL 0   // ablation build switches for conv_gemm_dma_kernel (tools/ablate_dma.sh); 0 in the product
-#endif
-constexpr int ABL = SMT_ABL;
 
 __device__ __forceinline__ void dma16(const void* gsrc, void* lds_dst_wave_base) {
   __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)gsrc,
@@ -407,7 +403,6 @@ __global__ __launch_bounds__(DMA_NT) void conv_gemm_dma_kernel(ConvArgs p, const
 
   for (int cc = 0; cc < ncc; ++cc) {
     __syncthreads();  // previous chunk's readers are done with lds_a / lds_w
-    if (!(ABL & 1))
     for (int g = wave; g < rows_pad / 4; g += NT / 64) {
       const int row = 4 * g + lrow;
       const int tin = tin0 + row;
@@ -416,33 +411,26 @@ __global__ __launch_bounds__(DMA_NT) void conv_gemm_dma_kernel(ConvArgs p, const
       dma16(src, lds_a + g * 1024);
     }
     stage_w(0, cc, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     __syncthreads();
     const int nsteps = p.taps;
     for (int s = 0; s < nsteps; ++s) {
-      if (s + 1 < nsteps && !(ABL & 2)) stage_w(s + 1, cc, (s + 1) & 1);
+      if (s + 1 < nsteps) stage_w(s + 1, cc, (s + 1) & 1);
       const unsigned char* wb = lds_w + (size_t)(s & 1) * BN * ROWB + (wn * 32 + r) * ROWB;
       const int bsw = (wn * 32 + r) & 15;
       const int arow0 = wm * (BM / 2) + s * p.dil + r;
-      bf16x8 bv0, av0[MW];
-      if (ABL & 16) bv0 = *reinterpret_cast<const bf16x8*>(wb + ((hh ^ bsw) << 4));
-      if (ABL & 8) {
-#pragma unroll
-        for (int i = 0; i < MW; ++i) av0[i] = *reinterpret_cast<const bf16x8*>(lds_a + (arow0 + 32 * i) * ROWB + ((hh ^ ((arow0 + 32 * i) & 15)) << 4));
-      }
 #pragma unroll
       for (int kk = 0; kk < KC / 16; ++kk) {
         const int ch = 2 * kk + hh;
-        bf16x8 bv = (ABL & 16) ? bv0 : *reinterpret_cast<const bf16x8*>(wb + ((ch ^ bsw) << 4));
+        const bf16x8 bv = *reinterpret_cast<const bf16x8*>(wb + ((ch ^ bsw) << 4));
 #pragma unroll
         for (int i = 0; i < MW; ++i) {
           const int ar = arow0 + 32 * i;
-          bf16x8 av = (ABL & 8) ? av0[i] : *reinterpret_cast<const bf16x8*>(lds_a + ar * ROWB + ((ch ^ (ar & 15)) << 4));
-          if (ABL & 4) asm volatile("" ::"v"(av), "v"(bv));
-          else acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[i], 0, 0, 0);
+          const bf16x8 av = *reinterpret_cast<const bf16x8*>(lds_a + ar * ROWB + ((ch ^ (ar & 15)) << 4));
+          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[i], 0, 0, 0);
         }
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      vm_wait<0>();
       __syncthreads();
     }
   }
@@ -566,7 +554,7 @@ __global__ __launch_bounds__(DMA_NT) void conv1x1_dma_kernel(ConvArgs p, const _
     const int buf = (tile - tile_begin) & 1;
     const int b = tile / p.tiles_per_batch;
     const int t0 = (tile % p.tiles_per_batch) * BM;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this tile's operand has landed (and older stores retired)
+    vm_wait<0>();                                       // this tile's operand has landed (and older stores retired)
     __syncthreads();                                    // ... for every wave; the other buffer is free again
     if (tile + 1 < tile_end) stage_a(tile + 1, buf ^ 1);
     // epilogue operands of THIS tile: requested before the MFMAs
@@ -667,8 +655,8 @@ __global__ __launch_bounds__(DMA_NT) void conv1x1_dma_kernel(ConvArgs p, const _
 //     straight from registers -- no LDS staging of the output, no epilogue barrier;
 //   * each wave DMAs its own 64-byte column slice of the residual / activation-source rows to LDS and reads
 //     only that back, so the epilogue operands need neither registers during the tap loop nor a barrier.
-// Measured motivation (tools/ablate_dma.sh): the streaming kernel spends as long waiting for HBM (tile in,
-// tile out) as it does in MFMAs, and with one workgroup per CU the two never overlap.
+// Measured motivation (ablation build, tools/ablate_dma.sh of commit 29a7cd8): the streaming kernel spends as long
+// waiting for HBM (tile in, tile out) as it does in MFMAs, and with one workgroup per CU the two never overlap.
 // Buffer addressing (raw V#, byte offsets): rows outside [0, valid rows) fall outside num_records and read as zero /
 // are not stored -- the hardware's range check replaces the per-lane bounds tests and zero-page selects, and a per-lane
 // 32-bit offset replaces the 64-bit address arithmetic (both were VALU work serial with the MFMAs: tools/ws_phases.py
@@ -791,7 +779,7 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_kernel(ConvArgs p, const __bf16
   };
 
   stage_a(tile_begin, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
     int b, cls, t0;
@@ -831,7 +819,6 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_kernel(ConvArgs p, const __bf16
     }
     auto frag_addr = [&](int q) -> unsigned { return tap_base[q / (KC / 16)] ^ (32u * (q % (KC / 16))); };
     bf16x8 afr[2][MW];
-    if (!(ABL & 4)) {
     {
       const unsigned ap = frag_addr(0);
 #pragma unroll
@@ -842,18 +829,12 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_kernel(ConvArgs p, const __bf16
     for (int q = 0; q < NTAPS * (KC / 16); ++q) {
       if (q + 1 < NTAPS * (KC / 16)) {
         const unsigned ap = frag_addr(q + 1);
-        if (ABL & 8) {           // ablation: no fragment reads after the first step
-#pragma unroll
-          for (int i = 0; i < MW; ++i) afr[(q + 1) & 1][i] = afr[q & 1][i];
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        } else {
 #pragma unroll
         for (int i = 0; i < MW; ++i)
           asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(afr[(q + 1) & 1][i]) : "v"(ap), "n"(i * 32 * ROWB));
-        asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-        }
+        lgkm_wait<MW>();                            // the MW reads of step q are done, those of step q + 1 in flight
       } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lgkm_wait<0>();
       }
 #pragma unroll
       for (int i = 0; i < MW; ++i) {
@@ -872,15 +853,10 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_kernel(ConvArgs p, const __bf16
     static_assert(MW == 4, "drain below names four accumulators");
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15"
                  : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
-    }
     WS_T(c5);
     // next tile + this tile's epilogue operands have landed (issued a whole tap loop ago); older stores retired
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     WS_T(c6);
-    if (ABL & 32) {   // ablation: no epilogue
-      asm volatile("" :: "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]));
-      continue;
-    }
 
     // ---- epilogue straight from the accumulators; same arithmetic as the other kernels: bf16(acc + bias) first.
     // Stores go through range-checked buffer descriptors (rows >= Tc are dropped by the hardware, 32-bit offsets).
@@ -1163,7 +1139,7 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_pipe_kernel(ConvArgs p, const _
   };
 
   stage_a(tile_begin, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
 #pragma unroll
   for (int i = 0; i < MW; ++i)
 #pragma unroll
@@ -1206,9 +1182,9 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_pipe_kernel(ConvArgs p, const _
 #pragma unroll
         for (int i = 0; i < MW; ++i)
           asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(afr[(q + 1) & 1][i]) : "v"(ap), "n"(i * 32 * ROWB));
-        asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
+        lgkm_wait<MW>();
       } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lgkm_wait<0>();
       }
       static_for<0, MW>([&](auto I) {
         constexpr int i = decltype(I)::value;
@@ -1228,7 +1204,7 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_pipe_kernel(ConvArgs p, const _
     // the hazard recogniser does not see MFMAs inside asm: let the last ones drain before VALU reads acc
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15"
                  : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // next tile has landed; older stores retired
+    vm_wait<0>();                                       // next tile has landed; older stores retired
     // hand the tile over: y = bf16(acc + bias), packed
 #pragma unroll
     for (int i = 0; i < MW; ++i)
@@ -1427,7 +1403,7 @@ __global__ __launch_bounds__(WS2_NT) void conv_ws2_kernel(ConvArgs p, const __bf
   };
 
   stage_a(tile_begin, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   int pb = 0, pcls = 0, pt0 = 0, pTc = 0;        // the tile whose sums waves 4-7 still hold
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
@@ -1477,11 +1453,11 @@ __global__ __launch_bounds__(WS2_NT) void conv_ws2_kernel(ConvArgs p, const __bf
 #pragma unroll
         for (int i = 0; i < MW; ++i)
           asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(afr[(q + 2) % 3][i]) : "v"(ap), "n"(i * 32 * ROWB));
-        asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
+        lgkm_wait<2 * MW>();                    // steps q + 1 and q + 2 in flight
       } else if constexpr (q + 1 < NSTEP) {
-        asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
+        lgkm_wait<MW>();
       } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lgkm_wait<0>();
       }
       // (clang's implicit capture in a generic lambda misses a variable that is only named in asm operands)
       constexpr int i0 = q - q, i1 = i0 + 1;
@@ -1501,7 +1477,7 @@ __global__ __launch_bounds__(WS2_NT) void conv_ws2_kernel(ConvArgs p, const __bf
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(acc[0]), "+v"(acc[1]));
     WS_T(c5);
     // next tile + this tile's epilogue operands have landed; older stores retired
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     WS_T(c6);
     if (rhalf == 0) epilogue(b, cls, t0, Tc);
     WS_T(c7);
@@ -1621,7 +1597,7 @@ __global__ __launch_bounds__(FO_NT) void conv1x1_fold_kernel(ConvArgs p, const _
     const int buf = (tile - tile_begin) & 1;
     const int b = tile / p.tiles_per_batch;
     const int t0 = (tile - b * p.tiles_per_batch) * FO_ROWS;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this tile has landed
+    vm_wait<0>();                                       // this tile has landed
     __syncthreads();                                    // ... for every wave; the other buffer is free again
     if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
     const unsigned char* ut = smem + (size_t)buf * FO_STAGE;
@@ -1701,6 +1677,7 @@ static int launch_conv1x1_fold(ConvArgs p, const void* zero_page, hipStream_t st
 // 64 w .. 64 w + 63); x tiles come through an LDS-DMA double buffer; transposed MFMA tiles, dropout hash and
 // ReLU on the accumulators, v_permlane32_swap pairing, 16-byte stores straight from registers.
 constexpr int K1_ROWS = 128, K1_NT = 512, K1_X = K1_ROWS * 128, K1_COUT = 512;
+constexpr int K1_STORES = (K1_ROWS / 32) * 2 * 2;      // stores per wave and tile: row groups x 2 channel tiles x 2
 
 __global__ __launch_bounds__(K1_NT) void conv_k1act_kernel(ConvArgs p, const __bf16* __restrict__ zero_page,
                                                            int tiles_per_wg) {
@@ -1759,19 +1736,14 @@ __global__ __launch_bounds__(K1_NT) void conv_k1act_kernel(ConvArgs p, const __b
   };
 
   stage(tile_begin, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the first tile, weights and biases; later tiles: counted wait at the END
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) asm volatile("" : "+v"(wfrag[c][kk]));      // (so that the compiler does not re-wait for them in the loop)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) asm volatile("" : "+v"(bval[c][e]));
-  }
+  // the first tile, weights and biases (pinned, so that the compiler does not re-wait for them in the loop); later tiles:
+  // counted wait at the END
+  vm_wait<0>(wfrag, bval);
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
     int b, t0;
     decode(tile, b, t0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait<0>();
     __builtin_amdgcn_s_barrier();                       // every wave's part of this tile landed; the other buffer is free again
     if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
     const unsigned char* xt = smem + (size_t)buf * K1_X;
@@ -1827,9 +1799,8 @@ __global__ __launch_bounds__(K1_NT) void conv_k1act_kernel(ConvArgs p, const __b
         }
       }
     }
-    // the next tile's DMA is older than this tile's 16 stores (4 row groups x 2 channel tiles x 2)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    // the next tile's DMA is older than this tile's stores
+    step_end_wait<K1_STORES>();
   }
 }
 
@@ -1860,6 +1831,7 @@ static int launch_conv_k1act(ConvArgs p, const void* zero_page, hipStream_t stre
 // by element -- out = bf16(bf16(acc + b) * keep_row + x) -- v_permlane32_swap pairing, 16-byte stores through a V#, one
 // counted wait per tile.
 constexpr int C64_ROWS = 64, C64_NT = 256, C64_TILE = C64_ROWS * 128;   // four waves: 32 output channels x 32 rows each
+constexpr int C64_STORES = 2;                                              // stores per wave and tile
 
 __global__ __launch_bounds__(C64_NT) void conv1x1_c64_kernel(ConvArgs p, int tiles_per_wg) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];   // 2 x [g tile | x tile], 64 rows x 128 B each
@@ -1908,16 +1880,12 @@ __global__ __launch_bounds__(C64_NT) void conv1x1_c64_kernel(ConvArgs p, int til
   };
 
   stage(tile_begin, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the first tile, weights and biases; later tiles: counted wait at the END
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) asm volatile("" : "+v"(wfrag[kk]));
-#pragma unroll
-  for (int e = 0; e < 16; ++e) asm volatile("" : "+v"(bval[e]));
+  vm_wait<0>(wfrag, bval);                              // the first tile, weights and biases; later tiles: counted wait at the END
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
     int b, t0;
     decode(tile, b, t0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait<0>();
     __builtin_amdgcn_s_barrier();                       // every wave's part of this tile landed; the other buffer is free again
     if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
     const unsigned char* gt = smem + (size_t)buf * 2 * C64_TILE;
@@ -1960,8 +1928,7 @@ __global__ __launch_bounds__(C64_NT) void conv1x1_c64_kernel(ConvArgs p, int til
       __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[0], (int)yp[1], (int)yp[2], (int)yp[3]}, ry, (int)vo, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[4], (int)yp[5], (int)yp[6], (int)yp[7]}, ry, (int)(vo + 32u), 0, 0);
     }
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");    // the next tile's DMA is older than this tile's two stores
+    step_end_wait<C64_STORES>();                        // the next tile's DMA is older than this tile's stores
   }
 }
 

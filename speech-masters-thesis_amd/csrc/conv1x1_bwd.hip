@@ -40,6 +40,7 @@ struct Bwd1x1Args {
 };
 
 constexpr int FB_ROWS = 128, FB_C = 128, FB_ROWB = FB_C * 2, FB_TILE = FB_ROWS * FB_ROWB, FB_NT = 512;
+constexpr int FB_NDX = 2 * 2;      // dx stores per wave and tile: two 32-row groups x 2
 
 __device__ __forceinline__ int fb_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
@@ -120,12 +121,12 @@ __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
   const int swz_r = fb_swz(r);                                   // rows 64 wm + 32 i + r share it
 
   if (tile_begin < tile_end) stage(tile_begin, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the first tile (and the weights); later tiles: counted wait at the END
+  vm_wait<0>();                                         // the first tile (and the weights); later tiles: counted wait at the END
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
     int b, t0;
     decode(tile, b, t0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait<0>();
     __builtin_amdgcn_s_barrier();                       // every wave's part of this tile landed; the other buffer is free again
     if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
     const unsigned char* dyt = smem + (size_t)buf * 2 * FB_TILE;
@@ -213,9 +214,8 @@ __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
     };
     if (wm == 0) { data_gradient(); weight_gradient(); }
     else { weight_gradient(); data_gradient(); }
-    // the next tile's 8 DMA instructions were issued before this tile's 4 dx stores: all but those stores are done
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    // the next tile's DMA instructions were issued before this tile's dx stores: all but those stores are done
+    step_end_wait<FB_NDX>();
   }
 
   // ---- partial dW / db of this workgroup -> slab[wg][blk = wm][plane][64][128]

@@ -89,7 +89,7 @@ __device__ __forceinline__ void untracked_dma16(const UntrackedRsrc& rs, unsigne
   // before an LDS-DMA reads it, and an SGPR written by the VALU (v_readfirstlane: the descriptor words, the LDS address) needs
   // five before a vector-memory instruction reads it.  s_nop 4 after the M0 write covers both.
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" : : "v"(voff), "s"(rs.w), "s"(m0v) : "memory");
-}   // writes M0 (not declarable as a clobber: reserved): do not mix with the ws_dma16 builtin in one kernel
+}
 
 // A 16-byte global load the COMPILER DOES NOT TRACK (scalar base + 32-bit lane offset).  While LDS-DMA is in flight hipcc
 // answers the first use of any ordinary load result with s_waitcnt vmcnt(0), which also drains the DMA of the NEXT tile and
@@ -101,11 +101,47 @@ __device__ __forceinline__ i32x4v untracked_load16(const void* sbase, unsigned v
   return v;
 }
 
-__device__ __forceinline__ void untracked_load8(const void* sbase, unsigned voff, unsigned& lo, unsigned& hi) {
-  typedef int i32x2v __attribute__((ext_vector_type(2)));
-  i32x2v v;
+typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32x2v untracked_load8(const void* sbase, unsigned voff) {
+  u32x2v v;
   asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %1, %2" : "=v"(v) : "v"(voff), "s"(sbase) : "memory");
-  lo = (unsigned)v[0]; hi = (unsigned)v[1];
+  return v;
+}
+
+// ---- counted waits: the one spelling of "wait, then these registers hold their data" ---------------------------------
+// The untracked loads above are invisible to hipcc's wait bookkeeping, so the kernels that use them wait themselves:
+// vm_wait<N> is `s_waitcnt vmcnt(N)`, N = the vector-memory instructions this wave issued after the newest one that must
+// have completed.  An asm load's destination counts as written when its statement ends, so every register an untracked load
+// filled must be listed here: each is pinned ("+v") right after the wait, and no instruction that reads, copies or spills it
+// can be scheduled above the wait.  lgkm_wait<N> is the same for the LDS / scalar-memory counter.  untracked_dma16 writes
+// M0, which cannot be declared as a clobber (reserved: an "m0" clobber only draws a warning), so it writes M0 in the same
+// statement that reads it; do not mix it with the ws_dma16 builtin in one kernel.
+template <typename T> __device__ __forceinline__ void pin_v(T& x) { asm volatile("" : "+v"(x)); }
+template <typename T, int N> __device__ __forceinline__ void pin_v(T (&a)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) pin_v(a[i]);
+}
+template <int N, typename... R> __device__ __forceinline__ void vm_wait(R&... regs) {
+  static_assert(0 <= N && N <= 63, "vmcnt is a 6-bit field on gfx9");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+  (pin_v(regs), ...);
+}
+template <int N, typename... R> __device__ __forceinline__ void lgkm_wait(R&... regs) {
+  static_assert(0 <= N && N <= 15, "lgkmcnt is a 4-bit field on gfx9");
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
+  (pin_v(regs), ...);
+}
+// Where the younger instructions are issued only on some paths (the last tile has no prefetch): vmcnt(N) if `counted`,
+// else vmcnt(0); the registers are pinned after either.
+template <int N, typename... R> __device__ __forceinline__ void vm_wait_or_drain(bool counted, R&... regs) {
+  if (counted) vm_wait<N>();
+  else vm_wait<0>();
+  (pin_v(regs), ...);
+}
+// End of a tile or step: nothing the compiler placed above may sink below the wait (and vice versa), then the wait.
+template <int N, typename... R> __device__ __forceinline__ void step_end_wait(R&... regs) {
+  __builtin_amdgcn_sched_barrier(0);
+  vm_wait<N>(regs...);
 }
 
 // lens[b] as a SCALAR load (the compiler picks a vector load for a pointer the kernel may also write through, tracks it,

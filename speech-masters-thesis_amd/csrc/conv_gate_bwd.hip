@@ -29,6 +29,7 @@ struct GateBwdArgs {
 };
 
 constexpr int GB_ROWS = 128, GB_C = 64, GB_NT = 512, GB_TILE = GB_ROWS * GB_C * 2, GB_STAGE = 2 * GB_TILE;
+constexpr int GB_NDX = 2;          // dx stores per wave and tile
 
 __device__ __forceinline__ int gb_swz(int row) { return ((row >> 1) & 3) << 1; }
 
@@ -103,14 +104,12 @@ __global__ __launch_bounds__(GB_NT) void conv_gate_bwd_kernel(GateBwdArgs p, con
   const int offb1 = GB_TILE + rb * 128 + (((col_b >> 3) ^ gb_swz(rb)) << 4) + (col_b & 7) * 2;
 
   if (tile_begin < tile_end) stage(tile_begin, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the first tile (and the weights); later tiles: counted wait at the END
-#pragma unroll
-  for (int kk = 0; kk < GB_C / 16; ++kk) asm volatile("" : "+v"(wfrag[kk]));
+  vm_wait<0>(wfrag);                                    // the first tile (and the weights); later tiles: counted wait at the END
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
     int b, t0;
     decode(tile, b, t0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait<0>();
     __builtin_amdgcn_s_barrier();                       // every wave's part of this tile landed; the other buffer is free again
     if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
     const unsigned char* base = smem + (size_t)buf * GB_STAGE;
@@ -163,9 +162,8 @@ __global__ __launch_bounds__(GB_NT) void conv_gate_bwd_kernel(GateBwdArgs p, con
       accw = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr, bfr, accw, 0, 0, 0);
       if (p.with_bias && wc == 0) accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr, ones, accb, 0, 0, 0);
     }
-    // the next tile's DMA was issued before this tile's 2 dx stores
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    // the next tile's DMA was issued before this tile's dx stores
+    step_end_wait<GB_NDX>();
   }
 
   // ---- partial dW / db -> slab[chunk = 2 wg + kh][plane][64 co][64 ci]

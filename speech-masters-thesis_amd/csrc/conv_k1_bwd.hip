@@ -8,7 +8,7 @@
 // A persistent workgroup streams 64-row tiles of dh (64 KiB) and x (8 KiB) through an LDS-DMA double buffer once:
 //   * data gradient: four 32 x 32 tiles of dx, each computed by TWO waves that split the 512 output channels (the
 //     contraction) in halves and keep their W^T fragments in registers (fetching them through L1 per tile left the
-//     kernel latency-bound: 1170 vs 695 us at the top level, tools/ablate_k1bwd.sh); the upper half hands its
+//     kernel latency-bound: 1170 vs 695 us at the top level, measured with an ablation build); the upper half hands its
 //     partial tile to the lower one through LDS (fixed order: bitwise reproducible), which adds the residual in
 //     registers, pairs lanes with v_permlane32_swap and stores 16-byte pieces;
 //   * weight gradient: wave w owns output channels 64 w .. 64 w + 63 (4 accumulator tiles + 2 bias tiles kept in
@@ -85,6 +85,7 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
   const int xrow = 8 * wave + (lane >> 3);
   const unsigned xoff0 = (unsigned)xrow * pitch_x + (unsigned)(((lane & 7) ^ kb_swz_x(xrow)) << 4);
   constexpr int KB_NDMA = KB_ROWS / (KB_NT / 64) + 1;       // LDS-DMA instructions per wave and tile
+  constexpr int KB_NDX = 2;                                 // dx stores per wave and tile (waves 0..3)
   auto stage = [&](int tile, int buf) {
     int b, t0;
     decode(tile, b, t0);
@@ -124,16 +125,15 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
   float* red = reinterpret_cast<float*>(smem + 2 * KB_STAGE) + (wave & 3) * 1024;   // [16 e][64 lanes] of tile (di, dc)
 
   if (tile_begin < tile_end) stage(tile_begin, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the first tile (and the weights); later tiles: counted waits
-#pragma unroll
-  for (int kk = 0; kk < KB_CO / 32; ++kk) asm volatile("" : "+v"(wfrag[kk]));   // tell the compiler the weight loads are done: it
-                                                       // would otherwise re-wait for them (vmcnt(18) .. vmcnt(3)) inside the loop
+  // the first tile (and the weights); later tiles: counted waits.  Pinning the weights tells the compiler their loads are
+  // done: it would otherwise re-wait for them (vmcnt(18) .. vmcnt(3)) inside the loop
+  vm_wait<0>(wfrag);
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
     int b, t0;
     decode(tile, b, t0);
     const bool more = tile + 1 < tile_end;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait<0>();
     __builtin_amdgcn_s_barrier();                       // every wave's part of this tile landed; the other buffer is free again
     const unsigned char* base = smem + (size_t)buf * KB_STAGE;
 
@@ -153,34 +153,29 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
       // residual rows of THIS tile (waves 0..3: channels 32 dc + 8 g + 4 hh + 0..3 of row 32 di + r), THEN the prefetch:
       // vector memory completes in issue order, so what this tile still needs must be older than the next tile's DMA.
       // (Issued here, after the MFMAs, the eight residual registers are not live across them: before them the kernel spills.)
-      unsigned rvw[4][2];
+      u32x2v rvw[4];
       if (!kh) {
         const unsigned char* rbase = reinterpret_cast<const unsigned char*>(p.res) + ((long long)b * p.res_bs) * 2;
         asm volatile("" : "+s"(rbase));
         const unsigned ro = (unsigned)min(t, p.T - 1) * (unsigned)p.ldres * 2u + (unsigned)(32 * dc + 4 * hh) * 2u;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) untracked_load8(rbase, ro + 16u * g, rvw[g][0], rvw[g][1]);
+        for (int g = 0; g < 4; ++g) rvw[g] = untracked_load8(rbase, ro + 16u * g);
       }
       if (more) stage(tile + 1, buf ^ 1);
       if (kh) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) red[e * 64 + lane] = accd[e];
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      lgkm_wait<0>();
       __builtin_amdgcn_s_barrier();                     // partial tiles of waves 4..7 are in LDS
       if (!kh) {
         const int len = p.lens ? scalar_load_i32(p.lens + b) : 0x7fffffff;
         const float keep_row = (t >= len) ? 0.f : 1.f;
         // the residual loads are older than the prefetch: all but its KB_NDMA instructions are done
-        if (more) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(KB_NDMA) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vm_wait_or_drain<KB_NDMA>(more, rvw);
         bf16x4 rv[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          asm volatile("" : "+v"(rvw[g][0]), "+v"(rvw[g][1]));          // values as of AFTER the wait
-          typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-          rv[g] = __builtin_bit_cast(bf16x4, u32x2{rvw[g][0], rvw[g][1]});
-        }
+        for (int g = 0; g < 4; ++g) rv[g] = __builtin_bit_cast(bf16x4, rvw[g]);
 #pragma unroll
         for (int e = 0; e < 16; ++e) accd[e] += red[e * 64 + lane];      // lower half + upper half, always in this order
         unsigned yp[8];
@@ -232,8 +227,8 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
     }
     // the prefetch is older than this tile's two dx stores (waves 0..3) / is the youngest (waves 4..7)
     __builtin_amdgcn_sched_barrier(0);
-    if (!kh) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (!kh) vm_wait<KB_NDX>();
+    else vm_wait<0>();
   }
 
   // ---- partial dW / db of this workgroup -> slab[wg][blk = wave][plane][64 co][64 ci]

@@ -27,10 +27,6 @@
 
 #include "conv_common.h"
 
-#ifndef KG_ABL
-#define KG_ABL 0      // timing experiments only (results invalid): 1 weights loaded once, 2 no gate math, 4 no z stores
-#endif
-
 namespace smt {
 
 struct K3GateArgs {
@@ -43,6 +39,7 @@ struct K3GateArgs {
 
 constexpr int KG_ROWS = 128, KG_NT = 512, KG_U = KG_ROWS * 256, KG_X = KG_ROWS * 128, KG_BIAS = 4 * 128 * 4,
               KG_LDS = 2 * KG_U + 2 * KG_X + KG_BIAS;       // [u buf 0 | u buf 1 | x buf 0 | x buf 1 | b3 + b1 of the four branches]
+constexpr int KG_Z_STORES = 2, KG_G_STORES = 1;             // stores per wave and 32-row group: z (every step), g (gate step)
 
 __device__ __forceinline__ float kg_lo(unsigned v) { return __uint_as_float(v << 16); }
 __device__ __forceinline__ float kg_hi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
@@ -131,7 +128,7 @@ __global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, const 
   stage_u(tile_begin, 0, 0);
   stage_x(tile_begin, 0);
   load_w(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the first slice, x tile and weights; later steps wait at their END
+  vm_wait<0>(wf, w2f);                                      // the first slice, x tile and weights; later steps wait at their END
   int ubuf = 0;
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int xbuf = (tile - tile_begin) & 1;
@@ -143,7 +140,7 @@ __global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, const 
     for (int d = 0; d < 4; ++d) {
       // every wave's slice of this step landed (its own counted wait at the end of the previous step) and every wave is
       // done reading the buffers the prefetch below overwrites
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      lgkm_wait<0>();
       __builtin_amdgcn_s_barrier();
       const bool more = d < 3 || tile + 1 < tile_end;
       if (more) {
@@ -170,7 +167,7 @@ __global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, const 
           const bf16x8 bv = *reinterpret_cast<const bf16x8*>(xt + row * 128 + (((2 * kk + hh) ^ ((row >> 1) & 7)) << 4));
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2f[kk], bv, acc, 0, 0, 0);
         }
-        if (i == 1 && more && !(KG_ABL & 1)) {
+        if (i == 1 && more) {
           __builtin_amdgcn_sched_barrier(0);                  // after the MFMAs that read the weight registers ...
           load_w((d + 1) & 3);                                // ... fetch the next branch's into them (12 untracked loads)
           __builtin_amdgcn_sched_barrier(0);
@@ -195,12 +192,12 @@ __global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, const 
             auto sw = __builtin_amdgcn_permlane32_swap(yp[4 * h2 + dd], yp[4 * h2 + 2 + dd], false, false);
             yp[4 * h2 + dd] = sw[0]; yp[4 * h2 + 2 + dd] = sw[1];
           }
-        if (!(KG_ABL & 4)) {                                  // rows >= T are out of the V#'s range: dropped, but ISSUED
+        {                                                     // rows >= T are out of the V#'s range: dropped, but ISSUED
           const unsigned vo = (unsigned)t * pitch_z + (unsigned)(16 * wn + 8 * hh) * 2u;   // 8 consecutive t channels, then the s ones
           __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[0], (int)yp[1], (int)yp[2], (int)yp[3]}, rz, (int)vo, 0, 0);
           __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[4], (int)yp[5], (int)yp[6], (int)yp[7]}, rz, (int)(vo + 128u), 0, 0);
         }
-        if (d == 3 && !(KG_ABL & 2)) {
+        if (d == 3) {
           // the gate, with the arithmetic of gate_mix_fwd_kernel on the bf16-rounded z (what backward will read)
           unsigned gq[4];
 #pragma unroll
@@ -242,12 +239,11 @@ __global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, const 
                                                  (int)((unsigned)t * pitch_g + (unsigned)(16 * wn + 8 * hh) * 2u), 0, 0);
         }
       }
-      // The slice and weights of the next step were issued BEFORE the last row group's stores (2 of z, + 1 of g in the gate
-      // step): everything older than those stores is done after this wait; the stores drain under the next step.
-      __builtin_amdgcn_sched_barrier(0);
-      if (KG_ABL & 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if (d == 3 && !(KG_ABL & 2)) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+      // The slice and weights of the next step were issued BEFORE the last row group's stores (z, + g in the gate step):
+      // everything older than those stores is done after this wait; the stores drain under the next step.  The weight
+      // registers are pinned by the wait: the next step's MFMAs read them.
+      if (d == 3) step_end_wait<KG_Z_STORES + KG_G_STORES>(wf, w2f);
+      else step_end_wait<KG_Z_STORES>(wf, w2f);
       ubuf ^= 1;
     }
   }

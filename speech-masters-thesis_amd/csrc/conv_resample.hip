@@ -27,6 +27,7 @@ struct RsArgs {
 };
 
 constexpr int RS_NT = 512;
+constexpr int RS_STORES = 2;                                 // stores per rs_store (one 32-row group of a wave)
 typedef unsigned rs_u32x4 __attribute__((ext_vector_type(4)));
 
 // pack the 16 accumulator values of a lane (+ bias, row mask) into two 16-byte pieces of 8 consecutive channels each
@@ -52,7 +53,6 @@ __device__ __forceinline__ void rs_store(const f32x16& acc, const float* bval, f
 // Round 3: both tile loops own their vector-memory waits (conv_common.h, conv_k3gate.hip): untracked LDS-DMA through a V#
 // (rows before the item wrap to huge offsets, rows >= len are beyond it: both read as zero), scalar lens loads, one counted
 // wait per tile that leaves the tile's stores in flight.
-#define RS_MARK_LOADED(arr, n) _Pragma("unroll") for (int i_ = 0; i_ < (n); ++i_) asm volatile("" : "+v"((arr)[i_]))
 
 // ------------------------------------------------------------------------------------------ transposed, C_in = 64
 constexpr int CT_TM = 128;                                   // input rows per tile (256 output rows)
@@ -117,13 +117,12 @@ __global__ __launch_bounds__(RS_NT) void convt4s2_kernel(RsArgs p, const __bf16*
   };
 
   stage(tile_begin, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the first tile, weights, biases; later tiles: counted wait at the END
-  RS_MARK_LOADED(wa, 4); RS_MARK_LOADED(wb, 4); RS_MARK_LOADED(bval, 16);
+  vm_wait<0>(wa, wb, bval);                                 // the first tile, weights, biases; later tiles: counted wait at the END
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
     int b, m0;
     decode(tile, b, m0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait<0>();
     __builtin_amdgcn_s_barrier();                             // every wave's part of this tile landed; the other buffer is free again
     if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
     const unsigned char* xt = smem + (size_t)buf * CT_BUF;
@@ -149,9 +148,8 @@ __global__ __launch_bounds__(RS_NT) void convt4s2_kernel(RsArgs p, const __bf16*
       const int m = m0 + lm, t = 2 * m + ph;
       rs_store(acc, bval, t < len_out ? 1.f : 0.f, ry, (unsigned)t * pitch_y + (unsigned)(cg * 32 + 8 * hh) * 2u);
     }
-    // the next tile's DMA is older than this tile's 2 RGW stores
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * RGW) : "memory");
+    // the next tile's DMA is older than this tile's stores
+    step_end_wait<RS_STORES * RGW>();
   }
 }
 
@@ -216,15 +214,12 @@ __global__ __launch_bounds__(RS_NT) void conv4s2_kernel(RsArgs p, const __bf16* 
   };
 
   stage(tile_begin, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the first tile, weights, biases; later tiles: counted wait at the END
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { RS_MARK_LOADED(wf[j], KS); }
-  RS_MARK_LOADED(bval, 16);
+  vm_wait<0>(wf, bval);                                     // the first tile, weights, biases; later tiles: counted wait at the END
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
     int b, t0;
     decode(tile, b, t0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait<0>();
     __builtin_amdgcn_s_barrier();
     if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
     const unsigned char* xt = smem + (size_t)buf * BUF;
@@ -245,9 +240,8 @@ __global__ __launch_bounds__(RS_NT) void conv4s2_kernel(RsArgs p, const __bf16* 
     const int len_out = p.lens_out ? scalar_load_i32(p.lens_out + b) : 0x7fffffff;
     const __amdgpu_buffer_rsrc_t ry = ws_rsrc(p.y, (long long)b * p.y_bs * 2, (unsigned)p.Tout * pitch_y);
     rs_store(acc, bval, t < len_out ? 1.f : 0.f, ry, (unsigned)t * pitch_y + (unsigned)(cg * 32 + 8 * hh) * 2u);
-    // the next tile's DMA is older than this tile's 2 stores
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    // the next tile's DMA is older than this tile's stores
+    step_end_wait<RS_STORES>();
   }
 }
 

@@ -245,11 +245,6 @@ __device__ __forceinline__ bf16x8 frag_tr_swz(const unsigned char* tile, int row
   return __builtin_bit_cast(bf16x8, v);
 }
 
-#ifndef SMT_WABL
-#define SMT_WABL 0   // ablation build switches (tools/ablate_wgrad.sh): 1 stage once, 2 no fragment reads, 4 no MFMA
-#endif
-constexpr int WABL = SMT_WABL;
-
 template <int NT>
 __global__ __launch_bounds__(512) void conv_wgrad_dma_kernel(WgradArgs p, const __bf16* __restrict__ zero_page) {
   typedef __bf16 T;
@@ -351,31 +346,29 @@ __global__ __launch_bounds__(512) void conv_wgrad_dma_kernel(WgradArgs p, const 
   // to arrive, so one tile of prefetch leaves the kernel waiting on latency (measured: 176 us per launch = 36 tiles x 2.5 us x
   // two rounds of workgroups).  Its DMA count per wave and tile is a constant (2 dy + 4 x pieces), so the counted wait can leave
   // the newest tile in flight.  The other modes keep two buffers (their tile size varies with taps and dilation).
+  constexpr int WIN_NDMA = (R / 8 + R / 4) / (NTHR / 64);   // DMA instructions per wave and tile in window mode (taps = 1)
   const int nbuf = p.win ? 3 : 2;
   stage(t_begin, 0);
-  if (p.win && t_begin + R < t_end) { stage(t_begin + R, 1); asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (p.win && t_begin + R < t_end) { stage(t_begin + R, 1); vm_wait<WIN_NDMA>(); }
+  else vm_wait<0>();
   int it = 0;
   for (int t0 = t_begin; t0 < t_end; t0 += R, ++it) {
     const int buf = it % nbuf;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lgkm_wait<0>();
     __builtin_amdgcn_s_barrier();          // tile `it` has landed for every wave (each waited at the end of the previous
                                            // iteration); the buffer read in the previous iteration is free
     const int ahead = nbuf - 1;
-    const bool more = t0 + ahead * R < t_end && !((WABL & 1) && it > 0);
+    const bool more = t0 + ahead * R < t_end;
     if (more) stage(t0 + ahead * R, (it + ahead) % nbuf);
     const unsigned char* dyt = smem + (size_t)buf * buf_bytes + dyoff;
     const unsigned char* xbase = smem + (size_t)buf * buf_bytes + DY_BYTES;
-    bf16x8 a0, b0;
-    if (WABL & 2) { a0 = tr2(dyt, 0, 4 * DYB); b0 = tr2(xbase + xoff[0], 0, 4 * XB); }
 #pragma unroll
     for (int k0 = 0; k0 < R; k0 += 16) {
-      bf16x8 a = (WABL & 2) ? a0 : tr2(dyt, k0 * DYB, 4 * DYB);
+      const bf16x8 a = tr2(dyt, k0 * DYB, 4 * DYB);
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         if (j < ntaps) {
-          bf16x8 bfrag = (WABL & 2) ? b0 : tr2(xbase + xoff[j], k0 * XB, 4 * XB);
-          if (WABL & 4) { asm volatile("" :: "v"(a), "v"(bfrag)); continue; }
+          const bf16x8 bfrag = tr2(xbase + xoff[j], k0 * XB, 4 * XB);
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bfrag, acc[j], 0, 0, 0);
         } else if (j == ntaps && bias_plane) {
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, acc[j], 0, 0, 0);
@@ -383,9 +376,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_dma_kernel(WgradArgs p, const 
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    // the next tile must have landed; in window mode the one after it (6 instructions per wave) may still be in flight
-    if (p.win && more) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // the next tile must have landed; in window mode the one after it may still be in flight
+    vm_wait_or_drain<WIN_NDMA>(p.win && more);
   }
   const int planes = ntaps + 1;
   float* out = p.slab + ((size_t)cgl * nblk + blk) * (size_t)planes * CB * CIB;
@@ -492,11 +484,12 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
   const int xoff = SH_DY + lrow * XB + (((colx >> 3) ^ ((lrow & 3) << 2)) << 4) + (colx & 7) * 2;
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   // The three fragments of k-step k0+1 are requested (asm, so that the request stays where it is written) before the
-  // MFMAs of k-step k0; `s_waitcnt lgkmcnt(6)` then retires exactly the older six reads (LDS returns in order).  The
-  // fragments are operands of the wait so that nothing that uses them can be scheduled above it.
+  // MFMAs of k-step k0; `s_waitcnt lgkmcnt(SH_NREAD)` then retires exactly the older six reads (LDS returns in order).  The
+  // fragments are pinned by the wait so that nothing that uses them can be scheduled above it.
   typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
   struct Frags { u32x2 a0, a1, p0, p1, q0, q1; };
+  constexpr int SH_NREAD = 6;                      // ds_read instructions per request
   auto request = [&](Frags& f, unsigned base, int k0) {
     const unsigned pa = base + dyoff + k0 * 16 * DYB, px = base + xoff + k0 * 16 * XB;
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.a0) : "v"(pa));
@@ -510,7 +503,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
   if (tile_begin < tile_end) stage(tile_begin, 0);
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     __syncthreads();                       // this tile has landed for every wave; the other buffer is free
     if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
     const unsigned base = lds0 + (unsigned)buf * SH_STAGE;
@@ -521,9 +514,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
       Frags& f = fr[k0 & 1];
       if (k0 + 1 < SH_R / 16) {
         request(fr[(k0 + 1) & 1], base, k0 + 1);
-        asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f.a0), "+v"(f.a1), "+v"(f.p0), "+v"(f.p1), "+v"(f.q0), "+v"(f.q1) :: "memory");
+        lgkm_wait<SH_NREAD>(f.a0, f.a1, f.p0, f.p1, f.q0, f.q1);
       } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f.a0), "+v"(f.a1), "+v"(f.p0), "+v"(f.p1), "+v"(f.q0), "+v"(f.q1) :: "memory");
+        lgkm_wait<0>(f.a0, f.a1, f.p0, f.p1, f.q0, f.q1);
       }
       const u32x4 aw = {f.a0[0], f.a0[1], f.a1[0], f.a1[1]};
       const bf16x8 a = __builtin_bit_cast(bf16x8, aw);

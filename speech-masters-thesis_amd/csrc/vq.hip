@@ -20,7 +20,7 @@
 // The [N, K] distance matrix is never materialised.
 #include <algorithm>
 
-#include "smt_common.h"
+#include "conv_common.h"
 
 #ifndef VQ_ABL
 #define VQ_ABL 0      // timing experiments (tools/ablate_vq.sh, results invalid): 1 no MFMAs, 2 no re-staging of the codebook,
@@ -222,7 +222,6 @@ __device__ __forceinline__ void vq_stage(const __bf16* kh, const __bf16* kl, con
     for (int i = 0; i < SUP / 64; ++i) vq_dma4(nkhalf + sc * SUP + 64 * i + lane, buf + 2 * G::TILE_BYTES + 256 * i);
   }
 }
-__device__ __forceinline__ void vq_stage_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // this lane's share of row `row` (dims 16 s + 8 h .. + 7 for every k-step s), centred and split; returns its share of
 // |x~|^2.  All loads are issued before the first use (callers pass a row index that is always in range).
@@ -350,7 +349,7 @@ __global__ __launch_bounds__(128 * VQ_MAXRG) void vq_search_kernel(const float* 
     xx = vq_load_row<D>(x, mu, row, h, xh[0], xl[0]);
     xx += __shfl_xor(xx, 32, 64);
   }
-  vq_stage_wait();
+  vm_wait<0>();
   __syncthreads();
   VQ_STAMP(1);
 
@@ -386,11 +385,11 @@ __global__ __launch_bounds__(128 * VQ_MAXRG) void vq_search_kernel(const float* 
   };
   for (int sc = 0; sc < nsc; sc += 2) {
     score_step(buf0, sc);
-    vq_stage_wait();                                        // step sc + 1 (issued one scoring phase ago) has landed in buf1
+    vm_wait<0>();                                           // step sc + 1 (issued one scoring phase ago) has landed in buf1
     __syncthreads();                                        // buf0 released
     if (sc + 2 < nsc) vq_stage<D, SUP>(kh, kl, nkhalf, sc + 2, buf0, nw, wave, lane);
     score_step(buf1, sc + 1);
-    vq_stage_wait();
+    vm_wait<0>();
     __syncthreads();                                        // buf1 released, step sc + 2 landed in buf0
     if (sc + 3 < nsc) vq_stage<D, SUP>(kh, kl, nkhalf, sc + 3, buf1, nw, wave, lane);   // lands while step sc + 2 is scored
   }
@@ -493,7 +492,7 @@ __global__ __launch_bounds__(128) void vq_candidates_kernel(const float* __restr
     vq_stage<D, SUP>(kh, kl, nkhalf, sp * per, smem, 2, wave, lane);
     vq_bf16x8 xh[1][G::NS], xl[1][G::NS];
     (void)vq_load_row<D>(x, mu, (long long)q_rows[qi], h, xh[0], xl[0]);
-    vq_stage_wait();
+    vm_wait<0>();
     __syncthreads();
     for (int i = 0; i < per; ++i) {
       const int buf = i & 1, sc = sp * per + i;
@@ -508,7 +507,7 @@ __global__ __launch_bounds__(128) void vq_candidates_kernel(const float* __restr
           if (pos < VQ_CAPS) l_code[j][pos] = cbase + 8 * (r >> 2) + (r & 3);
         }
       }
-      vq_stage_wait();
+      vm_wait<0>();
       __syncthreads();
     }
     if (threadIdx.x < 32 && rg * 32 + (int)threadIdx.x < n_q) {
