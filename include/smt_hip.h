@@ -472,6 +472,17 @@ int smt_glow_prior_logp(const float* x_m, const float* x_logs, const float* z, f
 int smt_glow_align_index(const float* path, int* idx, float* durations, int batch, int t_x, int t_y, smt_stream_t stream);
 int smt_glow_align_gather(const float* x, const int* idx, float* z, int batch, int t_x, int t_y, int dim, smt_stream_t stream);
 int smt_glow_align_scatter(const float* dz, const int* idx, float* dx, int batch, int t_x, int t_y, int dim, smt_stream_t stream);
+/* Inference durations (glow_tts.py:148-156, `infer_step`; ABI 5).  logw [batch, t_x], lens [batch] (int32) ->
+ * w [batch, t_x] = ceil(exp(logw) length_scale) for t < lens[b], else 0 (logw is never read at or past lens[b]);
+ * cum [batch, t_x] (int32) = inclusive prefix sum of w; z_lens[b] = (max(sum w, 1) / n_sqz) n_sqz.  An item with a non-finite
+ * w or sum w > 2^24 (where the reference's fp32 cumsum stops being exact) gets z_lens[b] = -1 and cum = 0.
+ * duration_index: idx [batch, t_out] (int32) = the token j < lens[b] with cum[b, j - 1] <= f < cum[b, j] for frames
+ * f < z_lens[b] (-1 where no token covers f, and past z_lens[b]) -- the frame -> token convention of smt_glow_align_index,
+ * so smt_glow_align_gather expands the prior statistics (the reference's generate_path + matmul, :157-163). */
+int smt_glow_durations(const float* logw, const int* lens, int batch, int t_x, float length_scale, int n_sqz, float* w,
+                       int* z_lens, int* cum, smt_stream_t stream);
+int smt_glow_duration_index(const int* cum, const int* lens, const int* z_lens, int batch, int t_x, int t_out, int* idx,
+                            smt_stream_t stream);
 /* MLE loss pieces (glow_tts.py:115-119): sums[0] = sum z_logs, sums[1] = sum exp(-2 z_logs) (z - z_m)^2 over n elements
  * (z_logs NULL = zeros); bwd with the DEVICE scalar coef: dz = coef exp(-2 zl)(z - zm), dz_m = -dz, dz_logs = coef (1 - ...). */
 size_t smt_glow_mle_workspace_bytes(int64_t n);

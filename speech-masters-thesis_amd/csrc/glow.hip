@@ -10,6 +10,7 @@
 //   attention    softmax(q k^T / sqrt(d) + relative keys, -1e4 fill), dropout, p v + relative values   submodules.py:463-512
 //   prior_logp   log N(z_j; m_i, exp(logs_i)) for every (token i, frame j)    glow_tts.py:87-95
 //   align        z_m = x_m[path], z_logs = x_logs[path], durations            glow_tts.py:99-101
+//   durations    ceil(exp(logw) length_scale), prefix sums, frame -> token    glow_tts.py:148-156 (inference)
 //   loss         MLE + duration losses                                        glow_tts.py:115-121
 // Reductions over rows are two-stage with a fixed order (bitwise reproducible); the only atomics are integer.
 #include <math.h>
@@ -495,6 +496,83 @@ __global__ __launch_bounds__(GL_NT) void gl_align_scatter_kernel(const float* __
   }
 }
 
+// ------------------------------------------------------------------------------------------------ durations -> frames (inference)
+// Largest total frame count of an item: past 2^24 the reference's fp32 cumsum (generate_path) is no longer exact.
+constexpr long long GL_MAX_FRAMES = 1ll << 24;
+// One workgroup per item.  w[b, t] = ceil(exp(logw) length_scale) for t < len, else 0; cum[b, t] = inclusive prefix sum of w
+// (int32); z_lens[b] = (max(sum w, 1) / n_sqz) n_sqz, or -1 (and cum = 0) when a valid w is not finite or sum w > 2^24.
+// Chunks of GL_NT tokens: a wave64 scan (shfl_up), the four wave totals through LDS, and the running carry of the earlier chunks.
+// logw is never read at or past len.
+__global__ __launch_bounds__(GL_NT) void gl_durations_kernel(const float* __restrict__ logw, const int* __restrict__ lens, int Tx,
+                                                             float length_scale, int n_sqz, float* __restrict__ w,
+                                                             int* __restrict__ z_lens, int* __restrict__ cum) {
+  __shared__ long long wave_tot[GL_NT / 64];
+  __shared__ int wave_bad[GL_NT / 64];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int len = min(max(lens[b], 0), Tx);
+  const size_t row = (size_t)b * Tx;
+  long long carry = 0;
+  int bad = 0;
+  for (int t0 = 0; t0 < Tx; t0 += GL_NT) {
+    const int t = t0 + threadIdx.x;
+    float wt = 0.f;
+    long long v = 0;
+    if (t < len) {
+      wt = ceilf(expf(logw[row + t]) * length_scale);
+      if (wt <= (float)GL_MAX_FRAMES) v = (long long)wt;            // false for NaN and +inf as well
+      else bad = 1;
+    }
+    if (t < Tx) w[row + t] = wt;
+    long long s = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long u = __shfl_up(s, o, 64);
+      if (lane >= o) s += u;
+    }
+    if (lane == 63) wave_tot[wv] = s;
+    const int any_bad = __any(bad);
+    if (lane == 0) wave_bad[wv] = any_bad;
+    __syncthreads();
+    long long before = carry, chunk = 0;
+#pragma unroll
+    for (int k = 0; k < GL_NT / 64; ++k) {
+      if (k < wv) before += wave_tot[k];
+      chunk += wave_tot[k];
+      bad |= wave_bad[k];
+    }
+    if (t < Tx) cum[row + t] = (int)min(before + s, GL_MAX_FRAMES + 1);
+    carry += chunk;
+    __syncthreads();                                                 // wave_tot / wave_bad are rewritten by the next chunk
+  }
+  const bool invalid = bad || carry > GL_MAX_FRAMES;
+  if (invalid)                                                       // the same thread overwrites the elements it wrote
+    for (int t = threadIdx.x; t < Tx; t += GL_NT) cum[row + t] = 0;
+  if (threadIdx.x == 0) z_lens[b] = invalid ? -1 : (int)((max(carry, 1ll) / n_sqz) * n_sqz);
+}
+// idx[b, f] = the token j < len with cum[b, j - 1] <= f < cum[b, j] (binary search) for f < z_lens[b]; -1 past z_lens[b] and
+// where no token covers f (sum w = 0 with z_lens = 1: the reference's path column is empty there)
+__global__ __launch_bounds__(GL_NT) void gl_duration_index_kernel(const int* __restrict__ cum, const int* __restrict__ lens,
+                                                                  const int* __restrict__ z_lens, int B, int Tx, int Tout,
+                                                                  int* __restrict__ idx) {
+  const long long total = (long long)B * Tout;
+  for (long long e = (long long)blockIdx.x * GL_NT + threadIdx.x; e < total; e += (long long)gridDim.x * GL_NT) {
+    const int b = (int)(e / Tout), f = (int)(e % Tout);
+    const int len = min(max(lens[b], 0), Tx);
+    int tok = -1;
+    if (f < z_lens[b] && len > 0) {
+      const int* cb = cum + (size_t)b * Tx;
+      int lo = 0, hi = len - 1;                                      // the first j in [lo, hi] with cum[j] > f, if any
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cb[mid] > f) hi = mid;
+        else lo = mid + 1;
+      }
+      tok = cb[lo] > f ? lo : -1;
+    }
+    idx[e] = tok;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ losses
 // per-workgroup partials of sum z_logs, sum exp(-2 z_logs) (z - z_m)^2 over all (b, j, d); and of sum_{t < len} (logw - logw_dec)^2
 __global__ __launch_bounds__(GL_NT) void gl_mle_part_kernel(const float* __restrict__ z, const float* __restrict__ zm,
@@ -767,6 +845,27 @@ extern "C" int smt_glow_align_scatter(const float* dz, const int* idx, float* dx
   SMT_CHECK_ARG(dz && idx && dx, "smt_glow_align_scatter: null pointer");
   gl_align_scatter_kernel<<<gl_grid((long long)batch * t_x * dim), GL_NT, 0, stream>>>(dz, idx, dx, batch, t_x, t_y, dim);
   SMT_CHECK_LAUNCH("glow_align_scatter");
+  return 0;
+}
+
+extern "C" int smt_glow_durations(const float* logw, const int* lens, int batch, int t_x, float length_scale, int n_sqz, float* w,
+                                  int* z_lens, int* cum, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (batch <= 0) return 0;
+  SMT_CHECK_ARG(logw && lens && w && z_lens && cum && t_x >= 0 && n_sqz >= 1 && length_scale > 0.f,
+                "smt_glow_durations: null pointer / bad sizes / length_scale <= 0");
+  gl_durations_kernel<<<batch, GL_NT, 0, stream>>>(logw, lens, t_x, length_scale, n_sqz, w, z_lens, cum);
+  SMT_CHECK_LAUNCH("glow_durations");
+  return 0;
+}
+
+extern "C" int smt_glow_duration_index(const int* cum, const int* lens, const int* z_lens, int batch, int t_x, int t_out, int* idx,
+                                       smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if ((long long)batch * t_out <= 0) return 0;
+  SMT_CHECK_ARG(cum && lens && z_lens && idx && t_x >= 0, "smt_glow_duration_index: null pointer / bad sizes");
+  gl_duration_index_kernel<<<gl_grid((long long)batch * t_out), GL_NT, 0, stream>>>(cum, lens, z_lens, batch, t_x, t_out, idx);
+  SMT_CHECK_LAUNCH("glow_duration_index");
   return 0;
 }
 

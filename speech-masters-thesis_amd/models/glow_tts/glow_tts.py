@@ -1,7 +1,7 @@
 """GlowTTS (reference models/glow_tts/glow_tts.py:12-168): text encoder -> prior statistics, flow decoder -> latent, monotonic
 alignment search between them ON THE DEVICE (the reference round-trips through numpy every step, glow_tts.py:87-97), MLE and
-duration losses.  Single speaker.  Activations are channels-last; the public tensors keep the reference's layouts
-(spectrograms [B, n_mels, T])."""
+duration losses; synthesis from token ids (``infer`` / ``infer_step``).  Single speaker.  Activations are channels-last; the
+public tensors keep the reference's layouts (spectrograms [B, n_mels, T])."""
 import math
 
 import torch
@@ -79,11 +79,102 @@ class GlowTTS(TokenToSpectrogramModel):
                 z_lens = ((torch.clamp_min(w.sum(1), 1).long() // n_sqz) * n_sqz).to(torch.int32)
                 eps = torch.randn_like(z_m) if noise is None else noise.transpose(1, 2).contiguous()
                 t_out = int(z_lens.max())              # sequence_mask(z_lengths, None): the mask is as long as the longest item
-                z_mask = submodules.sequence_mask(z_lens, t_out).unsqueeze(-1).float()
-                z_enc = ((z_m + (torch.exp(z_logs) if z_logs is not None else 1.0) * eps)[:, :t_out] * z_mask).contiguous()
+                z_enc = self._prior_sample(z_m, z_logs, eps, z_lens, t_out)
                 yh_rows, _ = self.decoder(z_enc, z_lens, reverse=True)
                 yh = yh_rows.transpose(1, 2)
         denom = (y_lens.sum() * z_dec.shape[2]).float()
         l_mle = glow.mle_loss(z_dec, z_m, z_logs, torch.sum(logdet), denom)
         l_length = glow.length_loss(logw_enc, durations, x_lens, x_lengths.sum().float())
         return {"loss_mle": l_mle, "loss_length": l_length, "loss": l_mle + l_length, "yh": yh}, {}
+
+    @staticmethod
+    def _prior_sample(z_m, z_logs, eps, z_lens, t_out, noise_scale=1.0):
+        """z = (z_m + exp(z_logs) noise_scale eps) on the first z_lens[b] frames of [B, T, n_mels] rows, exactly 0 after
+        (glow_tts.py:110, 165); rows of eps past z_lens[b] are selected away, so they may hold anything, NaN included."""
+        scale = torch.exp(z_logs) if z_logs is not None else 1.0
+        if noise_scale != 1.0:
+            scale = scale * noise_scale
+        keep = submodules.sequence_mask(z_lens, t_out).unsqueeze(-1)
+        return torch.where(keep, (z_m + scale * eps)[:, :t_out], 0.0).contiguous()
+
+    @torch.no_grad()
+    def infer(self, x, x_lengths=None, *, noise_scale=1.0, length_scale=1.0, noise=None):
+        """Mels from token ids (glow_tts.py:133-168 from the token ids on): x [B, Tx] int64, ragged with x_lengths [B] ->
+        (yh [B, n_mels, T_out] fp32, y_lengths [B] int64), T_out = max y_lengths and yh exactly 0 at or past y_lengths[b].
+
+        encoder -> smt_glow_durations (w = ceil(exp(logw) length_scale), prefix sums, lengths) -> ONE host read of the lengths
+        (the reference syncs there too) -> smt_glow_duration_index (frame -> token) -> align_gather of x_m / x_logs ->
+        z = (z_m + exp(z_logs) noise_scale eps) mask -> decoder(z, reverse=True).  eps = ``noise`` ([B, n_mels, T_out], the
+        layout of ``forward``'s noise; frames past y_lengths[b] are never read) or a torch.randn draw in that layout.
+        noise_scale = length_scale = 1 is the reference's computation.  Invalid inputs raise ValueError before the launch
+        they would corrupt: token ids outside [0, n_vocab) or an empty item (ids are checked on the host, as they come from
+        outside the program), length_scale <= 0, noise_scale < 0, a noise tensor of the wrong shape, and an item whose
+        durations are not finite or sum past 2^24 frames (smt_glow_durations returns -1 for it)."""
+        if self.training:
+            raise RuntimeError(f"{type(self).__name__}.infer needs evaluation mode: call .eval() first")
+        if not (math.isfinite(length_scale) and length_scale > 0):
+            raise ValueError(f"length_scale must be a finite number > 0, got {length_scale}")
+        if not (math.isfinite(noise_scale) and noise_scale >= 0):
+            raise ValueError(f"noise_scale must be a finite number >= 0, got {noise_scale}")
+        dev, n_vocab = self.encoder.emb.weight.device, self.encoder.emb.num_embeddings
+        n_mels, n_sqz = self.decoder.flows[0].channels // self.decoder.n_sqz, self.decoder.n_sqz
+        x = torch.as_tensor(x).detach()
+        if x.dim() != 2 or x.shape[0] == 0:
+            raise ValueError(f"x must be token ids [B, Tx] with B >= 1, got shape {tuple(x.shape)}")
+        b, tx = x.shape
+        if x_lengths is None:
+            lens = torch.full((b,), tx, dtype=torch.int64)
+        else:
+            lens = torch.as_tensor(x_lengths).detach().cpu()
+            if lens.shape != (b,) or lens.is_floating_point() or lens.is_complex():
+                raise ValueError(f"x_lengths must be {b} integers, got {lens.dtype} of shape {tuple(lens.shape)}")
+            lens = lens.long()
+        for i, n in enumerate(lens.tolist()):
+            if not 1 <= n <= tx:
+                raise ValueError(f"item {i} has {n} tokens: every item needs 1 to {tx} (the width of x)")
+        if x.is_floating_point() or x.is_complex() or x.dtype == torch.bool:
+            raise ValueError(f"x must hold integer token ids, got {x.dtype}")
+        xc = x.cpu().long()
+        valid = torch.arange(tx)[None, :] < lens[:, None]
+        bad = valid & ((xc < 0) | (xc >= n_vocab))
+        if bad.any():
+            i, t = (int(v) for v in bad.nonzero()[0])
+            raise ValueError(f"item {i}, token {t}: id {int(xc[i, t])} is outside [0, {n_vocab})")
+        if noise is not None and (noise.dim() != 3 or tuple(noise.shape[:2]) != (b, n_mels)):
+            raise ValueError(f"noise must be [B={b}, n_mels={n_mels}, T_out], got shape {tuple(noise.shape)}")
+
+        x_m, x_logs, logw, lens32 = self.encoder(torch.where(valid, xc, 0).to(dev), lens.to(dev))
+        _, z_lens, cum = glow.durations(logw, lens32, length_scale, n_sqz)
+        z_host = z_lens.cpu()                                          # the one host read (the reference's int(z_lengths))
+        invalid = (z_host < 0).nonzero().flatten().tolist()
+        if invalid:
+            raise ValueError(f"item {invalid[0]}: the predicted durations are not finite or sum past 2^24 frames "
+                             f"(length_scale {length_scale}; invalid items: {invalid})")
+        t_out = int(z_host.max())
+        if noise is not None and noise.shape[2] != t_out:
+            raise ValueError(f"noise must be [B={b}, n_mels={n_mels}, T_out={t_out}], got shape {tuple(noise.shape)}")
+        y_lengths = z_host.long().to(dev)
+        if t_out == 0:
+            return torch.zeros(b, n_mels, 0, device=dev), y_lengths
+        idx = glow.duration_index(cum, lens32, z_lens, t_out)
+        z_m = glow.align_gather(x_m, idx)
+        z_logs = None if x_logs is None else glow.align_gather(x_logs, idx)
+        eps = (torch.randn(b, n_mels, t_out, device=dev) if noise is None else noise.to(dev, torch.float32)).transpose(1, 2)
+        z = self._prior_sample(z_m, z_logs, eps, z_lens, t_out, noise_scale)
+        yh_rows, _ = self.decoder(z, z_lens, reverse=True)
+        return yh_rows.transpose(1, 2), y_lengths
+
+    @torch.no_grad()
+    def infer_step(self, t, speaker=None):
+        """One utterance's token ids (a list or a 1-D tensor) -> yh [1, n_mels, T] (glow_tts.py:133-168).  The reference takes a
+        string and phonemizes it with CMUDictParser, which is not built here."""
+        if isinstance(t, str):
+            raise NotImplementedError("infer_step takes token ids: the CMUDict text front end (models/parser.py) is not built "
+                                      "(DESIGN.md section 7)")
+        if speaker is not None:
+            raise ValueError("speaker embeddings (n_speakers > 1) have no native path; configs/models/glow_tts.yaml is single-speaker")
+        x = torch.as_tensor(t)
+        if x.dim() != 1:
+            raise ValueError(f"infer_step takes one utterance's token ids (1-D), got shape {tuple(x.shape)}")
+        yh, _ = self.infer(x.unsqueeze(0))
+        return yh

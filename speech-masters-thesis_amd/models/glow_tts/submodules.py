@@ -38,15 +38,6 @@ def maximum_path(value, mask, max_neg_val=None):
     return path.to(value.dtype)
 
 
-def generate_path(duration, mask):
-    """Alignment from predicted durations (submodules.py:70-85): duration [b, t_x], mask [b, t_x, t_y]."""
-    b, t_x, t_y = mask.shape
-    cum = torch.cumsum(duration, 1)
-    path = sequence_mask(cum.view(b * t_x), t_y).to(mask.dtype).view(b, t_x, t_y)
-    path = path - F.pad(path, (0, 0, 1, 0))[:, :-1]
-    return path * mask
-
-
 # ---- convolution helpers ---------------------------------------------------------------------------------------------
 def _cin_ok(c):
     """Input-channel counts the fp32 implicit-GEMM kernel takes (include/smt_hip.h, smt_conv1d_ntc)."""

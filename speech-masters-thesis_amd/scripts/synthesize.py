@@ -1,0 +1,91 @@
+"""Mel spectrograms from token ids with a trained GlowTTS (the reference's `GlowTTS.infer_step`, batched).
+
+    python -m scripts.synthesize --log_dir ./logs/glow_tts --ckpt_num 5000 --tokens utterances.txt --dump_dir ./outputs \
+        [--batch_size 16] [--noise_scale 0.667] [--length_scale 1.0] [--seed 0]
+
+``--tokens`` holds one utterance per line as whitespace-separated integer ids (the ids of datasets/synthetic.py, and the ones
+the reference's CMUDict parser would emit; the text front end itself is not built).  Writes
+``<dump_dir>/<ModelClass>@<ckpt>/mel_<i>.npy`` (float32 [n_mels, frames], trimmed to the utterance's length) and one
+``mel_spectrograms.png``.  Synthesis runs on MI355X through libsmt_hip.so (`GlowTTS.infer`); there is no vocoder."""
+import argparse
+import logging
+import os
+
+import numpy as np
+import torch
+
+from scripts.sample_from_lm import mel_grid
+from utils import config as cfglib
+from utils.commons import get_model
+from utils.train_utils import write_png_gray
+
+logger = logging.getLogger(__name__)
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--log_dir", type=str, required=True, help="Log directory of training")
+    p.add_argument("--ckpt_num", type=int, required=True, help="Checkpoint number to load")
+    p.add_argument("--tokens", type=str, required=True, help="One utterance per line: whitespace-separated token ids")
+    p.add_argument("--dump_dir", type=str, default="./outputs", help="Directory to dump the spectrograms")
+    p.add_argument("--batch_size", type=int, default=16, help="Utterances per inference call")
+    p.add_argument("--noise_scale", type=float, default=1.0, help="Scale of the prior noise (1 = the reference)")
+    p.add_argument("--length_scale", type=float, default=1.0, help="Scale of the predicted durations (1 = the reference)")
+    p.add_argument("--seed", type=int, default=0, help="Seed of the prior noise")
+    return p.parse_args(argv)
+
+
+def read_tokens(path):
+    """Non-empty lines -> lists of ints."""
+    with open(path, encoding="utf-8") as f:
+        rows = [line.split() for line in f]
+    try:
+        return [[int(v) for v in r] for r in rows if r]
+    except ValueError as e:
+        raise ValueError(f"{path}: every line must hold whitespace-separated integer token ids ({e})") from None
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if args.batch_size < 1:
+        raise ValueError("--batch_size must be >= 1")
+    if not torch.cuda.is_available():
+        raise RuntimeError("synthesize runs GlowTTS on MI355X (libsmt_hip.so); no GPU is visible")
+    utterances = read_tokens(args.tokens)
+    if not utterances:
+        raise ValueError(f"{args.tokens} holds no utterance")
+    device = torch.device("cuda")
+    config = cfglib.load(os.path.join(args.log_dir, "config.yaml"))
+    config.train.n_gpus = 1
+    ckpt = torch.load(os.path.join(args.log_dir, "ckpts", f"ckpt.{args.ckpt_num}.pt"), map_location=device, weights_only=True)
+    model, _ = get_model(config, device=device)
+    model.load_state_dict(ckpt["model"])
+    model.eval()
+    dump_dir = os.path.join(args.dump_dir, f"{type(model).__name__}@{args.ckpt_num}")
+    os.makedirs(dump_dir, exist_ok=True)
+
+    torch.manual_seed(args.seed)
+    mels = []
+    for lo in range(0, len(utterances), args.batch_size):
+        part = utterances[lo:lo + args.batch_size]
+        x = torch.zeros(len(part), max(len(t) for t in part), dtype=torch.int64)
+        for i, t in enumerate(part):
+            x[i, :len(t)] = torch.tensor(t, dtype=torch.int64)
+        yh, y_lengths = model.infer(x, torch.tensor([len(t) for t in part]), noise_scale=args.noise_scale,
+                                    length_scale=args.length_scale)
+        yh = yh.cpu().numpy()
+        mels += [np.ascontiguousarray(yh[i, :, :n], dtype=np.float32) for i, n in enumerate(y_lengths.tolist())]
+    for i, m in enumerate(mels):
+        np.save(os.path.join(dump_dir, f"mel_{i}.npy"), m)
+    drawn = [m for m in mels if m.shape[1] > 0]
+    if drawn:
+        width = max(m.shape[1] for m in drawn)
+        write_png_gray(os.path.join(dump_dir, "mel_spectrograms.png"),
+                       mel_grid([np.pad(m, ((0, 0), (0, width - m.shape[1])), constant_values=m.min()) for m in drawn]))
+    logger.info("Saved %d spectrograms under %s", len(mels), dump_dir)
+    return dump_dir
+
+
+if __name__ == "__main__":
+    logging.basicConfig(level=logging.INFO)
+    main()

@@ -303,6 +303,33 @@ def align_gather(x, idx):
     return _AlignGather.apply(x, idx)
 
 
+@torch.no_grad()
+def durations(logw, lens, length_scale=1.0, n_sqz=1):
+    """Predicted log-durations logw [B, Tx] -> (w [B, Tx] fp32, z_lens [B] int32, cum [B, Tx] int32): w = ceil(exp(logw)
+    length_scale) on the first lens[b] tokens, cum its inclusive prefix sum, z_lens = (max(sum w, 1) // n_sqz) n_sqz, or -1
+    for an item whose durations are not finite or sum past 2^24 (glow_tts.py:148-151)."""
+    logw = _f(logw)
+    b, tx = logw.shape
+    w = torch.empty_like(logw)
+    z_lens = torch.empty(b, dtype=torch.int32, device=logw.device)
+    cum = torch.empty(b, tx, dtype=torch.int32, device=logw.device)
+    N.check(N.lib().smt_glow_durations(N.ptr(logw), N.ptr(_lens(lens).contiguous()), b, tx, float(length_scale), int(n_sqz), N.ptr(w),
+                                       N.ptr(z_lens), N.ptr(cum), N.stream_ptr()), "smt_glow_durations")
+    return w, z_lens, cum
+
+
+@torch.no_grad()
+def duration_index(cum, lens, z_lens, t_out):
+    """Frame -> token index idx [B, t_out] (int32, -1 = no token) of the durations' prefix sums: the alignment path that
+    generate_path builds densely (glow_tts.py:155-156), in the convention of ``align_index``, for ``align_gather``."""
+    assert cum.dtype == torch.int32 and cum.is_cuda and z_lens.dtype == torch.int32
+    b, tx = cum.shape
+    idx = torch.empty(b, int(t_out), dtype=torch.int32, device=cum.device)
+    N.check(N.lib().smt_glow_duration_index(N.ptr(cum.contiguous()), N.ptr(_lens(lens).contiguous()), N.ptr(z_lens.contiguous()), b, tx,
+                                            int(t_out), N.ptr(idx), N.stream_ptr()), "smt_glow_duration_index")
+    return idx
+
+
 class _MleLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, z_m, z_logs, logdet_sum, denom):

@@ -9,7 +9,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SMT_HIP_LIB: an alternative build of the same ABI (tools/ablate_*.sh link their -D ablation builds to libsmt_hip_abl.so)
 LIB_PATH = os.environ.get("SMT_HIP_LIB") or os.path.join(_HERE, "libsmt_hip.so")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _lib = None
 _lock = threading.Lock()
@@ -114,6 +114,8 @@ _SIGNATURES = {
     "smt_glow_align_index": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr]),
     "smt_glow_align_gather": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "smt_glow_align_scatter": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
+    "smt_glow_durations": (c_int, [c_ptr, c_ptr, c_int, c_int, c_f32, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "smt_glow_duration_index": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
     "smt_glow_mle_workspace_bytes": (c_size, [c_i64]),
     "smt_glow_mle_sums": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
     "smt_glow_mle_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
