@@ -81,7 +81,10 @@ int smt_vq_backward(const float* x, const float* x_d, const float* row_mask, con
  * The rows are grouped by code first (counting sort, LDS-privatised histograms) and each wave sums a share of the sorted
  * order in registers: one 64-bit fixed-point integer atomic (units of 2^-24) per channel per (share, code) boundary, not per
  * row -- so the time does not depend on how skewed the code usage is, and the sums are bit-reproducible whatever order the
- * rows arrive in.  Exact for |x| < 2^15 on a 2^-24 grid (saturating beyond 2^39 units per element).  k_bins <= 16384. */
+ * rows arrive in.  Exact for |x| < 2^15 on a 2^-24 grid (saturating beyond 2^39 units per element).
+ * k_bins <= 16384 runs as described; larger tables (the grouped quantiser below: n_groups * l_bins, up to 262144) run the same
+ * counting sort with the histogram in global memory and a multi-workgroup scan, then the same summation: same sums, same
+ * bit-reproducibility.  A code outside [0, k_bins) is ignored by the large path. */
 size_t smt_vq_ema_accumulate_workspace_bytes(int64_t n_rows, int k_bins, int dim);
 int smt_vq_ema_accumulate(const float* x, const int64_t* idx, const float* row_mask,
                           int64_t n_rows, int k_bins, int dim, float* stats, void* workspace, size_t workspace_bytes,
@@ -95,6 +98,51 @@ int smt_vq_ema_accumulate(const float* x, const int64_t* idx, const float* row_m
 int smt_vq_ema_apply(float* codebook, float* k_sum, float* k_elem, const float* stats,
                      const float* k_rand, float mu, float threshold, int k_bins, int dim,
                      float* metrics, void* prep, size_t prep_bytes, smt_stream_t stream);
+
+
+/* ---- grouped quantiser: the text-conditioned bottleneck of VQTTS (models/vqtts/bottleneck.py:19-77) ----
+ * The codebook holds n_groups * l_bins codes; row r searches ONLY the l_bins codes of its group, rows
+ * [group[r] * l_bins, (group[r] + 1) * l_bins).  The reference gathers k[x_id] ([n, l_bins, dim]) and calls bmm; here the
+ * rows are bucketed by group and tiles of rows of one group sweep that group's codes: no gather, workspace O(n_rows).
+ * dim in {32, 64, 128}; l_bins a multiple of 32 in [32, 1024]; 1 <= n_groups <= 256; 0 <= n_rows <= 2^20.  Anything else is
+ * an argument error (smt_vq_grouped_prep_bytes then returns 0).
+ *
+ * smt_vq_grouped_prepare: the per-GROUP derived data (mean of the group's codes, centred bf16-pair split, -|k~|^2/2,
+ * max |k~|^2) in a caller-owned persistent buffer; same contract as smt_vq_prepare: smt_vq_grouped_ema_apply refreshes it,
+ * call this after any other write to `codebook`. */
+size_t smt_vq_grouped_prep_bytes(int n_groups, int l_bins, int dim);
+int smt_vq_grouped_prepare(const float* codebook, int n_groups, int l_bins, int dim, void* prep, size_t prep_bytes,
+                           smt_stream_t stream);
+
+/* bottleneck.py:24-28: group[b, j] = x_id[b, align_idx[b, j]] and row_mask[b, j] = 1 where frame j has a token, else group 0
+ * and mask 0 (what matmul(x_id, attn) and attn.sum(1) give).
+ *   x_id      [batch, t_x] int64 token ids; the caller guarantees 0 <= id < n_groups (the kernel clamps, it never faults)
+ *   align_idx [batch, t_y] int32, the convention of smt_glow_align_index: the token of frame j, -1 = none
+ *   group     [batch * t_y] int32, row_mask [batch * t_y] f32: outputs */
+int smt_vq_align_groups(const int64_t* x_id, const int* align_idx, int batch, int t_x, int t_y, int n_groups,
+                        int* group, float* row_mask, smt_stream_t stream);
+
+/* Grouped nearest-code search + dequantise (bottleneck.py:38-60).
+ *   x [n_rows, dim] f32; group [n_rows] int32 in [0, n_groups) (clamped); codebook [n_groups * l_bins, dim] f32;
+ *   prep     the buffer smt_vq_grouped_prepare / smt_vq_grouped_ema_apply filled for THIS codebook content (required);
+ *   row_mask [n_rows] f32 0/1 or NULL.  Masked rows ARE searched, in whatever group they carry (smt_vq_align_groups: 0):
+ *            the reference's fit sums min_dist over all rows; x_d is zero there.
+ * outputs
+ *   q_rel    [n_rows] int64  exact argmin over the group's codes of ||x - k_j||^2 (fp32 inputs), lowest index on ties
+ *   q_abs    [n_rows] int64  group * l_bins + q_rel
+ *   min_dist [n_rows] f32, x_d [n_rows, dim] = codebook[q_abs] * row_mask (may be NULL), sums [4] as smt_vq_forward.
+ * x_d, row_mask and sums feed smt_vq_backward unchanged. */
+size_t smt_vq_grouped_forward_workspace_bytes(int64_t n_rows);
+int smt_vq_grouped_forward(const float* x, const int* group, const float* codebook, void* prep, const float* row_mask,
+                           int64_t n_rows, int n_groups, int l_bins, int dim,
+                           int64_t* q_rel, int64_t* q_abs, float* min_dist, float* x_d, float* sums,
+                           void* workspace, size_t workspace_bytes, smt_stream_t stream);
+
+/* smt_vq_ema_apply for the grouped codebook (k_bins = n_groups * l_bins; stats from smt_vq_ema_accumulate on q_abs):
+ * same update and metrics, and `prep` (smt_vq_grouped_prep_bytes) is refreshed per group for the new codebook. */
+int smt_vq_grouped_ema_apply(float* codebook, float* k_sum, float* k_elem, const float* stats,
+                             const float* k_rand, float mu, float threshold, int n_groups, int l_bins, int dim,
+                             float* metrics, void* prep, size_t prep_bytes, smt_stream_t stream);
 
 
 /* --------------------------------------------------------------- losses ---- */

@@ -20,11 +20,7 @@
 // The [N, K] distance matrix is never materialised.
 #include <algorithm>
 
-#include "conv_common.h"
-
-#ifndef VQ_ABL
-#define VQ_ABL 0      // timing experiments (tools/ablate_vq.sh, results invalid): 1 no MFMAs, 2 no re-staging of the codebook,
-#endif                // 4 no best/runner-up folding, 8 no epilogue, 16 phase timestamps (tools/vq_phases.py), 32 no fragment reads
+#include "vq_common.h"
 
 namespace smt {
 
@@ -34,17 +30,6 @@ __device__ long long vq_dbg[8192 * 6];
 #else
 #define VQ_STAMP(k) do { } while (0)
 #endif
-
-constexpr int VQ_MAXRG = 5;           // 32-row MFMA column groups per workgroup of the search kernel (two waves each)
-constexpr int VQ_SSUP = 128;          // codes staged per step of the search kernel: two 32-code chunks per wave
-constexpr int VQ_CSUP = 64;           // ... of the candidates kernel: one chunk for each of its two waves
-constexpr int VQ_KPAD = 256;          // the prep pads the codebook to a multiple of this (two search steps)
-constexpr int VQ_CHUNK = 32;
-constexpr int VQ_SPLITS = 8;          // code-range splits of the candidate sweep (one workgroup each)
-constexpr int VQ_CAPS = 4;            // candidate codes kept per queued row and split
-constexpr int VQ_PART = 8;            // codes per partial column sum (prepare)
-
-typedef __bf16 vq_bf16x8 __attribute__((ext_vector_type(8)));
 
 // ---------------------------------------------------------------- prepare ---
 // Distances are translation invariant, so the filter runs on data centred at the codebook mean mu: trained encoders
@@ -76,15 +61,7 @@ static size_t vq_prep_layout(int K, int D, void* base, VqPrep* w) {
   return off;
 }
 
-// part[p][i] = sum of k[j][i] over the codes j of part p (index order)
-__global__ __launch_bounds__(128) void vq_colsum_kernel(const float* __restrict__ cb, int K, int D, float* __restrict__ part) {
-  const int i = threadIdx.x;
-  if (i >= D) return;
-  const int j0 = blockIdx.x * VQ_PART;
-  float s = 0.f;
-  for (int j = j0; j < min(K, j0 + VQ_PART); ++j) s += cb[(size_t)j * D + i];
-  part[(size_t)blockIdx.x * D + i] = s;
-}
+// (vq_colsum_kernel, the partial column sums: vq_common.h)
 
 // Single workgroup: mu from the partial column sums; with `cnt` also the metrics of update_k (bottleneck.py:85-90),
 // all reductions in fixed order.
@@ -93,21 +70,6 @@ __global__ __launch_bounds__(1024) void vq_mu_kernel(const float* __restrict__ p
                                                      const float* __restrict__ cnt, const float* __restrict__ k_elem,
                                                      const double* __restrict__ dkpart, float threshold,
                                                      float* __restrict__ metrics) {
-  __shared__ double sh[16];
-  __shared__ double bc;
-  auto block_sum = [&](double v) -> double {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = 0;
-      for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-      bc = t;
-    }
-    __syncthreads();
-    return bc;
-  };
   if ((int)threadIdx.x < D) {
     float t = 0.f;
 #pragma unroll 16
@@ -116,34 +78,8 @@ __global__ __launch_bounds__(1024) void vq_mu_kernel(const float* __restrict__ p
   }
   if (threadIdx.x == 0) { kmax2_bits[0] = 0u; kmax2_bits[32] = 0u; }     // + the queue counter of smt_vq_forward
   if (!cnt) return;                                        // workgroup-uniform
-  double tot = 0.0;
-  for (int j = threadIdx.x; j < K; j += blockDim.x) tot += cnt[j];
-  const float total = (float)block_sum(tot);
-  double ent = 0.0, used = 0.0, usage_n = 0.0, dk2 = 0.0;
-  for (int j = threadIdx.x; j < K; j += blockDim.x) {
-    const float c = cnt[j];
-    const float prob = c / total;
-    ent += -(double)(prob * logf(fmaxf(prob, 1e-5f)));
-    used += (c >= threshold) ? 1.0 : 0.0;
-    usage_n += (k_elem[j] >= threshold) ? 1.0 : 0.0;       // k_elem already holds the mixed value
-  }
-  for (int p = threadIdx.x; p < nparts; p += blockDim.x) dk2 += dkpart[p];
-  ent = block_sum(ent);
-  used = block_sum(used);
-  usage_n = block_sum(usage_n);
-  dk2 = block_sum(dk2);
-  if (threadIdx.x == 0) {
-    metrics[0] = (float)ent;
-    metrics[1] = (float)used;
-    metrics[2] = (float)usage_n;
-    metrics[3] = (float)(sqrt(dk2) / sqrt((double)K * D));
-  }
+  vq_update_metrics(cnt, k_elem, dkpart, nparts, K, D, threshold, metrics);
 }
-
-// Position of dim i of code j inside its [D] row of the kh / kl tiles: rows are NOT padded (they are copied to LDS by
-// linear LDS-DMA), so the 16-byte chunk index is XORed with the row index instead -- the 32 lanes of an MFMA A-fragment
-// read (32 consecutive codes, same chunk) then fall into 16 different 16-byte bank groups.
-__host__ __device__ __forceinline__ int vq_swz(int j, int D) { return (j / (128 / D)) & (D / 8 - 1); }
 
 // k~[j] = k[j] - mu as the bf16 pair (kh, kl) (v = hi + lo + eps, |eps| <= 2^-18 |v|), chunk-swizzled; nkhalf[j] =
 // -0.5 |k~[j]|^2 (fp32, index order per lane then wave tree); kmax2 = max_j |k~[j]|^2.  One wave per code, 16 codes per
@@ -178,139 +114,7 @@ __global__ __launch_bounds__(1024) void vq_split_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------- search ----
-// The codebook is the MFMA A operand (code on the row index i), x the B operand (row on the column index j = lane & 31),
-// so every lane owns ONE x row per column group and sees 16 codes per chunk in its accumulator registers: the running
-// best / runner-up is pure in-lane work.  Each fp32 operand is split into a bf16 pair and x~.k~ is evaluated as
-// kl.xh + kh.xl + kh.xh with fp32 accumulation on top of -|k~|^2/2 -- 3 bf16 MFMAs (16x the fp32-MFMA rate each)
-// instead of 8 fp32 MFMAs.  The score is only a FILTER: its error bound (vq_filter_err) decides which rows are
-// re-scored exactly, so the index semantics stay exact.
-//
-// Shape: 2 waves, 64 rows.  Each wave keeps BOTH 32-row column groups of the tile in registers (bf16 pairs of its
-// share of the rows) and takes one of the two 32-code chunks of every staged 64-code step, so one A fragment read from
-// LDS feeds 6 MFMAs and a workgroup stages the whole codebook exactly once for its 64 rows.  LDS: two stages of
-// [hi | lo][64][D + 8] bf16 + 64 floats.
-template <int D, int SUP> struct VqGeom {
-  static constexpr int NS = D / 16;                       // k-steps per chunk
-  static constexpr int TILE_BYTES = SUP * D * 2;          // one staged tile (hi or lo)
-  static constexpr int NDMA = TILE_BYTES / 1024;          // 1-KiB LDS-DMA wave-instructions per tile
-  static constexpr int BUF_BYTES = 2 * TILE_BYTES + SUP * 4;
-};
-
-__device__ __forceinline__ void vq_dma16(const void* gsrc, void* lds_dst_wave_base) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)gsrc,
-                                   (void __attribute__((address_space(3)))*)lds_dst_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ void vq_dma4(const void* gsrc, void* lds_dst_wave_base) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)gsrc,
-                                   (void __attribute__((address_space(3)))*)lds_dst_wave_base, 4, 0, 0);
-}
-// Stage step `sc` (SUP codes: hi tile, lo tile, -|k~|^2/2) into `buf` with LDS-DMA, no register round trip: the nw
-// waves of the workgroup issue the 1-KiB pieces in turn.  The data has landed after every issuing wave's
-// `s_waitcnt vmcnt(0)` + a barrier.
-template <int D, int SUP>
-__device__ __forceinline__ void vq_stage(const __bf16* kh, const __bf16* kl, const float* nkhalf, int sc, char* buf,
-                                         int nw, int wave, int lane) {
-  using G = VqGeom<D, SUP>;
-  if ((VQ_ABL & 2) && sc > 1) return;
-  for (int q = wave; q < 2 * G::NDMA; q += nw) {
-    const int which = q / G::NDMA, piece = q % G::NDMA;
-    const __bf16* src = (which ? kl : kh) + (size_t)sc * SUP * D + piece * 512 + lane * 8;
-    vq_dma16(src, buf + which * G::TILE_BYTES + piece * 1024);
-  }
-  if (wave == nw - 1) {
-#pragma unroll
-    for (int i = 0; i < SUP / 64; ++i) vq_dma4(nkhalf + sc * SUP + 64 * i + lane, buf + 2 * G::TILE_BYTES + 256 * i);
-  }
-}
-
-// this lane's share of row `row` (dims 16 s + 8 h .. + 7 for every k-step s), centred and split; returns its share of
-// |x~|^2.  All loads are issued before the first use (callers pass a row index that is always in range).
-template <int D>
-__device__ __forceinline__ float vq_load_row(const float* __restrict__ x, const float* __restrict__ mu, long long row,
-                                             int h, vq_bf16x8* xh, vq_bf16x8* xl) {
-  constexpr int NS = D / 16, HB = NS < 4 ? NS : 4;           // k-steps per batch of loads (bounds the live registers)
-  float xx = 0.f;
-#pragma unroll
-  for (int s0 = 0; s0 < NS; s0 += HB) {
-    f32x4 v[HB][2], m[HB][2];
-#pragma unroll
-    for (int s = 0; s < HB; ++s) {
-      const f32x4* src = reinterpret_cast<const f32x4*>(x + row * D + 16 * (s0 + s) + 8 * h);
-      const f32x4* msrc = reinterpret_cast<const f32x4*>(mu + 16 * (s0 + s) + 8 * h);
-      v[s][0] = src[0]; v[s][1] = src[1]; m[s][0] = msrc[0]; m[s][1] = msrc[1];
-    }
-#pragma unroll
-    for (int s = 0; s < HB; ++s) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float c = v[s][e >> 2][e & 3] - m[s][e >> 2][e & 3];
-        const __bf16 hi = (__bf16)c;
-        xh[s0 + s][e] = hi;
-        xl[s0 + s][e] = (__bf16)(c - (float)hi);
-        xx = fmaf(c, c, xx);
-      }
-    }
-  }
-  return xx;
-}
-
-// Error of the filter score against the exact acc = x~.k~ - |k~|^2/2 on the centred operands (norms are the centred
-// ones, Cauchy-Schwarz turns sums of products into norm products):
-//   bf16-pair split, three of the four partial products kept:  <= 3.01 * 2^-18 |x~| |k~|
-//   fp32 accumulation of 3D exact products + the initial term:  <= 1.05 (3D+2) 2^-24 (|x~||k~| + |k~|^2/2)
-//   fp32 rounding of khalf and of the centring x - mu, k - mu:  <= 2^-24 ((D+2)|k~|^2/2 + (|x~| + |k~|)^2)
-//   position tag in the 4 low mantissa bits of a score (vq_search_kernel):   <= 2^-19 (|x~||k~| + |k~|^2/2)
-// with |k~| <= |k~|max; a factor 1.25 of slack covers the MFMA's internal summation order and the fp32 rounding of xx.
-__device__ __forceinline__ float vq_filter_err(float xx, float kmax2, int D) {
-  const float xk = sqrtf(xx * kmax2);
-  const float u24 = 5.9604645e-8f;
-  return 1.25f * (3.01f * 64.f * u24 * xk + (1.05f * (float)(3 * D + 2) + 32.f) * u24 * (xk + 0.5f * kmax2) +
-                  u24 * (0.5f * (float)(D + 2) * kmax2 + xx + 2.f * xk + kmax2));
-}
-
-// One 32-code chunk against NG column groups: acc[g] = -|k~|^2/2 + sum_s (kl.xh + kh.xl + kh.xh), small terms first.
-template <int D, int SUP, int NG>
-__device__ __forceinline__ void vq_chunk_scores(const char* buf, int chunk, int j, int h, const vq_bf16x8 (*xh)[D / 16],
-                                                const vq_bf16x8 (*xl)[D / 16], f32x16* acc) {
-  using G = VqGeom<D, SUP>;
-  constexpr int NS = D / 16;
-  const float* nk = reinterpret_cast<const float*>(buf + 2 * G::TILE_BYTES) + chunk * VQ_CHUNK + 4 * h;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(nk + 8 * q);       // codes 8 q + 4 h + e of the chunk
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      acc[g][4 * q + 0] = v.x; acc[g][4 * q + 1] = v.y; acc[g][4 * q + 2] = v.z; acc[g][4 * q + 3] = v.w;
-    }
-  }
-  const int rowi = chunk * VQ_CHUNK + j, sw = vq_swz(rowi, D);
-  const char* ah = buf + rowi * (2 * D);
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    const int so = (VQ_ABL & 32) ? 0 : s;
-    const vq_bf16x8 fh = *reinterpret_cast<const vq_bf16x8*>(ah + 16 * ((2 * so + h) ^ sw));
-    const vq_bf16x8 fl = *reinterpret_cast<const vq_bf16x8*>(ah + G::TILE_BYTES + 16 * ((2 * so + h) ^ sw));
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      if (!(VQ_ABL & 1)) {
-        acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl, xh[g][s], acc[g], 0, 0, 0);
-        acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, xl[g][s], acc[g], 0, 0, 0);
-        acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, xh[g][s], acc[g], 0, 0, 0);
-      }
-    }
-  }
-}
-
-// top-2 merge of (best, second, idx) with another candidate triple; equal scores keep the lower index (the gap is then
-// zero and the row is re-scored exactly anyway)
-__device__ __forceinline__ void vq_merge(float& best, float& second, int& bidx, float ob, float os, int oi) {
-  if (ob > best || (ob == best && oi < bidx)) {
-    second = fmaxf(best, os); best = ob; bidx = oi;
-  } else {
-    second = fmaxf(second, ob);
-  }
-}
-
+// (operand layout, staging, the filter score and its error bound: vq_common.h)
 // Shape: RG = blockDim / 128 column groups of 32 rows, two waves each.  Wave (rg, c) keeps column group rg in
 // registers (bf16 pairs of its share of 32 rows) and takes chunks c and c + 2 of every staged 128-code step.  The host
 // picks RG = ceil(rows / 32 / 256) (up to VQ_MAXRG) so that ONE round of workgroups covers all rows with at most one
@@ -520,21 +324,7 @@ __global__ __launch_bounds__(128) void vq_candidates_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------- exact -----
-// d_j = sum_i (x_i - k_ji)^2 in fp64, index order, no fma contraction (the numpy float64 loop of the oracle)
-__device__ __forceinline__ double vq_exact_dist(const float* __restrict__ xr, const float* __restrict__ kr, int D) {
-  double d = 0.0;
-#pragma unroll 4
-  for (int i = 0; i < D; i += 4) {
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + i), kv = *reinterpret_cast<const f32x4*>(kr + i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const double df = __dsub_rn((double)xv[e], (double)kv[e]);
-      d = __dadd_rn(d, __dmul_rn(df, df));
-    }
-  }
-  return d;
-}
-// Half a wave per queued row, one lane per candidate slot (splits * VQ_CAPS <= 32); lowest index among equal distances.
+// (vq_exact_dist: vq_common.h)  Half a wave per queued row, one lane per candidate slot (splits * VQ_CAPS <= 32); lowest index among equal distances.
 // A row with no candidate or an overflowing piece (NaN input, degenerate codebook) scans all K codes the same way.
 __global__ __launch_bounds__(256) void vq_exact_kernel(const float* __restrict__ x, const float* __restrict__ cb,
                                                        const float* __restrict__ row_mask, const unsigned* __restrict__ kmax2_bits,
@@ -587,48 +377,7 @@ __global__ __launch_bounds__(256) void vq_exact_kernel(const float* __restrict__
   }
 }
 
-// ---------------------------------------------------------------- reduce ----
-// Single workgroup, fixed order: sums[0] = sum_all min_dist, sums[1] = sum_masked, sums[2] = sum mask,
-// sums[3] = rows that were re-scored exactly.  Resets the queue counter for the next forward.
-__global__ __launch_bounds__(1024) void vq_reduce_kernel(const float* __restrict__ min_dist,
-                                                         const float* __restrict__ row_mask, long long N,
-                                                         unsigned* __restrict__ kmax2_bits, float* __restrict__ sums) {
-  __shared__ double sh[3][16];
-  double a = 0.0, b = 0.0, c = 0.0;
-  constexpr int U = 10;                                     // 16-byte loads in flight per thread: 40,960 rows per pass
-  for (long long r0 = 4ll * threadIdx.x; r0 < N; r0 += 4096ll * U) {
-    f32x4 d[U], m[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long long r = r0 + 4096ll * u;
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f}, one = {1.f, 1.f, 1.f, 1.f};
-      if (r + 3 < N) {
-        d[u] = *reinterpret_cast<const f32x4*>(min_dist + r);
-        m[u] = row_mask ? *reinterpret_cast<const f32x4*>(row_mask + r) : one;
-      } else {
-        d[u] = z; m[u] = z;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (r + e < N) { d[u][e] = min_dist[r + e]; m[u][e] = row_mask ? row_mask[r + e] : 1.f; }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { a += d[u][e]; b += (m[u][e] != 0.f) ? d[u][e] : 0.f; c += m[u][e]; }
-  }
-  a = wave_sum_d(a); b = wave_sum_d(b); c = wave_sum_d(c);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { sh[0][wave] = a; sh[1][wave] = b; sh[2][wave] = c; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double ta = 0, tb = 0, tc = 0;
-    for (int w = 0; w < 16; ++w) { ta += sh[0][w]; tb += sh[1][w]; tc += sh[2][w]; }
-    sums[0] = (float)ta; sums[1] = (float)tb; sums[2] = (float)tc; sums[3] = (float)kmax2_bits[32];
-    kmax2_bits[32] = 0u;
-  }
-}
-
+// (vq_reduce_kernel, the fixed-order sums: vq_common.h)
 // ---------------------------------------------------------------- backward --
 __global__ __launch_bounds__(256) void vq_backward_kernel(const float* __restrict__ x, const float* __restrict__ x_d,
                                                           const float* __restrict__ row_mask, const float* __restrict__ dy,
@@ -727,6 +476,79 @@ __global__ __launch_bounds__(VQ_EMA_HIST_NT) void vq_ema_scatter_kernel(const lo
       order[base[code] + atomicAdd(&hist[code], 1)] = (int)r;
     }
 }
+// ---- tables of more than VQ_EMA_LDS_BINS codes (the grouped bottleneck: n_vocab * l_bins, tens of thousands) ----
+// The histogram no longer fits in LDS and one workgroup no longer scans it, so the same counting sort runs on global
+// memory: one integer atomic per unmasked row into counts[K] and one into cursor[K] (with K >> rows per code the atomics
+// spread over many lines), and a two-launch scan in blocks of VQ_EMA_SCAN_BLOCK codes.  The sorted order then feeds the
+// SAME accumulate / convert kernels as the small path: 64-bit fixed-point sums, any order gives the same bits.  A code
+// outside [0, K) is skipped by count and scatter alike (never a write out of range).
+constexpr int VQ_EMA_LDS_BINS = 16384;
+constexpr int VQ_EMA_MAX_BINS = 1 << 18;
+constexpr int VQ_EMA_SCAN_BLOCK = 4096;         // codes per workgroup of the large scan: 4 per thread
+__global__ __launch_bounds__(256) void vq_ema_count_large_kernel(const long long* __restrict__ idx, const float* __restrict__ row_mask,
+                                                                 long long N, int K, int* __restrict__ counts) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= N || (row_mask && row_mask[r] == 0.f)) return;
+  const long long code = idx[r];
+  if (code >= 0 && code < K) atomicAdd(&counts[code], 1);
+}
+// this thread's four codes of block blockIdx.x (zero past K)
+__device__ __forceinline__ void vq_ema_load4(const int* __restrict__ counts, int K, int k0, int* c) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) c[e] = k0 + e < K ? counts[k0 + e] : 0;
+}
+__global__ __launch_bounds__(1024) void vq_ema_blocksum_kernel(const int* __restrict__ counts, int K, int* __restrict__ bsum) {
+  __shared__ int sh[16];
+  int c[4];
+  vq_ema_load4(counts, K, blockIdx.x * VQ_EMA_SCAN_BLOCK + 4 * threadIdx.x, c);
+  int s = (c[0] + c[1]) + (c[2] + c[3]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+    for (int w = 0; w < 16; ++w) t += sh[w];
+    bsum[blockIdx.x] = t;
+  }
+}
+__global__ __launch_bounds__(1024) void vq_ema_scan_large_kernel(const int* __restrict__ counts, int K, const int* __restrict__ bsum,
+                                                                int* __restrict__ cursor, int* __restrict__ total) {
+  __shared__ int part[1024];
+  __shared__ int base;
+  if (threadIdx.x == 0) {
+    int t = 0;
+    for (int b = 0; b < (int)blockIdx.x; ++b) t += bsum[b];        // at most VQ_EMA_MAX_BINS / VQ_EMA_SCAN_BLOCK = 64 terms
+    base = t;
+  }
+  const int k0 = blockIdx.x * VQ_EMA_SCAN_BLOCK + 4 * threadIdx.x;
+  int c[4];
+  vq_ema_load4(counts, K, k0, c);
+  const int s = (c[0] + c[1]) + (c[2] + c[3]);
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const int v = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+    __syncthreads();
+    part[threadIdx.x] += v;
+    __syncthreads();
+  }
+  int run = base + part[threadIdx.x] - s;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (k0 + e < K) cursor[k0 + e] = run;
+    run += c[e];
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 1023) total[0] = base + part[1023];
+}
+__global__ __launch_bounds__(256) void vq_ema_scatter_large_kernel(const long long* __restrict__ idx, const float* __restrict__ row_mask,
+                                                                   long long N, int K, int* __restrict__ cursor, int* __restrict__ order) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= N || (row_mask && row_mask[r] == 0.f)) return;
+  const long long code = idx[r];
+  if (code >= 0 && code < K) order[atomicAdd(&cursor[code], 1)] = (int)r;
+}
+
 // one wave per share of VQ_EMA_SHARE sorted rows; PER = ceil(D / 64) channels per lane (D = 32: the upper half of the wave idles)
 constexpr int VQ_EMA_SHARE = 64;
 // A wave owns 64 consecutive positions of the sorted order.  Lane l fetches the row id and the code of position r0 + l once
@@ -793,45 +615,7 @@ __global__ __launch_bounds__(256) void vq_ema_convert_kernel(const unsigned long
   stats[e] = e < n_sums ? (float)((double)v * (1.0 / 16777216.0)) : (float)v;
 }
 
-// EMA mix + revival for VQ_PART codes per workgroup (bottleneck.py:78-84); leaves the partial column sums of the NEW
-// codebook and the partial sums of (k_new - k_old)^2 for vq_mu_kernel, which finishes the metrics in fixed order.
-__global__ __launch_bounds__(256) void vq_ema_apply_kernel(float* __restrict__ cb, float* __restrict__ k_sum,
-                                                           float* __restrict__ k_elem, const float* __restrict__ stats,
-                                                           const float* __restrict__ k_rand, float mu, float threshold,
-                                                           int K, int D, float* __restrict__ part, double* __restrict__ dkpart) {
-  __shared__ float slab[VQ_PART * 128];
-  __shared__ double red[4];
-  const int j0 = blockIdx.x * VQ_PART;
-  const int n = min(VQ_PART, K - j0) * D;
-  const float* cnt = stats + (size_t)K * D;
-  double dk2 = 0.0;
-  for (int e = threadIdx.x; e < n; e += 256) {
-    const int j = j0 + e / D;
-    const size_t ge = (size_t)j0 * D + e;
-    const float ne = mu * k_elem[j] + (1.f - mu) * cnt[j];   // k_elem is rewritten only after the barrier below
-    const float ns = mu * k_sum[ge] + (1.f - mu) * stats[ge];
-    const float usage = (ne >= threshold) ? 1.f : 0.f;
-    const float nk = usage * (ns / ne) + (1.f - usage) * k_rand[ge];
-    const float d = nk - cb[ge];
-    dk2 += (double)d * d;
-    k_sum[ge] = ns;
-    cb[ge] = nk;
-    slab[e] = nk;
-  }
-  dk2 = wave_sum_d(dk2);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dk2;
-  __syncthreads();
-  if ((int)threadIdx.x < min(VQ_PART, K - j0)) {
-    const int j = j0 + threadIdx.x;
-    k_elem[j] = mu * k_elem[j] + (1.f - mu) * cnt[j];
-  }
-  if (threadIdx.x == 0) dkpart[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-  if ((int)threadIdx.x < D) {
-    float t = 0.f;
-    for (int q = 0; q < min(VQ_PART, K - j0); ++q) t += slab[q * D + threadIdx.x];
-    part[(size_t)blockIdx.x * D + threadIdx.x] = t;
-  }
-}
+// (vq_ema_apply_kernel, the EMA mix + revival: vq_common.h)
 
 struct VqWorkspace { int* q_rows; float* q_thr; int* c_count; int* c_codes; void* prep; };
 
@@ -959,7 +743,7 @@ extern "C" int smt_vq_backward(const float* x, const float* x_d, const float* ro
   return 0;
 }
 
-// workspace: acc u64 [K D + K] | counts int [K] | cursor int [K] | total int [64] | order int [N]
+// workspace: acc u64 [K D + K] | counts int [K] | cursor int [K] | total int [64] (| bsum int [64]) | order int [N]
 static size_t vq_ema_ws_layout(long long N, int K, int D, size_t* off_counts, size_t* off_cursor, size_t* off_total, size_t* off_order) {
   size_t off = align_up(((size_t)K * D + K) * sizeof(unsigned long long), 256);
   if (off_counts) *off_counts = off;
@@ -967,7 +751,7 @@ static size_t vq_ema_ws_layout(long long N, int K, int D, size_t* off_counts, si
   if (off_cursor) *off_cursor = off;
   off += align_up((size_t)K * sizeof(int), 256);
   if (off_total) *off_total = off;
-  off += 256;
+  off += K > VQ_EMA_LDS_BINS ? 512 : 256;            // total int [64] (+ the large scan's block sums int [64])
   if (off_order) *off_order = off;
   off += align_up((size_t)std::max<long long>(N, 1) * sizeof(int), 256);
   return off;
@@ -982,7 +766,8 @@ extern "C" int smt_vq_ema_accumulate(const float* x, const int64_t* idx, const f
   hipStream_t stream = (hipStream_t)stream_;
   SMT_CHECK_ARG(stats && workspace && (n_rows == 0 || (x && idx)), "smt_vq_ema_accumulate: null pointer");
   SMT_CHECK_ARG(dim == 64 || dim == 128 || dim == 32, "smt_vq_ema_accumulate: dim must be 32, 64 or 128 (got %d)", dim);
-  SMT_CHECK_ARG(n_rows < (1ll << 31) && k_bins >= 1 && k_bins <= 16384, "smt_vq_ema_accumulate: bad sizes");
+  SMT_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 31), "smt_vq_ema_accumulate: n_rows must be in [0, 2^31) (got %lld)", (long long)n_rows);
+  SMT_CHECK_ARG(k_bins >= 1 && k_bins <= VQ_EMA_MAX_BINS, "smt_vq_ema_accumulate: k_bins must be in [1, %d] (got %d)", VQ_EMA_MAX_BINS, k_bins);
   size_t o_counts, o_cursor, o_total, o_order;
   SMT_CHECK_ARG(workspace_bytes >= vq_ema_ws_layout(n_rows, k_bins, dim, &o_counts, &o_cursor, &o_total, &o_order),
                 "smt_vq_ema_accumulate: workspace too small");
@@ -993,7 +778,18 @@ extern "C" int smt_vq_ema_accumulate(const float* x, const int64_t* idx, const f
   int* total = (int*)((char*)workspace + o_total);
   int* order = (int*)((char*)workspace + o_order);
   (void)hipMemsetAsync(workspace, 0, o_order, stream);                // accumulators, counts, cursors, total
-  if (n_rows > 0) {
+  if (n_rows > 0 && k_bins > VQ_EMA_LDS_BINS) {
+    const unsigned rgrid = (unsigned)((n_rows + 255) / 256), nb = (unsigned)((k_bins + VQ_EMA_SCAN_BLOCK - 1) / VQ_EMA_SCAN_BLOCK);
+    int* bsum = total + 64;
+    vq_ema_count_large_kernel<<<rgrid, 256, 0, stream>>>((const long long*)idx, row_mask, n_rows, k_bins, counts);
+    SMT_CHECK_LAUNCH("vq_ema_count_large");
+    vq_ema_blocksum_kernel<<<nb, 1024, 0, stream>>>(counts, k_bins, bsum);
+    SMT_CHECK_LAUNCH("vq_ema_blocksum");
+    vq_ema_scan_large_kernel<<<nb, 1024, 0, stream>>>(counts, k_bins, bsum, cursor, total);
+    SMT_CHECK_LAUNCH("vq_ema_scan_large");
+    vq_ema_scatter_large_kernel<<<rgrid, 256, 0, stream>>>((const long long*)idx, row_mask, n_rows, k_bins, cursor, order);
+    SMT_CHECK_LAUNCH("vq_ema_scatter_large");
+  } else if (n_rows > 0) {
     const int rows_per_wg = (int)std::max<long long>(VQ_EMA_HIST_NT, (n_rows + 255) / 256);
     const unsigned nwg = (unsigned)((n_rows + rows_per_wg - 1) / rows_per_wg);
     vq_ema_count_kernel<<<nwg, VQ_EMA_HIST_NT, (size_t)k_bins * sizeof(int), stream>>>((const long long*)idx, row_mask, n_rows, k_bins, rows_per_wg,
@@ -1004,6 +800,8 @@ extern "C" int smt_vq_ema_accumulate(const float* x, const int64_t* idx, const f
     vq_ema_scatter_kernel<<<nwg, VQ_EMA_HIST_NT, 2 * (size_t)k_bins * sizeof(int), stream>>>((const long long*)idx, row_mask, n_rows, k_bins,
                                                                                           rows_per_wg, cursor, order);
     SMT_CHECK_LAUNCH("vq_ema_scatter");
+  }
+  if (n_rows > 0) {
     const long long waves = (n_rows + VQ_EMA_SHARE - 1) / VQ_EMA_SHARE;
     const unsigned grid = (unsigned)((waves + 3) / 4);
     if (dim == 128) vq_ema_accumulate_kernel<128><<<grid, 256, 0, stream>>>(x, (const long long*)idx, order, total, k_bins, acc);

@@ -86,6 +86,10 @@ class BottleneckBlock(nn.Module):
             self.k_sum.mul_(expected)
         self.threshold = threshold
 
+    def _ema_apply(self, stats, revival):
+        """EMA mix + revival + metrics in place, and the search's derived data for the new codebook: (metrics, prep)."""
+        return vq.ema_apply(self.k, self.k_sum, self.k_elem, stats, revival, self.mu, self.threshold, self._prep)
+
     @torch.no_grad()
     def update_k(self, rows, idx, row_mask, k_rand=None):
         kb, d = self.k_bins, self.emb_width
@@ -98,7 +102,7 @@ class BottleneckBlock(nn.Module):
             revival.zero_()
         if dist.is_initialized():
             dist.all_reduce(stats, op=dist.ReduceOp.SUM)
-        m, self._prep = vq.ema_apply(self.k, self.k_sum, self.k_elem, stats, revival, self.mu, self.threshold, self._prep)
+        m, self._prep = self._ema_apply(stats, revival)
         self._prep_key = (self.k.data_ptr(), self.k._version)     # written by pointer: the version did not move
         return dict(entropy=m[0], used_curr=m[1], usage=m[2], dk=m[3])
 

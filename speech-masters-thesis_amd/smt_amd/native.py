@@ -9,7 +9,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SMT_HIP_LIB: an alternative build of the same ABI (tools/ablate_*.sh link their -D ablation builds to libsmt_hip_abl.so)
 LIB_PATH = os.environ.get("SMT_HIP_LIB") or os.path.join(_HERE, "libsmt_hip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _lib = None
 _lock = threading.Lock()
@@ -35,6 +35,14 @@ _SIGNATURES = {
     "smt_vq_ema_accumulate": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_size, c_ptr]),
     "smt_vq_ema_apply": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_f32, c_int, c_int, c_ptr, c_ptr, c_size,
                                  c_ptr]),
+    "smt_vq_grouped_prep_bytes": (c_size, [c_int, c_int, c_int]),
+    "smt_vq_grouped_prepare": (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_size, c_ptr]),
+    "smt_vq_align_groups": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "smt_vq_grouped_forward_workspace_bytes": (c_size, [c_i64]),
+    "smt_vq_grouped_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
+                                       c_ptr, c_ptr, c_size, c_ptr]),
+    "smt_vq_grouped_ema_apply": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_f32, c_int, c_int, c_int, c_ptr, c_ptr,
+                                         c_size, c_ptr]),
     "smt_pack_weight": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_ptr, c_int, c_ptr]),
     "smt_pack_weights_batched": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr]),
     "smt_conv1d_ntc": (c_int, [c_ptr, c_ptr]),
