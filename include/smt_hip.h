@@ -458,6 +458,41 @@ int smt_lm_ce_fwd(const float* logits, const int64_t* target, float* row_out, fl
 int smt_lm_ce_bwd(const float* logits, const int64_t* target, const float* lse, const float* coef, float* dlogits,
                   int64_t rows, int vocab, smt_stream_t stream);
 
+/* Incremental decoding (TransformerLM.sample(causal=True)): one new token per step against a key/value cache.  fp32, eval
+ * mode (no dropout), head dim 32, batch 1..32.  What changes from step to step -- the position, the tokens, the uniforms --
+ * lives in device memory, so a step is a fixed sequence of launches with fixed arguments.  Like the dropout keys above,
+ * the position comes twice: `pos` by value and `pos_dev`, a DEVICE pointer that overrides it when non-NULL.  A by-value
+ * position outside the buffers is an argument error; with a device position the kernels return without touching memory.
+ * Every sum is merged in a fixed order (no float atomics): equal inputs give equal bits. */
+
+/* out[b, :] = emb[tokens[b, pos]] * mul + pe[pos];  tokens [batch, tok_len] int64, emb [vocab_rows, dim], pe [pe_rows, dim],
+ * out [batch, dim].  A token outside [0, vocab_rows) gives a NaN row. */
+int smt_lm_decode_embed(const int64_t* tokens, const float* emb, const float* pe, float* out, int batch, int tok_len, int dim,
+                        int vocab_rows, int pe_rows, float mul, int pos, const int* pos_dev, smt_stream_t stream);
+
+/* out [batch, out_dim] = x [batch, in_dim] . w [out_dim, in_dim]^T (+ bias [out_dim] if non-NULL) (ReLU if relu != 0): the
+ * weight matrix (an nn.Linear weight as is) is streamed once.  in_dim % 64 == 0, out_dim >= 1; fp32 products and sums. */
+int smt_lm_decode_linear(const float* x, const float* w, const float* bias, float* out, int batch, int in_dim, int out_dim, int relu,
+                         smt_stream_t stream);
+
+/* One layer's attention for the token at `pos`: qkv [batch, 3*heads*32] (q | k | v as in_proj produces them); the k and v
+ * rows are stored to cache row pos (k_cache, v_cache [batch, heads, l_max, 32]) and
+ * ctx [batch, heads*32] = softmax(q . K[0..pos]^T / sqrt(32)) . V[0..pos].  Cache rows beyond pos are never read.
+ * workspace: smt_lm_decode_attention_workspace_bytes (partial softmaxes of the 256-row chunks; 0 when l_max <= 256). */
+size_t smt_lm_decode_attention_workspace_bytes(int batch, int heads, int l_max);
+int smt_lm_decode_attention(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace, size_t workspace_bytes,
+                            int batch, int heads, int l_max, int pos, const int* pos_dev, smt_stream_t stream);
+
+/* Inverse-CDF draw: p_i = exp((logits[b, i] - max_i) * inv_sigma), S = sum p_i, k = the smallest index whose cumulative sum
+ * exceeds uniforms[pos, b] * S (if rounding leaves none: the last k with p_k > 0).  logits [batch, vocab], uniforms
+ * [n_steps, batch] in [0, 1); writes tokens[b, pos + 1] = k + token_offset (tokens [batch, tok_len] int64) and
+ * codes[b, pos] = k (codes [batch, n_steps] int64). */
+int smt_lm_decode_sample(const float* logits, const float* uniforms, int64_t* tokens, int64_t* codes, int batch, int vocab,
+                         int tok_len, int n_steps, float inv_sigma, int token_offset, int pos, const int* pos_dev, smt_stream_t stream);
+
+/* pos_dev[0] += 1: the last launch of a step. */
+int smt_lm_decode_advance(int* pos_dev, smt_stream_t stream);
+
 /* ------------------------------------------------------- GlowTTS ---- */
 /* SURVEY 8(f4) / BASELINE.json configs[4]: the pieces of the reference's GlowTTS (models/glow_tts/glow_tts.py:59-130,
  * modules.py:134-236, submodules.py:88-512) that are not convolutions; fp32, channels-last rows [batch, t, channels] with

@@ -1,0 +1,386 @@
+// Incremental decoding of the causal TransformerLM (TransformerLM.sample(causal=True)): one new token per step against a
+// key/value cache, batch 1..32, fp32, eval mode (no dropout anywhere).
+//
+//   lm_decode_embed      emb[tokens[b, pos]] * sqrt(d) + pe[pos]
+//   lm_decode_linear     out[B, N] = x[B, K] W[N, K]^T (+ bias) (ReLU): the weights are streamed once, B <= 32 rows ride along
+//   lm_decode_attention  this step's k / v rows into the cache, softmax(q K[0..pos]^T / sqrt(32)) V[0..pos]
+//   lm_decode_sample     inverse-CDF draw from softmax(logits / sigma) with a uniform number from device memory
+//   lm_decode_advance    pos += 1
+//
+// Everything that changes from step to step -- the position, the tokens, the uniforms -- lives in device memory: a step is
+// a fixed sequence of launches with fixed arguments (what a captured graph replays).  `pos` follows the convention of the
+// dropout keys of lm.hip: by value, overridden by *pos_dev when that pointer is non-NULL.  A position outside the buffers
+// (which the host cannot check when it sits in device memory) makes a kernel return without touching memory.
+// Sums are merged in fixed orders: no float atomics, the same inputs give the same bits.
+#include <algorithm>
+
+#include "smt_common.h"
+
+namespace smt {
+
+constexpr int DEC_DH = 32;                   // head dim, as in lm.hip
+constexpr int DEC_CHUNK = 256;               // cache rows per workgroup of the attention kernel
+constexpr int DEC_PART = 36;                 // floats per partial softmax: m, z, 2 unused, o[32] (16-byte aligned)
+constexpr int DEC_ROWS = 8;                  // output columns per workgroup of the linear kernel
+constexpr int DEC_KW = 128;                  // contraction elements per wave of the linear kernel (two per lane)
+constexpr int DEC_KMAX = 16 * DEC_KW;        // ... and per launch (16 waves)
+constexpr float DEC_LOG2E = 1.4426950408889634f;
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// ------------------------------------------------------------------------------------------------ embedding
+__global__ __launch_bounds__(256) void lm_decode_embed_kernel(const long long* __restrict__ tok, const float* __restrict__ emb,
+                                                              const float* __restrict__ pe, float* __restrict__ out, int L_tok,
+                                                              int D, int vocab_rows, int pe_rows, float mul, int pos,
+                                                              const int* __restrict__ pos_dev) {
+  if (pos_dev) pos = *pos_dev;
+  if (pos < 0 || pos >= L_tok || pos >= pe_rows) return;
+  const int b = blockIdx.x;
+  const long long t = tok[(long long)b * L_tok + pos];
+  const bool ok = t >= 0 && t < vocab_rows;                   // a token outside the table: NaN, never a read past it
+  for (int c = threadIdx.x; c < D; c += 256)
+    out[(size_t)b * D + c] = ok ? emb[t * D + c] * mul + pe[(size_t)pos * D + c] : NAN;
+}
+
+// ------------------------------------------------------------------------------------------------ skinny linear
+// Sum 32 values per lane over the 64 lanes of a wave, leaving the total of value (lane >> 1) in v[0]: five
+// halving exchanges (a lane keeps the half its lane bit selects and sends the other) and one plain exchange -- 32 shuffles
+// instead of the 192 of 32 separate wave sums.  The order of the additions is fixed by the lane numbers.
+template <int CNT>
+__device__ __forceinline__ void dec_halve(float (&v)[32], int lane, int off) {
+  const bool up = (lane & off) != 0;
+#pragma unroll
+  for (int i = 0; i < CNT / 2; ++i) {
+    const float send = up ? v[i] : v[i + CNT / 2];
+    const float keep = up ? v[i + CNT / 2] : v[i];
+    v[i] = keep + __shfl_xor(send, off, 64);
+  }
+}
+__device__ __forceinline__ void dec_reduce32(float (&v)[32], int lane) {
+  dec_halve<32>(v, lane, 32);
+  dec_halve<16>(v, lane, 16);
+  dec_halve<8>(v, lane, 8);
+  dec_halve<4>(v, lane, 4);
+  dec_halve<2>(v, lane, 2);
+  v[0] += __shfl_xor(v[0], 1, 64);
+}
+
+// A workgroup owns DEC_ROWS consecutive output columns n and all BP (>= B, a power of two) batch rows.  The contraction is
+// split over its waves, DEC_KW elements each: a lane keeps its two x elements of every batch row in registers (2 BP) and
+// streams two elements of each of the eight weight rows -- a wave reads 512 contiguous bytes per weight row, all eight
+// loads in flight before the first product.  The 8 * BP per-lane products-of-two are summed over the lanes 32 at a
+// time (dec_reduce32), then over the waves through LDS in wave order; bias and ReLU on the way out.  Products and sums
+// are fp32 FMAs.  accumulate != 0 adds to `out` (the second and later launches of a contraction longer than DEC_KMAX).
+template <int BP, int MAXT>
+__global__ __launch_bounds__(MAXT) void lm_decode_linear_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                                const float* __restrict__ bias, float* out, int B, int N, int kc,
+                                                                int ldx, int ldw, int relu, int accumulate) {
+  constexpr int R = 32 / BP;                                  // weight rows per group of 32 values
+  __shared__ float red[MAXT / 64][DEC_ROWS * BP];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  const int k = w * DEC_KW + 2 * lane;
+  const bool live = k < kc;
+  const int n0 = blockIdx.x * DEC_ROWS;
+  f32x2 wr[DEC_ROWS], xr[BP];
+#pragma unroll
+  for (int r = 0; r < DEC_ROWS; ++r) {
+    const int n = min(n0 + r, N - 1);
+    wr[r] = live ? *(const f32x2*)(W + (size_t)n * ldw + k) : f32x2{0.f, 0.f};
+  }
+#pragma unroll
+  for (int b = 0; b < BP; ++b) xr[b] = (live && b < B) ? *(const f32x2*)(x + (size_t)b * ldx + k) : f32x2{0.f, 0.f};
+#pragma unroll
+  for (int g = 0; g < DEC_ROWS / R; ++g) {
+    float v[32];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int b = 0; b < BP; ++b) v[r * BP + b] = fmaf(wr[g * R + r].x, xr[b].x, wr[g * R + r].y * xr[b].y);
+    dec_reduce32(v, lane);
+    if ((lane & 1) == 0) red[w][g * 32 + (lane >> 1)] = v[0];
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < DEC_ROWS * BP; t += blockDim.x) {
+    const int n = n0 + t / BP, b = t % BP;
+    float s = red[0][t];
+    for (int ww = 1; ww < nw; ++ww) s += red[ww][t];
+    if (n < N && b < B) {
+      float* dst = out + (size_t)b * N + n;
+      if (accumulate) s += *dst;
+      if (bias) s += bias[n];
+      *dst = relu ? fmaxf(s, 0.f) : s;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ attention over the cache
+// One (batch, head) scans contiguous 128-byte rows of K and V [B, H, l_max, 32].  Workgroup (s, bh) takes cache rows
+// [256 s, 256 s + 256) up to pos; eight lanes share a row (16 bytes each: a wave loads 8 rows = 1 KiB per instruction, four
+// K and four V loads in flight), so a score costs three shuffles and the V row needs none; every lane group keeps its own
+// running maximum / sum / four output channels, merged over the eight groups of a wave by shuffles, over the four waves
+// through LDS in wave order, and over the workgroups by lm_decode_attn_merge_kernel in chunk order.  The step's own k / v
+// rows come from qkv (one wave stores them to the cache; no value read from cache row pos is used in this launch), rows
+// beyond pos are never read.
+struct DecAcc { float m, z; f32x4 o; };
+__device__ __forceinline__ void dec_merge(DecAcc& a, float m2, float z2, const f32x4& o2) {
+  const float mn = fmaxf(a.m, m2), ms = (mn == -INFINITY) ? 0.f : mn;
+  const float e1 = __builtin_amdgcn_exp2f(a.m - ms), e2 = __builtin_amdgcn_exp2f(m2 - ms);
+  a.z = a.z * e1 + z2 * e2;
+  a.o = a.o * e1 + o2 * e2;
+  a.m = mn;
+}
+
+__global__ __launch_bounds__(256) void lm_decode_attn_kernel(const float* __restrict__ qkv, float* kcache, float* vcache,
+                                                             float* __restrict__ ctx, float* __restrict__ part, int H, int l_max,
+                                                             int nsplit, int pos, const int* __restrict__ pos_dev) {
+  if (pos_dev) pos = *pos_dev;
+  if (pos < 0 || pos >= l_max) return;
+  const int s = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H, d = H * DEC_DH;
+  const int c0 = s * DEC_CHUNK;
+  if (c0 > pos) return;                                       // uniform: no visible row in this chunk (the merge skips it too)
+  __shared__ float red[4][8][6];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 3, c = lane & 7;
+  const float* qrow = qkv + (size_t)b * 3 * d + h * DEC_DH + 4 * c;
+  const f32x4 q = *(const f32x4*)qrow * (rsqrtf((float)DEC_DH) * DEC_LOG2E);   // base-2 scores: exp2 is one instruction
+  const f32x4 kn = *(const f32x4*)(qrow + d), vn = *(const f32x4*)(qrow + 2 * d);
+  float* kb = kcache + (size_t)bh * l_max * DEC_DH + 4 * c;
+  float* vb = vcache + (size_t)bh * l_max * DEC_DH + 4 * c;
+  if (pos - c0 < DEC_CHUNK && w == 0 && g == 0) {             // the chunk that holds row pos
+    *(f32x4*)(kb + (size_t)pos * DEC_DH) = kn;
+    *(f32x4*)(vb + (size_t)pos * DEC_DH) = vn;
+  }
+  const int end = min(pos, c0 + DEC_CHUNK - 1);               // last visible row of this chunk
+  const int before = max(pos - 1, 0);
+  DecAcc a{-INFINITY, 0.f, f32x4{0.f, 0.f, 0.f, 0.f}};
+  for (int r0 = c0 + 32 * w; r0 <= end; r0 += 128) {
+    f32x4 kf[4], vf[4];
+    float sc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int row = min(r0 + 8 * u + g, end);
+      const size_t off = (size_t)(row == pos ? before : row) * DEC_DH;   // row pos: a load that is thrown away, from a row < pos (or row 0)
+      kf[u] = *(const f32x4*)(kb + off);
+      vf[u] = *(const f32x4*)(vb + off);
+      if (row == pos) { kf[u] = kn; vf[u] = vn; }
+    }
+    float mloc = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float t = fmaf(q.x, kf[u].x, fmaf(q.y, kf[u].y, fmaf(q.z, kf[u].z, q.w * kf[u].w)));
+      t += __shfl_xor(t, 1, 64);
+      t += __shfl_xor(t, 2, 64);
+      t += __shfl_xor(t, 4, 64);
+      sc[u] = (r0 + 8 * u + g <= end) ? t : -INFINITY;
+      mloc = fmaxf(mloc, sc[u]);
+    }
+    const float mn = fmaxf(a.m, mloc), ms = (mn == -INFINITY) ? 0.f : mn;
+    const float corr = __builtin_amdgcn_exp2f(a.m - ms);       // a.m = -inf: 0
+    a.z *= corr;
+    a.o *= corr;
+    a.m = mn;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float p = __builtin_amdgcn_exp2f(sc[u] - ms);     // masked: exp2(-inf) = 0
+      a.z += p;
+      a.o += vf[u] * p;
+    }
+  }
+#pragma unroll
+  for (int off = 8; off < 64; off <<= 1) {
+    const float m2 = __shfl_xor(a.m, off, 64), z2 = __shfl_xor(a.z, off, 64);
+    f32x4 o2;
+    o2.x = __shfl_xor(a.o.x, off, 64); o2.y = __shfl_xor(a.o.y, off, 64);
+    o2.z = __shfl_xor(a.o.z, off, 64); o2.w = __shfl_xor(a.o.w, off, 64);
+    dec_merge(a, m2, z2, o2);
+  }
+  if (g == 0) {
+    float* r = red[w][c];
+    r[0] = a.m; r[1] = a.z; r[2] = a.o.x; r[3] = a.o.y; r[4] = a.o.z; r[5] = a.o.w;
+  }
+  __syncthreads();
+  if (w == 0 && g == 0) {
+    DecAcc t{red[0][c][0], red[0][c][1], f32x4{red[0][c][2], red[0][c][3], red[0][c][4], red[0][c][5]}};
+#pragma unroll
+    for (int ww = 1; ww < 4; ++ww)
+      dec_merge(t, red[ww][c][0], red[ww][c][1], f32x4{red[ww][c][2], red[ww][c][3], red[ww][c][4], red[ww][c][5]});
+    if (nsplit == 1) {
+      *(f32x4*)(ctx + (size_t)b * d + h * DEC_DH + 4 * c) = t.o * (1.f / t.z);    // row 0 is always visible: z > 0
+    } else {
+      float* dst = part + ((size_t)bh * nsplit + s) * DEC_PART;
+      if (c == 0) { dst[0] = t.m; dst[1] = t.z; }
+      *(f32x4*)(dst + 4 + 4 * c) = t.o;
+    }
+  }
+}
+
+// ctx = sum over the chunks 0 .. pos / 256, in chunk order, of the partial softmaxes; a thread per (batch, head, channel)
+__global__ __launch_bounds__(256) void lm_decode_attn_merge_kernel(const float* __restrict__ part, float* __restrict__ ctx, int BH,
+                                                                   int l_max, int nsplit, int pos, const int* __restrict__ pos_dev) {
+  if (pos_dev) pos = *pos_dev;
+  if (pos < 0 || pos >= l_max) return;
+  const int t = blockIdx.x * 256 + threadIdx.x, bh = t >> 5, c = t & 31;
+  if (bh >= BH) return;
+  const int ns = min(nsplit, pos / DEC_CHUNK + 1);
+  const float* p = part + (size_t)bh * nsplit * DEC_PART;
+  float mm = -INFINITY;
+  for (int s = 0; s < ns; ++s) mm = fmaxf(mm, p[s * DEC_PART]);
+  float z = 0.f, o = 0.f;
+  for (int s = 0; s < ns; ++s) {
+    const float e = __builtin_amdgcn_exp2f(p[s * DEC_PART] - mm);
+    z = fmaf(p[s * DEC_PART + 1], e, z);
+    o = fmaf(p[s * DEC_PART + 4 + c], e, o);
+  }
+  ctx[(size_t)bh * DEC_DH + c] = o / z;                       // [B, H * 32]: (b H + h) * 32 + c
+}
+
+// ------------------------------------------------------------------------------------------------ sampler
+// One wave per batch row; lane i owns the contiguous codes [i ch, (i + 1) ch), ch = ceil(V / 64).  p = exp((l - max) /
+// sigma); the cumulative sum runs lane by lane (an inclusive scan of the lanes' totals, then along the lane's own codes),
+// S is the scan's last element.  The code is the smallest k whose cumulative sum exceeds u S; if rounding leaves none
+// (u S >= the last cumulative sum), the last k with p > 0.
+__global__ __launch_bounds__(256) void lm_decode_sample_kernel(const float* __restrict__ logits, const float* __restrict__ uni,
+                                                               long long* __restrict__ tokens, long long* __restrict__ codes, int B,
+                                                               int V, int L_tok, int n_steps, float inv_sigma, int token_offset,
+                                                               int pos, const int* __restrict__ pos_dev) {
+  if (pos_dev) pos = *pos_dev;
+  if (pos < 0 || pos >= n_steps || pos + 1 >= L_tok) return;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const float* l = logits + (size_t)b * V;
+  const int ch = (V + 63) / 64, lo = min(V, lane * ch), hi = min(V, lo + ch);
+  float m = -INFINITY;
+  for (int i = lo; i < hi; ++i) m = fmaxf(m, l[i]);
+  m = wave_max(m);
+  float t = 0.f;
+  int last = -1;
+  for (int i = lo; i < hi; ++i) {
+    const float p = expf((l[i] - m) * inv_sigma);
+    t += p;
+    if (p > 0.f) last = i;
+  }
+  float inc = t;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += y;
+  }
+  const float thr = uni[(size_t)pos * B + b] * __shfl(inc, 63, 64);
+  float cum = __shfl_up(inc, 1, 64);
+  if (lane == 0) cum = 0.f;
+  int k = 0x7fffffff;
+  for (int i = lo; i < hi; ++i) {
+    cum += expf((l[i] - m) * inv_sigma);
+    if (cum > thr && k == 0x7fffffff) k = i;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    k = min(k, __shfl_xor(k, o, 64));
+    last = max(last, __shfl_xor(last, o, 64));
+  }
+  if (k == 0x7fffffff) k = max(last, 0);
+  if (lane == 0) {
+    tokens[(size_t)b * L_tok + pos + 1] = k + token_offset;
+    codes[(size_t)b * n_steps + pos] = k;
+  }
+}
+
+__global__ void lm_decode_advance_kernel(int* pos_dev) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) pos_dev[0] += 1;
+}
+
+static int dec_splits(int l_max) { return (l_max + DEC_CHUNK - 1) / DEC_CHUNK; }
+
+template <int BP>
+static void dec_linear_launch(const float* x, const float* w, const float* bias, float* out, int B, int N, int kc, int ld, int relu,
+                              int accumulate, hipStream_t stream) {
+  const int nw = (kc + DEC_KW - 1) / DEC_KW, grid = (N + DEC_ROWS - 1) / DEC_ROWS;
+  if (nw <= 4)
+    lm_decode_linear_kernel<BP, 256><<<grid, 64 * nw, 0, stream>>>(x, w, bias, out, B, N, kc, ld, ld, relu, accumulate);
+  else
+    lm_decode_linear_kernel<BP, 1024><<<grid, 64 * nw, 0, stream>>>(x, w, bias, out, B, N, kc, ld, ld, relu, accumulate);
+}
+
+}  // namespace smt
+
+using namespace smt;
+
+extern "C" int smt_lm_decode_embed(const int64_t* tokens, const float* emb, const float* pe, float* out, int batch, int tok_len,
+                                   int dim, int vocab_rows, int pe_rows, float mul, int pos, const int* pos_dev, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(tokens && emb && pe && out, "smt_lm_decode_embed: null pointer");
+  SMT_CHECK_ARG(batch >= 1 && batch <= 32 && tok_len >= 1 && dim >= 1 && vocab_rows >= 1 && pe_rows >= 1,
+                "smt_lm_decode_embed: batch must be 1..32 and every size positive (batch %d)", batch);
+  SMT_CHECK_ARG(pos_dev || (pos >= 0 && pos < tok_len && pos < pe_rows), "smt_lm_decode_embed: pos %d outside the token buffer (%d) or the position table (%d)",
+                pos, tok_len, pe_rows);
+  lm_decode_embed_kernel<<<batch, 256, 0, stream>>>((const long long*)tokens, emb, pe, out, tok_len, dim, vocab_rows, pe_rows, mul, pos, pos_dev);
+  SMT_CHECK_LAUNCH("lm_decode_embed");
+  return 0;
+}
+
+extern "C" int smt_lm_decode_linear(const float* x, const float* w, const float* bias, float* out, int batch, int in_dim, int out_dim,
+                                    int relu, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(x && w && out, "smt_lm_decode_linear: null pointer");
+  SMT_CHECK_ARG(batch >= 1 && batch <= 32, "smt_lm_decode_linear: batch must be 1..32 (got %d)", batch);
+  SMT_CHECK_ARG(in_dim >= 64 && in_dim % 64 == 0 && out_dim >= 1, "smt_lm_decode_linear: in_dim must be a positive multiple of 64, out_dim >= 1 (got %d, %d)",
+                in_dim, out_dim);
+  for (int k0 = 0; k0 < in_dim; k0 += DEC_KMAX) {
+    const int kc = std::min(DEC_KMAX, in_dim - k0), last = k0 + kc == in_dim;
+    const float* bl = last ? bias : nullptr;
+    const int rl = last ? relu : 0, acc = k0 > 0;
+    if (batch <= 4) dec_linear_launch<4>(x + k0, w + k0, bl, out, batch, out_dim, kc, in_dim, rl, acc, stream);
+    else if (batch <= 8) dec_linear_launch<8>(x + k0, w + k0, bl, out, batch, out_dim, kc, in_dim, rl, acc, stream);
+    else if (batch <= 16) dec_linear_launch<16>(x + k0, w + k0, bl, out, batch, out_dim, kc, in_dim, rl, acc, stream);
+    else dec_linear_launch<32>(x + k0, w + k0, bl, out, batch, out_dim, kc, in_dim, rl, acc, stream);
+    SMT_CHECK_LAUNCH("lm_decode_linear");
+  }
+  return 0;
+}
+
+extern "C" size_t smt_lm_decode_attention_workspace_bytes(int batch, int heads, int l_max) {
+  if (batch <= 0 || heads <= 0 || l_max <= 0 || dec_splits(l_max) == 1) return 0;
+  return (size_t)batch * heads * dec_splits(l_max) * DEC_PART * sizeof(float);
+}
+
+extern "C" int smt_lm_decode_attention(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace,
+                                       size_t workspace_bytes, int batch, int heads, int l_max, int pos, const int* pos_dev,
+                                       smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(qkv && k_cache && v_cache && ctx, "smt_lm_decode_attention: null pointer");
+  SMT_CHECK_ARG(batch >= 1 && batch <= 32 && heads >= 1 && l_max >= 1, "smt_lm_decode_attention: batch must be 1..32, heads and l_max positive");
+  SMT_CHECK_ARG((long long)batch * heads <= 65535 && (long long)l_max * DEC_DH < (1ll << 31), "smt_lm_decode_attention: batch * heads <= 65535, l_max * 32 < 2^31");
+  SMT_CHECK_ARG(pos_dev || (pos >= 0 && pos < l_max), "smt_lm_decode_attention: pos %d outside the cache (%d rows)", pos, l_max);
+  const int nsplit = dec_splits(l_max);
+  SMT_CHECK_ARG(nsplit == 1 || (workspace && workspace_bytes >= smt_lm_decode_attention_workspace_bytes(batch, heads, l_max)),
+                "smt_lm_decode_attention: workspace too small");
+  lm_decode_attn_kernel<<<dim3(nsplit, batch * heads), 256, 0, stream>>>(qkv, k_cache, v_cache, ctx, (float*)workspace, heads, l_max, nsplit, pos, pos_dev);
+  SMT_CHECK_LAUNCH("lm_decode_attention");
+  if (nsplit > 1) {
+    lm_decode_attn_merge_kernel<<<(batch * heads * DEC_DH + 255) / 256, 256, 0, stream>>>((const float*)workspace, ctx, batch * heads, l_max, nsplit, pos, pos_dev);
+    SMT_CHECK_LAUNCH("lm_decode_attention_merge");
+  }
+  return 0;
+}
+
+extern "C" int smt_lm_decode_sample(const float* logits, const float* uniforms, int64_t* tokens, int64_t* codes, int batch, int vocab,
+                                    int tok_len, int n_steps, float inv_sigma, int token_offset, int pos, const int* pos_dev,
+                                    smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(logits && uniforms && tokens && codes, "smt_lm_decode_sample: null pointer");
+  SMT_CHECK_ARG(batch >= 1 && batch <= 32 && vocab >= 1 && n_steps >= 1 && tok_len >= 2, "smt_lm_decode_sample: batch must be 1..32, vocab and n_steps positive");
+  SMT_CHECK_ARG(inv_sigma > 0.f, "smt_lm_decode_sample: 1 / sigma must be positive");
+  SMT_CHECK_ARG(pos_dev || (pos >= 0 && pos < n_steps && pos + 1 < tok_len), "smt_lm_decode_sample: pos %d outside the uniforms (%d rows) or the token buffer (%d)",
+                pos, n_steps, tok_len);
+  lm_decode_sample_kernel<<<(batch + 3) / 4, 256, 0, stream>>>(logits, uniforms, (long long*)tokens, (long long*)codes, batch, vocab, tok_len, n_steps,
+                                                             inv_sigma, token_offset, pos, pos_dev);
+  SMT_CHECK_LAUNCH("lm_decode_sample");
+  return 0;
+}
+
+extern "C" int smt_lm_decode_advance(int* pos_dev, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(pos_dev, "smt_lm_decode_advance: null pointer");
+  lm_decode_advance_kernel<<<1, 64, 0, stream>>>(pos_dev);
+  SMT_CHECK_LAUNCH("lm_decode_advance");
+  return 0;
+}

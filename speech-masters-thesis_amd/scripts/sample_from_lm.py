@@ -1,7 +1,7 @@
 """Ancestral samples from a trained TransformerLM (reference scripts/sample_from_lm.py).
 
     python -m scripts.sample_from_lm --log_dir ./logs/transformer_lm --ckpt_num 5000 --dump_dir ./outputs \
-        --n_samples 4 --n_steps 512 [--sigma 1.0]
+        --n_samples 4 --n_steps 512 [--sigma 1.0] [--causal [--graph] [--seed 0]]
 
 Writes ``<dump_dir>/<ModelClass>@<ckpt>/sample_<i>.wav``, ``mel_spectrograms.png`` and ``tokens.txt`` like the reference.
 The sampling loop, the dequantisation and the VQ-VAE decoder run on MI355X through libsmt_hip.so (`TransformerLM.sample`);
@@ -29,6 +29,9 @@ def parse_args(argv=None):
     p.add_argument("--n_samples", type=int, default=4, help="Batch size for inference")
     p.add_argument("--n_steps", type=int, default=1024, help="Number of codes to sample")
     p.add_argument("--sigma", type=float, default=1.0, help="Sampling temperature")
+    p.add_argument("--causal", action="store_true", help="Sample with the causal mask the model was trained with (key/value cache)")
+    p.add_argument("--graph", action="store_true", help="With --causal: replay one captured decoding step")
+    p.add_argument("--seed", type=int, default=None, help="With --causal: seed of the generator the uniforms are drawn from")
     return p.parse_args(argv)
 
 
@@ -64,7 +67,14 @@ def main(argv=None):
     dump_dir = os.path.join(args.dump_dir, f"{type(model).__name__}@{args.ckpt_num}")
     os.makedirs(dump_dir, exist_ok=True)
 
-    x_samples, q_samples = model.sample(batch_size=args.n_samples, n_steps=args.n_steps, device=device, sigma=args.sigma)
+    if args.causal:
+        generator = None if args.seed is None else torch.Generator(device=device).manual_seed(args.seed)
+        x_samples, q_samples = model.sample(batch_size=args.n_samples, n_steps=args.n_steps, device=device, sigma=args.sigma,
+                                            causal=True, generator=generator, graph=args.graph)
+    else:
+        if args.graph or args.seed is not None:
+            raise ValueError("--graph and --seed belong to --causal")
+        x_samples, q_samples = model.sample(batch_size=args.n_samples, n_steps=args.n_steps, device=device, sigma=args.sigma)
     logger.info("Generated token samples")
 
     from datasets.transforms import MelSpectrogram

@@ -238,3 +238,119 @@ def cross_entropy(logits, target):
     the reference's boolean row selection turned into target = -1 on the rows it drops."""
     assert target.dtype == torch.int64
     return _CrossEntropy.apply(logits, target)
+
+
+# ------------------------------------------------------------------------------------------------ incremental decoding
+# csrc/lm_decode.hip, include/smt_hip.h "Incremental decoding": eval mode, fp32, no autograd.  Every op writes into a buffer the
+# caller owns (DecodeState) and takes the position by value (`pos`) or from device memory (`pos_dev`, which overrides it).
+def _pos_args(pos, pos_dev):
+    if pos_dev is not None:
+        assert pos_dev.is_cuda and pos_dev.dtype == torch.int32 and pos_dev.numel() == 1
+    return int(pos), N.ptr(pos_dev)
+
+
+def decode_embed(tokens, weight, pe, out, pos=0, pos_dev=None):
+    """out[b] = weight[tokens[b, pos]] * sqrt(dim) + pe[pos]; tokens [batch, tok_len] int64, out [batch, dim]."""
+    b, l = tokens.shape
+    d = weight.shape[1]
+    assert tokens.dtype == torch.int64 and pe.shape[-1] == d and out.shape == (b, d) and out.dtype == torch.float32
+    p, pd = _pos_args(pos, pos_dev)
+    N.check(N.lib().smt_lm_decode_embed(N.ptr(tokens), N.ptr(_f32(weight)), N.ptr(_f32(pe)), N.ptr(out), b, l, d, weight.shape[0],
+                                        pe.shape[0], math.sqrt(d), p, pd, N.stream_ptr()), "smt_lm_decode_embed")
+    return out
+
+
+def decode_linear(x, weight, bias=None, out=None, relu=False):
+    """out [batch, n] = x [batch, k] @ weight [n, k]^T (+ bias) (ReLU); batch <= 32, k % 64 == 0 (else RuntimeError)."""
+    b, k = x.shape
+    n = weight.shape[0]
+    assert weight.shape == (n, k) and (bias is None or bias.shape == (n,))
+    if out is None:
+        out = torch.empty(b, n, device=x.device, dtype=torch.float32)
+    assert out.shape == (b, n) and out.dtype == torch.float32
+    N.check(N.lib().smt_lm_decode_linear(N.ptr(_f32(x)), N.ptr(_f32(weight)), N.ptr(None if bias is None else _f32(bias)), N.ptr(out),
+                                         b, k, n, int(relu), N.stream_ptr()), "smt_lm_decode_linear")
+    return out
+
+
+def decode_attention_workspace(batch, heads, l_max, device):
+    """The partial-softmax buffer of `decode_attention` for caches of l_max rows (None when none is needed)."""
+    nbytes = N.lib().smt_lm_decode_attention_workspace_bytes(batch, heads, l_max)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def decode_attention(qkv, k_cache, v_cache, ctx, workspace=None, pos=0, pos_dev=None):
+    """qkv [batch, 3 * heads * 32] of the token at `pos`; k_cache / v_cache [batch, heads, l_max, 32] get its k / v rows at row
+    pos; ctx [batch, heads * 32] = softmax(q K[0..pos]^T / sqrt(32)) V[0..pos]."""
+    b, h, l_max, dh = k_cache.shape
+    assert dh == 32 and v_cache.shape == k_cache.shape and qkv.shape == (b, 3 * h * 32) and ctx.shape == (b, h * 32)
+    assert k_cache.dtype == v_cache.dtype == ctx.dtype == torch.float32
+    p, pd = _pos_args(pos, pos_dev)
+    N.check(N.lib().smt_lm_decode_attention(N.ptr(_f32(qkv)), N.ptr(k_cache), N.ptr(v_cache), N.ptr(ctx), N.ptr(workspace),
+                                            0 if workspace is None else workspace.numel(), b, h, l_max, p, pd, N.stream_ptr()),
+            "smt_lm_decode_attention")
+    return ctx
+
+
+def decode_sample(logits, uniforms, tokens, codes, sigma=1.0, pos=0, pos_dev=None, token_offset=2):
+    """Inverse-CDF draw from softmax(logits / sigma) with uniforms[pos, b]: tokens[b, pos + 1] = k + token_offset,
+    codes[b, pos] = k.  logits [batch, vocab], uniforms [n_steps, batch] f32, tokens [batch, tok_len] / codes [batch, n_steps] int64."""
+    b, v = logits.shape
+    n_steps = uniforms.shape[0]
+    assert uniforms.shape == (n_steps, b) and uniforms.dtype == torch.float32 and tokens.shape[0] == b and codes.shape == (b, n_steps)
+    assert tokens.dtype == codes.dtype == torch.int64
+    p, pd = _pos_args(pos, pos_dev)
+    N.check(N.lib().smt_lm_decode_sample(N.ptr(_f32(logits)), N.ptr(uniforms), N.ptr(tokens), N.ptr(codes), b, v, tokens.shape[1], n_steps,
+                                         1.0 / sigma, token_offset, p, pd, N.stream_ptr()), "smt_lm_decode_sample")
+
+
+def decode_advance(pos_dev):
+    """pos_dev += 1 on the device."""
+    assert pos_dev.is_cuda and pos_dev.dtype == torch.int32 and pos_dev.numel() == 1
+    N.check(N.lib().smt_lm_decode_advance(N.ptr(pos_dev), N.stream_ptr()), "smt_lm_decode_advance")
+
+
+def decode_layer_norm(x, h, h_bias, gamma, beta, eps, out, stats):
+    """smt_lm_add_ln_fwd on `rows = batch` without dropout, into caller-owned `out` / `stats`."""
+    rows, d = x.shape
+    N.check(N.lib().smt_lm_add_ln_fwd(N.ptr(x), N.ptr(h), N.ptr(h_bias), N.ptr(_f32(gamma)), N.ptr(_f32(beta)), N.ptr(out), N.ptr(stats),
+                                      rows, d, eps, 0, None, 0, 1.0, N.stream_ptr()), "smt_lm_add_ln_fwd")
+    return out
+
+
+class DecodeState:
+    """Every buffer of an incremental decoding loop (TransformerLM.sample(causal=True) / step_logits): the key/value cache
+    [layers, 2, batch, heads, l_max, 32], the token [batch, n_steps + 1] and code [batch, n_steps] buffers, the position
+    (``pos_dev`` on the device, mirrored by ``pos`` on the host), the uniforms [n_steps, batch] and the activations of one step.
+    Nothing here comes from the grow-only workspace of smt_amd.native: captured launches keep pointing at these tensors."""
+
+    def __init__(self, batch, n_steps, dim, heads, dim_ff, vocab, layers, device, first_token=1, uniforms=None):
+        assert dim == heads * 32, "the attention kernels are built for head dim 32"
+        f32 = dict(device=device, dtype=torch.float32)
+        self.batch, self.n_steps = batch, n_steps
+        self.kv = torch.empty(layers, 2, batch, heads, n_steps, 32, **f32)           # rows beyond pos are never read
+        self.tokens = torch.zeros(batch, n_steps + 1, device=device, dtype=torch.int64)
+        self.tokens[:, 0] = first_token
+        self.codes = torch.zeros(batch, n_steps, device=device, dtype=torch.int64)
+        self.pos_dev = torch.zeros(1, device=device, dtype=torch.int32)
+        self.pos = 0
+        self.uniforms = torch.zeros(n_steps, batch, **f32) if uniforms is None else uniforms.to(**f32).contiguous()
+        assert self.uniforms.shape == (n_steps, batch)
+        self.h, self.h1, self.ctx, self.a = (torch.empty(batch, dim, **f32) for _ in range(4))
+        self.qkv = torch.empty(batch, 3 * dim, **f32)
+        self.f = torch.empty(batch, dim_ff, **f32)
+        self.stats = torch.empty(batch, 2, **f32)
+        self.logits = torch.empty(batch, vocab, **f32)
+        self.attn_ws = decode_attention_workspace(batch, heads, n_steps, device)
+
+    def advance(self):
+        """pos += 1, on the device and in the host mirror."""
+        decode_advance(self.pos_dev)
+        self.pos += 1
+
+    def push(self, tokens):
+        """Force the next token (teacher forcing): tokens [batch] int64 -> tokens[:, pos + 1], then advance."""
+        if self.pos + 1 > self.n_steps:
+            raise ValueError(f"DecodeState.push: the token buffer holds {self.n_steps + 1} tokens")
+        self.tokens[:, self.pos + 1] = tokens.to(self.tokens.device, torch.int64)
+        self.advance()
