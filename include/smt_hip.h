@@ -490,6 +490,25 @@ int smt_lm_decode_attention(const float* qkv, float* k_cache, float* v_cache, fl
 int smt_lm_decode_sample(const float* logits, const float* uniforms, int64_t* tokens, int64_t* codes, int batch, int vocab,
                          int tok_len, int n_steps, float inv_sigma, int token_offset, int pos, const int* pos_dev, smt_stream_t stream);
 
+/* The same draw over a kept set, the first n codes of the order pi (logit descending, then code index ascending), with
+ * w_i = exp((logits[b, i] - max_i) * inv_sigma):
+ *   candidates  top_k > 0: the first K = min(top_k, vocab) codes of pi; top_k = 0: all.  W = their total weight.
+ *   kept        top_p < 1: the smallest n >= 1 whose first-n weight is >= top_p * W (so top-p acts on the distribution
+ *               renormalised over the candidates); top_p = 1: n = the number of candidates.  Equal logits at the cut are
+ *               taken lowest index first.  kept (NULL or [n_steps, batch] int32) gets n at row pos.
+ *   draw        as smt_lm_decode_sample over the kept codes in code-index order (the others have weight 0 and are never drawn); with top_k = 0
+ *               and top_p = 1 the codes are bit-identical to smt_lm_decode_sample.
+ * top_k >= 0, 0 < top_p <= 1, vocab <= 4096 (keys and weights of a row sit in 32 KiB of LDS). */
+int smt_lm_decode_sample_filtered(const float* logits, const float* uniforms, int64_t* tokens, int64_t* codes, int batch, int vocab,
+                                  int tok_len, int n_steps, float inv_sigma, int token_offset, int top_k, float top_p,
+                                  int32_t* kept, int pos, const int* pos_dev, smt_stream_t stream);
+
+/* Keys / values of a whole prompt: qkv [batch, len, 3*heads*32] (the batched in-projection, batch-major; 16-byte aligned)
+ * -> its k and v thirds into rows 0..len-1 of k_cache / v_cache [batch, heads, l_max, 32]; rows >= len are not touched.
+ * 1 <= len <= l_max; batch, heads and l_max bounded as in smt_lm_decode_attention. */
+int smt_lm_decode_prefill_kv(const float* qkv, float* k_cache, float* v_cache, int batch, int len, int heads, int l_max,
+                             smt_stream_t stream);
+
 /* pos_dev[0] += 1: the last launch of a step. */
 int smt_lm_decode_advance(int* pos_dev, smt_stream_t stream);
 

@@ -5,6 +5,8 @@
 //   lm_decode_linear     out[B, N] = x[B, K] W[N, K]^T (+ bias) (ReLU): the weights are streamed once, B <= 32 rows ride along
 //   lm_decode_attention  this step's k / v rows into the cache, softmax(q K[0..pos]^T / sqrt(32)) V[0..pos]
 //   lm_decode_sample     inverse-CDF draw from softmax(logits / sigma) with a uniform number from device memory
+//   lm_decode_sample_filtered  the same draw over the top-k / nucleus (top-p) prefix of the codes ordered by logit
+//   lm_decode_prefill_kv the keys / values of a whole prompt (batched in-projection) into cache rows 0..len-1
 //   lm_decode_advance    pos += 1
 //
 // Everything that changes from step to step -- the position, the tokens, the uniforms -- lives in device memory: a step is
@@ -237,16 +239,12 @@ __global__ __launch_bounds__(256) void lm_decode_attn_merge_kernel(const float* 
 // One wave per batch row; lane i owns the contiguous codes [i ch, (i + 1) ch), ch = ceil(V / 64).  p = exp((l - max) /
 // sigma); the cumulative sum runs lane by lane (an inclusive scan of the lanes' totals, then along the lane's own codes),
 // S is the scan's last element.  The code is the smallest k whose cumulative sum exceeds u S; if rounding leaves none
-// (u S >= the last cumulative sum), the last k with p > 0.
-__global__ __launch_bounds__(256) void lm_decode_sample_kernel(const float* __restrict__ logits, const float* __restrict__ uni,
-                                                               long long* __restrict__ tokens, long long* __restrict__ codes, int B,
-                                                               int V, int L_tok, int n_steps, float inv_sigma, int token_offset,
-                                                               int pos, const int* __restrict__ pos_dev) {
-  if (pos_dev) pos = *pos_dev;
-  if (pos < 0 || pos >= n_steps || pos + 1 >= L_tok) return;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (b >= B) return;
-  const float* l = logits + (size_t)b * V;
+// (u S >= the last cumulative sum), the last k with p > 0.  FILTER: a code i with keep[i] == 0 has p = 0 and is never the
+// answer (keep: LDS, one word per code, written by the filtered kernel below); nothing else differs, so "everything kept"
+// draws the same code.
+template <bool FILTER>
+__device__ __forceinline__ int dec_draw(const float* __restrict__ l, const float* __restrict__ u, const unsigned* keep, int V,
+                                        float inv_sigma, int lane) {
   const int ch = (V + 63) / 64, lo = min(V, lane * ch), hi = min(V, lo + ch);
   float m = -INFINITY;
   for (int i = lo; i < hi; ++i) m = fmaxf(m, l[i]);
@@ -254,7 +252,8 @@ __global__ __launch_bounds__(256) void lm_decode_sample_kernel(const float* __re
   float t = 0.f;
   int last = -1;
   for (int i = lo; i < hi; ++i) {
-    const float p = expf((l[i] - m) * inv_sigma);
+    float p = expf((l[i] - m) * inv_sigma);
+    if (FILTER) p = keep[i] ? p : 0.f;
     t += p;
     if (p > 0.f) last = i;
   }
@@ -264,13 +263,19 @@ __global__ __launch_bounds__(256) void lm_decode_sample_kernel(const float* __re
     const float y = __shfl_up(inc, o, 64);
     if (lane >= o) inc += y;
   }
-  const float thr = uni[(size_t)pos * B + b] * __shfl(inc, 63, 64);
+  const float thr = *u * __shfl(inc, 63, 64);
   float cum = __shfl_up(inc, 1, 64);
   if (lane == 0) cum = 0.f;
   int k = 0x7fffffff;
   for (int i = lo; i < hi; ++i) {
-    cum += expf((l[i] - m) * inv_sigma);
-    if (cum > thr && k == 0x7fffffff) k = i;
+    float p = expf((l[i] - m) * inv_sigma);
+    bool in = true;                                           // the scan's sums are not monotone to the last bit: a lane behind
+    if (FILTER) {                                             // the kept codes may hold a sum above thr, and must not answer
+      in = keep[i] != 0u;
+      p = in ? p : 0.f;
+    }
+    cum += p;
+    if (cum > thr && in && k == 0x7fffffff) k = i;
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -278,10 +283,143 @@ __global__ __launch_bounds__(256) void lm_decode_sample_kernel(const float* __re
     last = max(last, __shfl_xor(last, o, 64));
   }
   if (k == 0x7fffffff) k = max(last, 0);
+  return k;
+}
+
+__global__ __launch_bounds__(256) void lm_decode_sample_kernel(const float* __restrict__ logits, const float* __restrict__ uni,
+                                                               long long* __restrict__ tokens, long long* __restrict__ codes, int B,
+                                                               int V, int L_tok, int n_steps, float inv_sigma, int token_offset,
+                                                               int pos, const int* __restrict__ pos_dev) {
+  if (pos_dev) pos = *pos_dev;
+  if (pos < 0 || pos >= n_steps || pos + 1 >= L_tok) return;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const int k = dec_draw<false>(logits + (size_t)b * V, uni + (size_t)pos * B + b, nullptr, V, inv_sigma, lane);
   if (lane == 0) {
     tokens[(size_t)b * L_tok + pos + 1] = k + token_offset;
     codes[(size_t)b * n_steps + pos] = k;
   }
+}
+
+// The same draw restricted to a kept set: the first n codes of the order pi (logit descending, then code index ascending).
+//   candidates  the first K = min(top_k, V) codes of pi (top_k = 0: all V); W = their total weight w = exp((l - max) / sigma)
+//   kept        top_p < 1: the smallest n >= 1 whose first-n weight is >= top_p W; else n = the number of candidates
+// A prefix of pi is { key > T } plus the first r codes, by index, of { key == T }, where key is an order-preserving 32-bit
+// image of the logit -- so no sort: T is found bit by bit, from the top, as the largest value whose count (top-k: >= K) or
+// weight (top-p: >= top_p W) of { key >= T } still suffices; 32 passes each over the keys and weights in LDS (code i belongs
+// to lane i % 64 here: conflict-free, and a lane reads back only what it wrote), a wave reduction after each pass.  Tied
+// codes at T have one weight wT, so r is the smallest count with A + r wT >= top_p W (A: the weight above T), found by
+// bisection; their ranks by index come from ballots, 64 codes at a time.  Every sum runs lane-locally in index order and
+// then through the same xor butterfly: a sum over fewer codes is never larger, which is what the bitwise search relies on.
+constexpr int DEC_VMAX = 4096;               // vocabulary cap of the filtered sampler: 32 KiB of LDS per wave
+
+__device__ __forceinline__ unsigned dec_key(float x) {
+  const unsigned u = __float_as_uint(x + 0.f);                // -0 -> +0: equal logits, equal keys
+  return max((u & 0x80000000u) ? ~u : (u | 0x80000000u), 1u); // 0 is kept free: it marks a code outside the candidates
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// weight resp. number of the codes with key >= t (ge) or key > t (!ge)
+__device__ __forceinline__ float dec_mass(const unsigned* key, const float* wt, int V, int lane, unsigned t, bool ge) {
+  float s = 0.f;
+  for (int i = lane; i < V; i += 64) s += (ge ? key[i] >= t : key[i] > t) ? wt[i] : 0.f;
+  return wave_sum(s);
+}
+__device__ __forceinline__ int dec_count(const unsigned* key, int V, int lane, unsigned t, bool ge) {
+  int c = 0;
+  for (int i = lane; i < V; i += 64) c += (ge ? key[i] >= t : key[i] > t) ? 1 : 0;
+  return wave_sum_i(c);
+}
+// key[i] = 0 for every code outside { key > t } + the first r, by index, of { key == t }; `flag`: 1 for the codes inside
+__device__ __forceinline__ void dec_cut(unsigned* key, float* wt, int V, int lane, unsigned t, int r, bool flag) {
+  int seen = 0;
+  for (int i0 = 0; i0 < V; i0 += 64) {                        // uniform trip count: the ballot needs the whole wave
+    const int i = i0 + lane;
+    const unsigned kv = i < V ? key[i] : 0u;
+    const bool eq = i < V && kv == t;
+    const unsigned long long tied = __ballot(eq);
+    const int rank = seen + __popcll(tied & ((1ull << lane) - 1ull));
+    seen += __popcll(tied);
+    if (i < V) {
+      const bool in = kv > t || (eq && rank < r);
+      key[i] = in ? (flag ? 1u : kv) : 0u;
+      if (!in) wt[i] = 0.f;
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void lm_decode_sample_filtered_kernel(const float* __restrict__ logits, const float* __restrict__ uni,
+                                                                       long long* __restrict__ tokens, long long* __restrict__ codes,
+                                                                       int* __restrict__ kept, int B, int V, int L_tok, int n_steps,
+                                                                       float inv_sigma, int token_offset, int top_k, float top_p, int pos,
+                                                                       const int* __restrict__ pos_dev) {
+  if (pos_dev) pos = *pos_dev;
+  if (pos < 0 || pos >= n_steps || pos + 1 >= L_tok) return;
+  __shared__ unsigned key[DEC_VMAX];
+  __shared__ float wt[DEC_VMAX];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* l = logits + (size_t)b * V;
+  float m = -INFINITY;
+  for (int i = lane; i < V; i += 64) m = fmaxf(m, l[i]);
+  m = wave_max(m);
+  for (int i = lane; i < V; i += 64) {
+    key[i] = dec_key(l[i]);
+    wt[i] = expf((l[i] - m) * inv_sigma);
+  }
+  int n = V;
+  if (top_k > 0 && top_k < V) {                               // T = the top_k-th largest key
+    unsigned t = 0u;
+    for (unsigned bit = 0x80000000u; bit; bit >>= 1)
+      if (dec_count(key, V, lane, t | bit, true) >= top_k) t |= bit;
+    dec_cut(key, wt, V, lane, t, top_k - dec_count(key, V, lane, t, false), false);
+    n = top_k;
+  }
+  if (top_p < 1.f) {
+    const float target = top_p * dec_mass(key, wt, V, lane, 0u, true);      // top_p W: a code outside the candidates has weight 0
+    unsigned t = 0u;
+    for (unsigned bit = 0x80000000u; bit; bit >>= 1)
+      if (dec_mass(key, wt, V, lane, t | bit, true) >= target) t |= bit;
+    const float above = dec_mass(key, wt, V, lane, t, false);
+    const int n_above = dec_count(key, V, lane, t, false), n_tied = dec_count(key, V, lane, t, true) - n_above;
+    float w_tied = 0.f;
+    for (int i = lane; i < V; i += 64) w_tied = fmaxf(w_tied, key[i] == t ? wt[i] : 0.f);
+    w_tied = wave_max(w_tied);
+    int lo = 1, hi = max(n_tied, 1);                          // the smallest r in 1..n_tied with above + r w_tied >= target, else n_tied
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (fmaf((float)mid, w_tied, above) >= target) hi = mid; else lo = mid + 1;
+    }
+    dec_cut(key, wt, V, lane, t, lo, true);
+    n = n_above + lo;
+  } else {
+    for (int i = lane; i < V; i += 64) key[i] = key[i] != 0u;
+  }
+  __syncthreads();                                            // the draw reads the flags of contiguous codes: other lanes' words
+  const int k = dec_draw<true>(l, uni + (size_t)pos * B + b, key, V, inv_sigma, lane);
+  if (lane == 0) {
+    tokens[(size_t)b * L_tok + pos + 1] = k + token_offset;
+    codes[(size_t)b * n_steps + pos] = k;
+    if (kept) kept[(size_t)pos * B + b] = n;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ prompt keys / values
+// The k and v thirds of qkv [B, L, 3 H 32] (what the batched in-projection of a prompt produces) into rows 0..L-1 of the caches
+// [B, H, l_max, 32]: a thread moves 16 bytes of k and 16 of v; consecutive threads write consecutive 16 bytes of a (batch,
+// head)'s cache rows (a wave stores 1 KiB contiguous) and read 128-byte pieces of the qkv rows.  Rows >= L are not touched.
+__global__ __launch_bounds__(256) void lm_decode_prefill_kv_kernel(const float* __restrict__ qkv, float* __restrict__ kcache,
+                                                                   float* __restrict__ vcache, int L, int H, int l_max) {
+  const int t = blockIdx.x * 256 + threadIdx.x, row = t >> 3, c = t & 7;
+  if (row >= L) return;
+  const int bh = blockIdx.y, b = bh / H, h = bh % H, d = H * DEC_DH;
+  const float* src = qkv + ((size_t)b * L + row) * 3 * d + d + h * DEC_DH + 4 * c;
+  const size_t dst = ((size_t)bh * l_max + row) * DEC_DH + 4 * c;
+  const f32x4 kk = *(const f32x4*)src, vv = *(const f32x4*)(src + d);
+  *(f32x4*)(kcache + dst) = kk;
+  *(f32x4*)(vcache + dst) = vv;
 }
 
 __global__ void lm_decode_advance_kernel(int* pos_dev) {
@@ -374,6 +512,37 @@ extern "C" int smt_lm_decode_sample(const float* logits, const float* uniforms, 
   lm_decode_sample_kernel<<<(batch + 3) / 4, 256, 0, stream>>>(logits, uniforms, (long long*)tokens, (long long*)codes, batch, vocab, tok_len, n_steps,
                                                              inv_sigma, token_offset, pos, pos_dev);
   SMT_CHECK_LAUNCH("lm_decode_sample");
+  return 0;
+}
+
+extern "C" int smt_lm_decode_sample_filtered(const float* logits, const float* uniforms, int64_t* tokens, int64_t* codes, int batch,
+                                             int vocab, int tok_len, int n_steps, float inv_sigma, int token_offset, int top_k,
+                                             float top_p, int32_t* kept, int pos, const int* pos_dev, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(logits && uniforms && tokens && codes, "smt_lm_decode_sample_filtered: null pointer");
+  SMT_CHECK_ARG(batch >= 1 && batch <= 32 && vocab >= 1 && n_steps >= 1 && tok_len >= 2,
+                "smt_lm_decode_sample_filtered: batch must be 1..32, vocab and n_steps positive");
+  SMT_CHECK_ARG(vocab <= DEC_VMAX, "smt_lm_decode_sample_filtered: vocab %d above the cap of %d", vocab, DEC_VMAX);
+  SMT_CHECK_ARG(inv_sigma > 0.f, "smt_lm_decode_sample_filtered: 1 / sigma must be positive");
+  SMT_CHECK_ARG(top_k >= 0, "smt_lm_decode_sample_filtered: top_k must be >= 0 (0 = off; got %d)", top_k);
+  SMT_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "smt_lm_decode_sample_filtered: top_p must lie in (0, 1] (1 = off; got %g)", (double)top_p);
+  SMT_CHECK_ARG(pos_dev || (pos >= 0 && pos < n_steps && pos + 1 < tok_len),
+                "smt_lm_decode_sample_filtered: pos %d outside the uniforms (%d rows) or the token buffer (%d)", pos, n_steps, tok_len);
+  lm_decode_sample_filtered_kernel<<<batch, 64, 0, stream>>>(logits, uniforms, (long long*)tokens, (long long*)codes, kept, batch, vocab, tok_len,
+                                                             n_steps, inv_sigma, token_offset, top_k, top_p, pos, pos_dev);
+  SMT_CHECK_LAUNCH("lm_decode_sample_filtered");
+  return 0;
+}
+
+extern "C" int smt_lm_decode_prefill_kv(const float* qkv, float* k_cache, float* v_cache, int batch, int len, int heads, int l_max,
+                                        smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(qkv && k_cache && v_cache, "smt_lm_decode_prefill_kv: null pointer");
+  SMT_CHECK_ARG(batch >= 1 && batch <= 32 && heads >= 1 && l_max >= 1, "smt_lm_decode_prefill_kv: batch must be 1..32, heads and l_max positive");
+  SMT_CHECK_ARG((long long)batch * heads <= 65535 && (long long)l_max * DEC_DH < (1ll << 31), "smt_lm_decode_prefill_kv: batch * heads <= 65535, l_max * 32 < 2^31");
+  SMT_CHECK_ARG(len >= 1 && len <= l_max, "smt_lm_decode_prefill_kv: len %d outside 1..l_max = %d", len, l_max);
+  lm_decode_prefill_kv_kernel<<<dim3((len * 8 + 255) / 256, batch * heads), 256, 0, stream>>>(qkv, k_cache, v_cache, len, heads, l_max);
+  SMT_CHECK_LAUNCH("lm_decode_prefill_kv");
   return 0;
 }
 

@@ -75,6 +75,22 @@ class _EncoderLayer(nn.Module):
         return K.add_layer_norm(x, f, self.norm2.weight, self.norm2.bias, self.norm2.eps, K.Drop(p, tr, seed, site0 + 3, kd),
                                 h_bias=self.linear2.bias)
 
+    def prefill(self, x, k_cache, v_cache, last):
+        """Eval-mode `forward` over a prompt x [B, P, d] (causal, no lengths, no dropout) that also writes the P key / value
+        rows into the decoding cache; the last layer stops there (nothing reads its output: the next decoding step attends
+        to the cache only) and returns None."""
+        sa = self.self_attn
+        qkv = F.linear(x, sa.in_proj_weight, sa.in_proj_bias)
+        K.decode_prefill_kv(qkv, k_cache, v_cache)
+        if last:
+            return None
+        ctx = K.attention(qkv, None, sa.num_heads, True)
+        a = F.linear(ctx, sa.out_proj.weight)
+        x = K.add_layer_norm(x, a, self.norm1.weight, self.norm1.bias, self.norm1.eps, h_bias=sa.out_proj.bias)
+        f = K.bias_relu_dropout_(F.linear(x, self.linear1.weight), self.linear1.bias)
+        f = F.linear(f, self.linear2.weight)
+        return K.add_layer_norm(x, f, self.norm2.weight, self.norm2.bias, self.norm2.eps, h_bias=self.linear2.bias)
+
 
 class _Encoder(nn.Module):
     """``layers`` + final ``norm`` as in nn.TransformerEncoder, which deep-copies ONE initialised layer: every layer
@@ -225,10 +241,51 @@ class TransformerLM(TokenToWaveformModel):
         K.decode_layer_norm(st.h, None, None, norm.weight, norm.bias, norm.eps, st.h1, st.stats)
         K.decode_linear(st.h1, self.classifier.weight, self.classifier.bias, st.logits)
 
-    def _decode_step(self, st, sigma):
+    def _decode_step(self, st, sigma, top_k=None, top_p=None):
         self._decode_logits(st)
-        K.decode_sample(st.logits, st.uniforms, st.tokens, st.codes, sigma, 0, st.pos_dev, TransformerLM.OFFSET)
+        if top_k is None and top_p is None:
+            K.decode_sample(st.logits, st.uniforms, st.tokens, st.codes, sigma, 0, st.pos_dev, TransformerLM.OFFSET)
+        else:
+            K.decode_sample_filtered(st.logits, st.uniforms, st.tokens, st.codes, sigma, top_k, top_p, st.kept, 0, st.pos_dev,
+                                     TransformerLM.OFFSET)
         st.advance()
+
+    def _check_prompt(self, codes, batch):
+        """codes int64 [B, P] or [P] (broadcast over the batch), values in [0, vocab), P >= 1 -> [B, P]."""
+        vocab = self.classifier.out_features
+        if not torch.is_tensor(codes) or codes.dtype != torch.int64 or codes.dim() not in (1, 2):
+            raise ValueError("prompt: an int64 tensor of codes, [batch, P] or [P]")
+        if codes.dim() == 1:
+            codes = codes[None, :].expand(batch, -1)
+        if codes.shape[0] != batch or codes.shape[1] < 1:
+            raise ValueError(f"prompt: shape [{batch}, P >= 1] or [P] expected (got {tuple(codes.shape)})")
+        if int(codes.min()) < 0 or int(codes.max()) >= vocab:
+            raise ValueError(f"prompt: codes must lie in [0, {vocab}) (no special-token offset)")
+        return codes
+
+    @torch.no_grad()
+    def prefill(self, state, codes):
+        """Hand a prompt of P codes (int64 [B, P] or [P], values in [0, vocab), the same length for every row) to a fresh
+        decoding state in ONE batched pass: tokens[:, 1:P + 1] = codes + OFFSET, codes[:, :P] = codes, and tokens 0..P-1
+        (<bos> and the first P - 1 codes) go through the kernels of `logits` in eval mode, every layer's keys and values
+        landing in cache rows 0..P-1.  The last layer stops after its in-projection; the final norm and the classifier do
+        not run.  Leaves the state at position P: the next `step_logits` / decoding step processes tokens[:, P], the last
+        prompt code, and yields the logits of the first new code."""
+        if self.training:
+            raise ValueError("prefill: incremental decoding runs in eval mode (no dropout)")
+        if state.pos != 0:
+            raise ValueError(f"prefill: needs a state at position 0 (it is at {state.pos})")
+        codes = self._check_prompt(codes, state.batch).to(state.tokens.device)
+        p = codes.shape[1]
+        if p > state.n_steps:
+            raise ValueError(f"prefill: the state holds {state.n_steps + 1} tokens, <bos> and {p} prompt codes do not fit")
+        state.tokens[:, 1:p + 1] = codes + TransformerLM.OFFSET
+        state.codes[:, :p] = codes
+        h = K.embed(state.tokens[:, :p].contiguous(), self.embedding.weight, self.pos_encoding.table(), K.NO_DROP, TransformerLM.PAD)
+        layers = self.transformer.layers
+        for i, layer in enumerate(layers):
+            h = layer.prefill(h, state.kv[i, 0], state.kv[i, 1], i + 1 == len(layers))
+        state.prefill_done(p)
 
     @torch.no_grad()
     def step_logits(self, state):
@@ -242,7 +299,7 @@ class TransformerLM(TokenToWaveformModel):
         self._decode_logits(state)
         return state.logits.clone()
 
-    def _sample_causal(self, batch_size, n_steps, device, sigma, uniforms, generator, graph):
+    def _sample_causal(self, batch_size, n_steps, device, sigma, uniforms, generator, graph, prompt=None, top_k=None, top_p=None):
         if self.training:
             raise ValueError("sample(causal=True) runs in eval mode (no dropout)")
         if not sigma > 0:
@@ -251,6 +308,16 @@ class TransformerLM(TokenToWaveformModel):
             raise ValueError(f"sample(causal=True) runs batches of 1..32 (got {batch_size})")
         if n_steps < 1 or n_steps + 1 > self.pos_encoding.pe.shape[0]:
             raise ValueError(f"n_steps must be in 1..max_len - 1 = {self.pos_encoding.pe.shape[0] - 1} (got {n_steps})")
+        if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= self.classifier.out_features):
+            raise ValueError(f"top_k must be an int in 1..vocab = {self.classifier.out_features} (got {top_k!r})")
+        if top_p is not None and not 0.0 < top_p <= 1.0:
+            raise ValueError(f"top_p must lie in (0, 1] (got {top_p!r})")
+        n_prompt = 0
+        if prompt is not None:
+            prompt = self._check_prompt(prompt, batch_size)
+            n_prompt = prompt.shape[1]
+            if n_prompt + n_steps + 1 > self.pos_encoding.pe.shape[0]:
+                raise ValueError(f"prompt ({n_prompt}) + n_steps ({n_steps}) + 1 exceeds max_len = {self.pos_encoding.pe.shape[0]}")
         if uniforms is None:
             uniforms = torch.rand(n_steps, batch_size, generator=generator, device=device if generator is None else generator.device)
         else:
@@ -260,23 +327,28 @@ class TransformerLM(TokenToWaveformModel):
                 raise ValueError(f"uniforms must be a float32 tensor of shape ({n_steps}, {batch_size})")
             if not bool(((uniforms >= 0) & (uniforms < 1)).all()):
                 raise ValueError("uniforms must lie in [0, 1)")
-        st = self.new_decode_state(batch_size, n_steps, device, uniforms)
+        if n_prompt:                                            # position t draws with row t: the caller's rows follow the prompt's
+            uniforms = torch.cat([torch.zeros(n_prompt, batch_size, dtype=torch.float32, device=device), uniforms.to(device)])
+        st = self.new_decode_state(batch_size, n_prompt + n_steps, device, uniforms)
+        if n_prompt:
+            self.prefill(st, prompt)                            # eager, before any capture: the step below holds DecodeState buffers only
         eager = min(2, n_steps) if graph else n_steps           # a graphed run warms up with its first two steps
         for _ in range(eager):
-            self._decode_step(st, sigma)
+            self._decode_step(st, sigma, top_k, top_p)
         if n_steps > eager:
             step = torch.cuda.CUDAGraph()
             with torch.cuda.graph(step):                        # one linear chain of launches on the capture stream
-                self._decode_step(st, sigma)
+                self._decode_step(st, sigma, top_k, top_p)
             for _ in range(n_steps - eager):
                 step.replay()
-            st.pos = n_steps                                    # the host mirror of what the replays did on the device
+            st.pos = n_prompt + n_steps                         # the host mirror of what the replays did on the device
             torch.cuda.current_stream().synchronize()           # after the loop: the graph must outlive its last replay
         q = st.codes
         return self.reconstruct(q, torch.ones_like(q).unsqueeze(1)), q
 
     @torch.no_grad()
-    def sample(self, batch_size, n_steps, device="cuda", sigma=1.0, *, causal=False, uniforms=None, generator=None, graph=False):
+    def sample(self, batch_size, n_steps, device="cuda", sigma=1.0, *, causal=False, uniforms=None, generator=None, graph=False,
+               prompt=None, top_k=None, top_p=None):
         """Ancestral sampling (transformer_lm.py:137-155).  As in the reference every step re-runs the whole prefix WITHOUT
         the causal mask (mask=None there), so a key/value cache cannot reproduce it; the step is one pass of `logits`.
 
@@ -284,11 +356,16 @@ class TransformerLM(TokenToWaveformModel):
         step is ONE new token against a key/value cache (csrc/lm_decode.hip) and the loop never synchronises with the host.
         The draws are inverse-CDF with `uniforms` [n_steps, batch_size] in [0, 1) (float32; drawn with torch.rand from
         `generator` or the global one when not given); graph=True replays one captured step instead of issuing the launches.
+        `prompt` (int64 codes [batch_size, P] or [P], no special-token offset) is continued instead of starting at <bos>: it
+        goes through `prefill` in one batched pass, P + n_steps + 1 <= max_len, and the returned codes [batch_size, P + n_steps]
+        and audio hold the prompt followed by the n_steps new codes.  `top_k` (1..vocab) keeps the top_k most likely codes,
+        `top_p` (0 < top_p <= 1) the shortest most-likely-first prefix of them that holds top_p of their mass; the draw is
+        from the kept codes, renormalised (smt_lm_decode_sample_filtered in include/smt_hip.h has the exact rule).
         Returns (audio, codes) like the other path."""
         if causal:
-            return self._sample_causal(batch_size, n_steps, device, sigma, uniforms, generator, graph)
-        if uniforms is not None or generator is not None or graph:
-            raise ValueError("uniforms, generator and graph belong to sample(causal=True)")
+            return self._sample_causal(batch_size, n_steps, device, sigma, uniforms, generator, graph, prompt, top_k, top_p)
+        if uniforms is not None or generator is not None or graph or prompt is not None or top_k is not None or top_p is not None:
+            raise ValueError("uniforms, generator, graph, prompt, top_k and top_p belong to sample(causal=True)")
         assert sigma > 0, "Temperature scalar must be positive"
         q = torch.full((batch_size, 1), TransformerLM.BOS, dtype=torch.long, device=device)
         for _ in range(n_steps):

@@ -1,7 +1,12 @@
 """Ancestral samples from a trained TransformerLM (reference scripts/sample_from_lm.py).
 
     python -m scripts.sample_from_lm --log_dir ./logs/transformer_lm --ckpt_num 5000 --dump_dir ./outputs \
-        --n_samples 4 --n_steps 512 [--sigma 1.0] [--causal [--graph] [--seed 0]]
+        --n_samples 4 --n_steps 512 [--sigma 1.0] [--causal [--graph] [--seed 0] [--top_k 32] [--top_p 0.95] \
+        [--prompt_file ./data/VQ-Latent/val/00000.pkl --prompt_len 64]]
+
+With a prompt (the first ``--prompt_len`` codes of a VQ-Latent utterance file, the same for every sample) the model continues
+it: audio and ``tokens.txt`` hold the prompt followed by the ``--n_steps`` new codes.  ``--causal`` runs ``--n_samples`` in
+chunks of at most 32, the batch limit of the decoding kernels.
 
 Writes ``<dump_dir>/<ModelClass>@<ckpt>/sample_<i>.wav``, ``mel_spectrograms.png`` and ``tokens.txt`` like the reference.
 The sampling loop, the dequantisation and the VQ-VAE decoder run on MI355X through libsmt_hip.so (`TransformerLM.sample`);
@@ -32,7 +37,22 @@ def parse_args(argv=None):
     p.add_argument("--causal", action="store_true", help="Sample with the causal mask the model was trained with (key/value cache)")
     p.add_argument("--graph", action="store_true", help="With --causal: replay one captured decoding step")
     p.add_argument("--seed", type=int, default=None, help="With --causal: seed of the generator the uniforms are drawn from")
+    p.add_argument("--top_k", type=int, default=None, help="With --causal: draw from the top_k most likely codes only")
+    p.add_argument("--top_p", type=float, default=None, help="With --causal: draw from the smallest set of most likely codes holding top_p of the mass")
+    p.add_argument("--prompt_file", type=str, default=None, help="With --causal: VQ-Latent utterance file (.pkl) whose codes are continued")
+    p.add_argument("--prompt_len", type=int, default=None, help="With --prompt_file: number of leading codes used as the prompt")
     return p.parse_args(argv)
+
+
+def load_prompt(path, length):
+    """The first `length` codes (field "q") of a VQ-Latent utterance file as an int64 tensor [length]."""
+    from datasets.vqlatent import load_plain_pickle
+    q = load_plain_pickle(path)["q"]
+    if length is None:
+        length = len(q)
+    if not 1 <= length <= len(q):
+        raise ValueError(f"--prompt_len must be in 1..{len(q)}, the number of codes in {path} (got {length})")
+    return torch.tensor(q[:length], dtype=torch.int64)
 
 
 def mel_grid(spects):
@@ -68,12 +88,17 @@ def main(argv=None):
     os.makedirs(dump_dir, exist_ok=True)
 
     if args.causal:
+        if args.prompt_len is not None and args.prompt_file is None:
+            raise ValueError("--prompt_len belongs to --prompt_file")
+        prompt = None if args.prompt_file is None else load_prompt(args.prompt_file, args.prompt_len).to(device)
         generator = None if args.seed is None else torch.Generator(device=device).manual_seed(args.seed)
-        x_samples, q_samples = model.sample(batch_size=args.n_samples, n_steps=args.n_steps, device=device, sigma=args.sigma,
-                                            causal=True, generator=generator, graph=args.graph)
+        chunks = [model.sample(batch_size=min(32, args.n_samples - i), n_steps=args.n_steps, device=device, sigma=args.sigma, causal=True,
+                               generator=generator, graph=args.graph, prompt=prompt, top_k=args.top_k, top_p=args.top_p)
+                  for i in range(0, max(args.n_samples, 1), 32)]       # the decoding kernels take batches of 1..32
+        x_samples, q_samples = (chunks[0] if len(chunks) == 1 else tuple(torch.cat(t) for t in zip(*chunks)))
     else:
-        if args.graph or args.seed is not None:
-            raise ValueError("--graph and --seed belong to --causal")
+        if args.graph or args.seed is not None or any(v is not None for v in (args.top_k, args.top_p, args.prompt_file, args.prompt_len)):
+            raise ValueError("--graph, --seed, --top_k, --top_p, --prompt_file and --prompt_len belong to --causal")
         x_samples, q_samples = model.sample(batch_size=args.n_samples, n_steps=args.n_steps, device=device, sigma=args.sigma)
     logger.info("Generated token samples")
 

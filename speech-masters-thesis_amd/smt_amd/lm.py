@@ -304,6 +304,33 @@ def decode_sample(logits, uniforms, tokens, codes, sigma=1.0, pos=0, pos_dev=Non
                                          1.0 / sigma, token_offset, p, pd, N.stream_ptr()), "smt_lm_decode_sample")
 
 
+def decode_sample_filtered(logits, uniforms, tokens, codes, sigma=1.0, top_k=None, top_p=None, kept=None, pos=0, pos_dev=None,
+                           token_offset=2):
+    """`decode_sample` over the top-k / nucleus prefix of the codes ordered by logit (descending, ties by index): the first
+    min(top_k, vocab) codes are the candidates, of which the shortest prefix holding top_p of THEIR mass is kept (None = off);
+    kept [n_steps, batch] int32 (optional) gets the size of the kept set at row pos.  Both off: the codes of `decode_sample`."""
+    b, v = logits.shape
+    n_steps = uniforms.shape[0]
+    assert uniforms.shape == (n_steps, b) and uniforms.dtype == torch.float32 and tokens.shape[0] == b and codes.shape == (b, n_steps)
+    assert tokens.dtype == codes.dtype == torch.int64
+    assert kept is None or (kept.shape == (n_steps, b) and kept.dtype == torch.int32 and kept.is_cuda and kept.is_contiguous())
+    p, pd = _pos_args(pos, pos_dev)
+    N.check(N.lib().smt_lm_decode_sample_filtered(N.ptr(_f32(logits)), N.ptr(uniforms), N.ptr(tokens), N.ptr(codes), b, v, tokens.shape[1],
+                                                  n_steps, 1.0 / sigma, token_offset, 0 if top_k is None else int(top_k),
+                                                  1.0 if top_p is None else float(top_p), N.ptr(kept), p, pd, N.stream_ptr()),
+            "smt_lm_decode_sample_filtered")
+
+
+def decode_prefill_kv(qkv, k_cache, v_cache):
+    """The k and v thirds of qkv [batch, len, 3 * heads * 32] (the batched in-projection of a prompt) into rows 0..len-1 of
+    k_cache / v_cache [batch, heads, l_max, 32]; rows from len on are left alone."""
+    b, h, l_max, dh = k_cache.shape
+    assert dh == 32 and v_cache.shape == k_cache.shape and qkv.dim() == 3 and qkv.shape[0] == b and qkv.shape[2] == 3 * h * 32
+    assert k_cache.dtype == v_cache.dtype == torch.float32 and k_cache.is_contiguous() and v_cache.is_contiguous()
+    N.check(N.lib().smt_lm_decode_prefill_kv(N.ptr(_f32(qkv)), N.ptr(k_cache), N.ptr(v_cache), b, qkv.shape[1], h, l_max, N.stream_ptr()),
+            "smt_lm_decode_prefill_kv")
+
+
 def decode_advance(pos_dev):
     """pos_dev += 1 on the device."""
     assert pos_dev.is_cuda and pos_dev.dtype == torch.int32 and pos_dev.numel() == 1
@@ -321,7 +348,8 @@ def decode_layer_norm(x, h, h_bias, gamma, beta, eps, out, stats):
 class DecodeState:
     """Every buffer of an incremental decoding loop (TransformerLM.sample(causal=True) / step_logits): the key/value cache
     [layers, 2, batch, heads, l_max, 32], the token [batch, n_steps + 1] and code [batch, n_steps] buffers, the position
-    (``pos_dev`` on the device, mirrored by ``pos`` on the host), the uniforms [n_steps, batch] and the activations of one step.
+    (``pos_dev`` on the device, mirrored by ``pos`` on the host), the uniforms [n_steps, batch], the kept-set sizes of the
+    filtered sampler [n_steps, batch] int32 and the activations of one step.
     Nothing here comes from the grow-only workspace of smt_amd.native: captured launches keep pointing at these tensors."""
 
     def __init__(self, batch, n_steps, dim, heads, dim_ff, vocab, layers, device, first_token=1, uniforms=None):
@@ -336,6 +364,7 @@ class DecodeState:
         self.pos = 0
         self.uniforms = torch.zeros(n_steps, batch, **f32) if uniforms is None else uniforms.to(**f32).contiguous()
         assert self.uniforms.shape == (n_steps, batch)
+        self.kept = torch.zeros(n_steps, batch, device=device, dtype=torch.int32)
         self.h, self.h1, self.ctx, self.a = (torch.empty(batch, dim, **f32) for _ in range(4))
         self.qkv = torch.empty(batch, 3 * dim, **f32)
         self.f = torch.empty(batch, dim_ff, **f32)
@@ -347,6 +376,14 @@ class DecodeState:
         """pos += 1, on the device and in the host mirror."""
         decode_advance(self.pos_dev)
         self.pos += 1
+
+    def prefill_done(self, n):
+        """The position after a prefill of n prompt tokens (their keys / values are in cache rows 0..n-1): pos = n on the
+        device and in the host mirror, so the next step processes tokens[:, n]."""
+        if self.pos != 0 or not 1 <= n <= self.n_steps:
+            raise ValueError(f"DecodeState.prefill_done: needs a state at position 0 and 1 <= n <= {self.n_steps} (pos {self.pos}, n {n})")
+        self.pos_dev.fill_(n)
+        self.pos = n
 
     def push(self, tokens):
         """Force the next token (teacher forcing): tokens [batch] int64 -> tokens[:, pos + 1], then advance."""

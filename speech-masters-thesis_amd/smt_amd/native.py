@@ -9,7 +9,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SMT_HIP_LIB: an alternative build of the same ABI (tools/ablate_*.sh link their -D ablation builds to libsmt_hip_abl.so)
 LIB_PATH = os.environ.get("SMT_HIP_LIB") or os.path.join(_HERE, "libsmt_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _lib = None
 _lock = threading.Lock()
@@ -108,6 +108,9 @@ _SIGNATURES = {
     "smt_lm_decode_attention_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "smt_lm_decode_attention": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "smt_lm_decode_sample": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_f32, c_int, c_int, c_ptr, c_ptr]),
+    "smt_lm_decode_sample_filtered": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_f32, c_int, c_int, c_f32, c_ptr,
+                                              c_int, c_ptr, c_ptr]),
+    "smt_lm_decode_prefill_kv": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "smt_lm_decode_advance": (c_int, [c_ptr, c_ptr]),
     "smt_glow_reduce_workspace_bytes": (c_size, [c_i64, c_int]),
     "smt_glow_actnorm_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),

@@ -11,7 +11,9 @@ around calls that end in a device synchronise; one warm-up call, `--iters` timed
 per second.  For the cached paths also the bytes a step cannot avoid -- the 12 layers' projection weights, the classifier
 weight, and the keys and values of the positions so far, 2 * layers * batch * d * 4 * (t + 1), averaged over t -- and what
 fraction of the copy rate this project quotes for the device (0.79 of 8 TB/s) moving that floor in the measured step time comes to.
-A second table times the two streaming kernels alone.  Prints the tables and one JSON line.
+A second table times the two streaming kernels alone.  A third compares handing over a prompt of P codes by `prefill` (one
+batched pass, keys / values copied into the cache) with P `push`es (one decoding step per prompt token), a fourth the graphed
+`sample` and the sampler launch alone with and without the top-k / top-p filter.  Prints the tables and one JSON line.
 
     python tools/bench_lm_sample.py [--iters 3] [--full_iters 2] [--batches 4 32] [--steps 256 1024]
 """
@@ -101,6 +103,78 @@ def kernel_table(model, batches, l_max=1024, reps=20):
     return rows
 
 
+def prefill_table(model, batches, prompts=(64, 256), iters=5):
+    """`prefill` of P codes against P steps of `_decode_logits` + `push` (what `step_logits` / `push` issue), host clock around
+    calls that end in a device synchronise; the state is made once and rewound between calls."""
+    rows = []
+    vocab = model.classifier.out_features
+    print(f"{'batch':>5} {'prompt':>6} {'prefill ms':>11} {'pushes ms':>10} {'ratio':>7}")
+    for b in batches:
+        for p in prompts:
+            codes = torch.randint(0, vocab, (b, p), generator=torch.Generator().manual_seed(p + b)).cuda()
+            st = model.new_decode_state(b, p + 1, "cuda")
+
+            def rewind():
+                st.pos = 0
+                st.pos_dev.zero_()
+
+            def by_prefill():
+                rewind()
+                model.prefill(st, codes)
+
+            def by_pushes():
+                rewind()
+                for t in range(p):
+                    model._decode_logits(st)
+                    st.push(codes[:, t] + model.OFFSET)
+
+            t_pre, t_push = statistics.median(timed(by_prefill, iters)), statistics.median(timed(by_pushes, iters))
+            rows.append({"batch": b, "prompt": p, "prefill_s": t_pre, "pushes_s": t_push})
+            print(f"{b:>5} {p:>6} {t_pre * 1e3:11.3f} {t_push * 1e3:10.3f} {t_push / t_pre:7.1f}", flush=True)
+    return rows
+
+
+def filter_table(model, batches, n_steps=256, iters=3, reps=20, launches=50):
+    """Graphed `sample` of n_steps codes, and `launches` sampler launches captured as one graph (HIP events over `reps` replays),
+    without a filter and with top_k = 64, top_p = 0.95 and both."""
+    from smt_amd import lm as K
+    rows = []
+    filters = [("none", None, None), ("top_k 64", 64, None), ("top_p 0.95", None, 0.95), ("top_k 64, top_p 0.95", 64, 0.95)]
+    print(f"{'batch':>5} {'filter':>22} {'us/step (graphed)':>18} {'us/sampler launch':>18}")
+    for b in batches:
+        u = torch.rand(n_steps, b, generator=torch.Generator().manual_seed(b)).cuda()
+        st = model.new_decode_state(b, n_steps, "cuda", u)
+        st.logits.normal_()
+        for name, top_k, top_p in filters:
+            ts = timed(lambda: model.sample(b, n_steps, "cuda", causal=True, uniforms=u, graph=True, top_k=top_k, top_p=top_p), iters)
+
+            def draw():
+                for _ in range(launches):
+                    if top_k is None and top_p is None:
+                        K.decode_sample(st.logits, st.uniforms, st.tokens, st.codes, 1.0, pos=0)
+                    else:
+                        K.decode_sample_filtered(st.logits, st.uniforms, st.tokens, st.codes, 1.0, top_k, top_p, st.kept, pos=0)
+
+            draw()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                draw()
+            graph.replay()
+            torch.cuda.synchronize()
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(reps):
+                graph.replay()
+            end.record()
+            torch.cuda.synchronize()
+            t_launch = start.elapsed_time(end) * 1e-3 / (reps * launches)
+            rows.append({"batch": b, "filter": name, "n_steps": n_steps, "us_per_step": statistics.median(ts) / n_steps * 1e6,
+                         "sampler_us": t_launch * 1e6})
+            print(f"{b:>5} {name:>22} {rows[-1]['us_per_step']:18.1f} {rows[-1]['sampler_us']:18.2f}", flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=3)
@@ -136,8 +210,10 @@ def main():
                       f"{floor:>9} {frac:>12}", flush=True)
     with torch.no_grad():
         kernels = kernel_table(model, args.batches)
+        prefill = prefill_table(model, args.batches)
+        filtered = filter_table(model, args.batches)
     print(json.dumps({"tool": "bench_lm_sample", "config": "transformer_lm.yaml (12 x d512 h16 ff2048, vocab 512), random init",
-                      "copy_rate_bytes_per_s": COPY_RATE, "runs": runs, "kernels": kernels}))
+                      "copy_rate_bytes_per_s": COPY_RATE, "runs": runs, "kernels": kernels, "prefill": prefill, "filtered": filtered}))
 
 
 if __name__ == "__main__":
