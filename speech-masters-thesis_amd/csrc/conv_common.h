@@ -45,6 +45,19 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(unsigned, v);
 }
 
+typedef short s16x2v __attribute__((ext_vector_type(2)));
+typedef unsigned short u16x2v __attribute__((ext_vector_type(2)));
+// relu on a packed bf16 pair: a negative bf16 is a negative int16 (v_pk_max_i16)
+__device__ __forceinline__ unsigned pk_relu_bf16(unsigned w) {
+  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2v, w), s16x2v{0, 0}));
+}
+// 0xFFFF per 16-bit half of h that is >= thr (thr_m1 = thr - 1 in both halves, thr >= 1): saturating subtract, min 1, negate
+__device__ __forceinline__ unsigned pk_keep_mask(unsigned h, unsigned thr_m1) {
+  u16x2v d = __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2v, h), __builtin_bit_cast(u16x2v, thr_m1));
+  d = __builtin_elementwise_min(d, u16x2v{1, 1});
+  return __builtin_bit_cast(unsigned, (u16x2v)(u16x2v{0, 0} - d));
+}
+
 // tanh for the gate (resnet.py:233): 1 - 2 / (exp(2x) + 1) on the hardware exp2 / rcp -- 5 instructions instead of the
 // ~40 of tanhf; absolute error <= 2e-7 (the gate's output is O(1) and is stored in bf16 on the fast path), exact limits
 // +-1 at +-inf.  Every gate kernel (forward, fused forward, backward) uses this one function, so they stay consistent.
@@ -70,6 +83,34 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t ws_rsrc(const void* base, long
 __device__ __forceinline__ void ws_dma16(__amdgpu_buffer_rsrc_t rs, unsigned voff, void* lds_wave_base) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_wave_base, 16, (int)voff, 0, 0, 0);
 }
+// Persistent workgroups: every workgroup takes a contiguous run of tiles_per_wg tiles, and the runs of workgroups b, b + 8, ..
+// (one XCD, one L2) are adjacent -- neighbouring tiles share their halo rows and the weights in L2.  False: no tile left.
+__device__ __forceinline__ bool wg_tile_run(int ntiles, int tiles_per_wg, int& wg, int& tile_begin, int& tile_end) {
+  const int nwg = gridDim.x;
+  wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
+  tile_begin = wg * tiles_per_wg;
+  tile_end = min(ntiles, tile_begin + tiles_per_wg);
+  return tile_begin < tile_end;
+}
+
+// Output of a TRANSPOSED 32 x 32 MFMA tile (A = weights, B = rows), packed to bf16 pairs v[2g + h] = channels 8g + 4hh + 2h, +1:
+// lanes r and r + 32 hold channels {0-3, 8-11, 16-19, 24-27} and {4-7, 12-15, 20-23, 28-31} of the same row: swap so that
+// lane r owns 0-7 | 16-23 and lane r + 32 owns 8-15 | 24-31 (16-byte pieces) ...
+__device__ __forceinline__ void pair_up8(unsigned (&v)[8]) {
+#pragma unroll
+  for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      auto sw = __builtin_amdgcn_permlane32_swap(v[4 * h2 + d], v[4 * h2 + 2 + d], false, false);
+      v[4 * h2 + d] = sw[0]; v[4 * h2 + 2 + d] = sw[1];
+    }
+}
+// ... and store them straight from registers: vo = byte offset of this lane's first piece (row, channel 8 hh of the tile)
+__device__ __forceinline__ void store_paired(const unsigned (&v)[8], __amdgpu_buffer_rsrc_t rs, unsigned vo) {
+  __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)v[0], (int)v[1], (int)v[2], (int)v[3]}, rs, (int)vo, 0, 0);
+  __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)v[4], (int)v[5], (int)v[6], (int)v[7]}, rs, (int)(vo + 32u), 0, 0);
+}
+
 // The same instruction as inline asm, for loops that own their vmcnt waits: the compiler tracks LDS-DMA builtins and puts a
 // wait for every DMA in flight in front of the first LDS intrinsic it cannot disambiguate (ds_read_b64_tr_b16: measured in
 // conv1x1_bwd, a vmcnt wait for the NEXT tile's prefetch in the middle of the current tile) and answers the first use of
@@ -152,6 +193,38 @@ __device__ __forceinline__ int scalar_load_i32(const int* ptr) {
                                                         // come from v_readfirstlane (VALU-written SGPR read by a memory instruction)
   return v;
 }
+
+// ---- arguments of the smt_conv1d_ntc kernels (conv.hip, conv_ws.hip) ---------------------------------------------------
+struct ConvArgs {
+  const void* x; const void* w; const float* bias; void* y; const void* res; const void* gate_h; void* y_act;
+  const int* lens_in; const int* lens_out;
+  long long x_bs, y_bs, res_bs, gh_bs, ya_bs;  // batch strides (elements)
+  int ldx, ldy, ldr, ldgh, ldya;               // row pitches (elements)
+  int B, Tin, Tout, Cin, Cout;          // Tout = output rows PER LAUNCH INDEX t (before os/oo)
+  int taps, stride, dil, pad;
+  int out_stride, out_offset, Ty;       // output row = t*out_stride + out_offset, Ty rows in y per batch
+  int act_out, epi_act;                 // relu+dropout of the OUTPUT (second store) / its derivative as epilogue
+  unsigned drop_keys[8]; int site_width; unsigned drop_thresh16; float drop_scale;
+  const unsigned* drop_keys_dev; int drop_keys_dev_stride;   // keys in device memory (graph replay): override drop_keys
+  int tiles_per_batch;
+  int rs;   // row stride of the dilation-class decomposition (LDS-DMA kernel), 1 = off
+  const void* x2; const void* w2; const float* bias2; const int* lens_in2; long long x2_bs; int ldx2;   // folded second 1x1 term (conv1x1_fold)
+  int dbg;  // ablation switches (SMT_CONV_DBG): 1 no A loads, 2 no W loads, 4 no MFMA, 8 no stores
+};
+
+// dropout key of site s of this launch: by value, or from device memory when the caller keeps its keys there
+__device__ __forceinline__ unsigned site_key(const ConvArgs& p, int site) {
+  return p.drop_keys_dev ? p.drop_keys_dev[(site & 7) * p.drop_keys_dev_stride] : p.drop_keys[site & 7];
+}
+
+// ---- the weight-stationary family (conv_ws.hip) as conv.hip's dispatch sees it -----------------------------------------
+struct WsPlan { int buf_bytes; size_t lds; int tiles_per_wg; dim3 grid; };
+// Plan the weight-stationary launch of p (dilation classes already applied: p.rs, p.dil, p.pad), or say that p is not
+// eligible.  On success p.tiles_per_batch is set.
+bool plan_conv_ws(ConvArgs& p, WsPlan& pl);
+void launch_conv_ws(const ConvArgs& p, const WsPlan& pl, const void* zero_page, hipStream_t stream);
+// the name smt_conv1d_kernel_name reports for the variant that launch_conv_ws picks for p
+const char* conv_ws_variant_name(const ConvArgs& p);
 
 // Tiles a persistent workgroup of the fused backward kernels takes at least (SMT_FUSED_MIN_TPW): every workgroup leaves a
 // partial weight-gradient slab that the reduce kernel reads back, so at the small levels of the model fewer, longer

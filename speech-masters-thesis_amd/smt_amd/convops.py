@@ -426,7 +426,7 @@ def _tag(desc):
 
 
 def _kernel_of(desc):
-    """Which kernel smt_conv1d_ntc dispatches to (asked of the library: one dispatch rule, csrc/conv.hip)."""
+    """Which kernel smt_conv1d_ntc dispatches to (asked of the library: one dispatch rule, csrc/conv.hip and csrc/conv_ws.hip)."""
     return N.lib().smt_conv1d_kernel_name(ctypes.byref(desc)).decode()
 
 

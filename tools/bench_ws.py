@@ -2,7 +2,10 @@
 launches them: forward = activated output only (relu + counter dropout), data gradient = activation-gradient mask + residual;
 operands are 128-channel slices of 512-channel tensors (row pitch 1 KiB).  T = rows per batch item (default: the top level).
 
-    python tools/bench_ws.py            # SMT_CONV_NO_WS2=1 / SMT_CONV_NO_PIPE=1 select the older kernels for A/B runs
+    python tools/bench_ws.py
+
+A/B runs against the older kernels (SMT_CONV_NO_WS2=1, SMT_CONV_NO_PIPE=1) need the -DSMT_WS_AB=1 build of csrc/conv_ws.hip:
+tools/ablate_ws.sh builds it and runs this file three times.
 """
 import os, sys, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
