@@ -1039,11 +1039,6 @@ static bool conv_dma_eligible(const smt_conv_desc* d) {
 }
 
 // Plan of the LDS-DMA family for one conv: dilation classes, then weight-stationary / 256-row / 128-row tiles.
-// rows a dilation class must have for the decomposition to pay (tile quantisation wastes ceil(Tc/128)*128 - Tc rows)
-static int class_min_rows() {
-  static const int v = getenv("SMT_CLASS_MIN_ROWS") ? atoi(getenv("SMT_CLASS_MIN_ROWS")) : 128;
-  return v;
-}
 struct DmaPlan { bool ws; WsPlan wsp; bool big; size_t lds; dim3 grid; };
 static bool plan_conv_dma(ConvArgs& p, DmaPlan& pl) {
   // Dilation classes (see conv_gemm_dma_kernel) for same-size convs whose padding is a multiple of a large

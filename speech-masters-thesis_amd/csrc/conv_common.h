@@ -234,12 +234,17 @@ inline int fused_min_tpw() {
   return v;
 }
 
+// Rows a dilation class must have for the class decomposition to pay (SMT_CLASS_MIN_ROWS): tile quantisation wastes
+// ceil(Tc/128)*128 - Tc rows per class.  Read by the forward / data-gradient plan (conv.hip) and the shift weight gradient.
+inline int class_min_rows() {
+  static const int v = [] { const char* e = getenv("SMT_CLASS_MIN_ROWS"); return e ? atoi(e) : 128; }();
+  return v;
+}
+
 // Fixed-order reduction of weight-gradient partial slabs (conv_wgrad.hip): slab[chunk][blk = co/64 * nblk_ci + ci/cib]
 // [plane = tap | bias][64 co][cib ci] -> dw[co*so + ci*si + jmap[tap]*sj], db[co] (column 0 of the bias plane).
 int launch_wgrad_reduce(const float* slab, float* dw, float* db, int n_chunks, int nblk_co, int nblk_ci, int taps,
                         int c_in, int c_out, int cib, long long so, long long si, long long sj, const int* jmap,
-                        hipStream_t stream, int bias_cols = 1,    // bias_cols > 1: db = sum of columns 0, 32, .. of the bias plane
-                        int vsplit = 0);                          // vsplit > 0: slab column ci = channel ci % vsplit of tap ci / vsplit
-
+                        hipStream_t stream, int bias_cols = 1);   // bias_cols > 1: db = sum of columns 0, 32, .. of the bias plane
 
 }  // namespace smt

@@ -29,9 +29,6 @@ struct WgradArgs {
   int B, Tin, Tout, Ty, Cin, Cout;
   int taps, stride, dil, pad, out_stride, out_offset;
   int rows_per_chunk, chunks_per_batch, nblk_ci, nblk_co, with_bias;
-  int rs;   // dilation-class row stride (LDS-DMA kernel), 1 = off
-  int win, xstride;   // window mode (LDS-DMA kernel): the Cin "channels" of output row t are the 64-channel rows
-                      // xstride t - pad, xstride t - pad + 1, .. of x side by side (Cin / 64 taps of a 64-channel conv)
 };
 
 // R = rows per staged tile; CIB = input channels per workgroup (CIB/32 wave columns, 2 wave rows);
@@ -47,17 +44,32 @@ template <> struct WTr<float> {
   static constexpr int pitch(int ch) { return ch + 4; }
 };
 
-// transposed fragment: element e of lane (n = lane&31, hh = lane>>5) = tile[row0 + 8*hh + e][col0 + n]
-__device__ __forceinline__ bf16x8 frag_tr_bf16(const __bf16* tile, int pitch, int row0, int col0, int lane) {
-  const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-  const int hh = g >> 1;
-  const __bf16* a0 = tile + (row0 + 8 * hh + q) * pitch + col0 + 16 * (g & 1) + 4 * pp;
-  const __bf16* a1 = a0 + 4 * pitch;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a1);
+// Transposed fragments (ds_read_b64_tr_b16): element e of lane (n = lane&31, hh = lane>>5) is tile[row + 8*hh + e][col + n].
+// A lane addresses row tr_lane_row, column tr_lane_col of the 16 x 32 block and reads twice, four rows apart.
+__device__ __forceinline__ int tr_lane_row(int lane) { return 8 * (lane >> 5) + ((lane & 15) >> 2); }
+__device__ __forceinline__ int tr_lane_col(int lane) { return 16 * ((lane >> 4) & 1) + 4 * (lane & 3); }
+__device__ __forceinline__ bf16x8 tr_read2(const void* a0, int step4_bytes) {
+  const unsigned char* a = reinterpret_cast<const unsigned char*>(a0);
+  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
+  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + step4_bytes));
   typedef short s16x8 __attribute__((ext_vector_type(8)));
   s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8, v);
+}
+__device__ __forceinline__ bf16x8 frag_tr_bf16(const __bf16* tile, int pitch, int row0, int col0, int lane) {
+  return tr_read2(tile + (row0 + tr_lane_row(lane)) * pitch + col0 + tr_lane_col(lane), 4 * pitch * 2);
+}
+
+// Workgroup -> (global chunk index cgl, block blk of the nblk 64 x CIB blocks of dw).  XCD-aware order: the blocks of one row
+// chunk run back to back on the same XCD (ids == mod 8), so the second reader of a chunk's rows hits L2.
+struct WgBlock { int nblk, blk, cgl; };
+__device__ __forceinline__ WgBlock wgrad_block(int nblk_ci, int nblk_co) {
+  WgBlock w;
+  w.nblk = nblk_ci * nblk_co;
+  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+  w.blk = q % w.nblk;
+  w.cgl = (q / w.nblk) * 8 + xcd;
+  return w;
 }
 
 // NT = accumulator planes (taps + bias plane); CIB = input channels per workgroup; STRIDED = stride > 1
@@ -74,16 +86,11 @@ __global__ __launch_bounds__(CIB * 4) void conv_wgrad_kernel(WgradArgs p) {
   const int wm = wave / WNC, wn = wave % WNC;
   const int r = lane & 31, hh = lane >> 5;
 
-  // XCD-aware order: the co-blocks of one row chunk run back to back on the same XCD (ids == mod 8),
-  // so the second reader of a chunk's rows hits L2
-  const int nblk = p.nblk_ci * p.nblk_co;
-  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-  const int blk = q % nblk;
-  const int cgl = (q / nblk) * 8 + xcd;          // global chunk index
-  if (cgl >= p.B * p.chunks_per_batch) return;
-  const int co0 = (blk / p.nblk_ci) * CB, ci0 = (blk % p.nblk_ci) * CIB;
-  const int b = cgl / p.chunks_per_batch;
-  const int chunk = cgl % p.chunks_per_batch;
+  const WgBlock w = wgrad_block(p.nblk_ci, p.nblk_co);
+  if (w.cgl >= p.B * p.chunks_per_batch) return;
+  const int co0 = (w.blk / p.nblk_ci) * CB, ci0 = (w.blk % p.nblk_ci) * CIB;
+  const int b = w.cgl / p.chunks_per_batch;
+  const int chunk = w.cgl % p.chunks_per_batch;
   const int t_begin = chunk * p.rows_per_chunk;
   const int t_end = min(p.Tout, t_begin + p.rows_per_chunk);
 
@@ -198,9 +205,9 @@ __global__ __launch_bounds__(CIB * 4) void conv_wgrad_kernel(WgradArgs p) {
       }
     }
   }
-  // partial block -> slab[chunk_global][plane][co 64][ci 64] for this (co,ci) block
+  // partial block -> slab[chunk_global][blk][plane][co 64][ci CIB]
   const int planes = ntaps + 1;   // slab layout always carries the bias plane (zeros when not requested)
-  float* out = p.slab + ((size_t)cgl * nblk + blk) * (size_t)planes * CB * CIB;
+  float* out = p.slab + ((size_t)w.cgl * w.nblk + w.blk) * (size_t)planes * CB * CIB;
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     if (j >= planes) break;
@@ -215,38 +222,19 @@ __global__ __launch_bounds__(CIB * 4) void conv_wgrad_kernel(WgradArgs p) {
 
 // ------------------------------------------------------------------------------------------------
 // LDS-DMA variant (bf16, stride 1, C_in % 128 == 0, C_out % 64 == 0): the dy / x row tiles go
-// HBM/L2 -> LDS with global_load_lds_dwordx4 into a DOUBLE buffer (tile i+1 lands while tile i is
+// HBM/L2 -> LDS with buffer_load ... lds into a DOUBLE buffer (tile i+1 lands while tile i is
 // multiplied), rows unpadded.  The transposed reads stay conflict-free through an XOR swizzle of the
 // 16-byte chunk index, applied on the source address while staging:
 //   x  rows (256 B): chunk ^ ((row & 3) << 2)        dy rows (128 B): chunk ^ (((row >> 1) & 1) << 2)
 // (a 32-lane half of ds_read_b64_tr_b16 touches 4 rows x 64 B; the swizzles put those on 4 distinct
 // 64-byte slots of the 256-byte bank row).
-__device__ __forceinline__ void wg_dma16(const void* gsrc, void* lds_dst_wave_base) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)gsrc,
-                                   (void __attribute__((address_space(3)))*)lds_dst_wave_base, 16, 0, 0);
-}
-
-// element e of lane (n = lane&31, hh = lane>>5) = tile[row0 + 8*hh + e][col0 + n], rows of ROWB bytes, swizzled
-template <int ROWB, bool IS_X>
-__device__ __forceinline__ bf16x8 frag_tr_swz(const unsigned char* tile, int row0, int col0, int lane) {
-  const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-  const int hh = g >> 1;
-  const int col = col0 + 16 * (g & 1) + 4 * pp;
-  const int chunk = col >> 3, within = (col & 7) * 2;
-  const int ra = row0 + 8 * hh + q, rb = ra + 4;
-  const int fa = IS_X ? ((ra & 3) << 2) : (((ra >> 1) & 1) << 2);
-  const int fb = IS_X ? ((rb & 3) << 2) : (((rb >> 1) & 1) << 2);
-  const unsigned char* a0 = tile + ra * ROWB + ((chunk ^ fa) << 4) + within;
-  const unsigned char* a1 = tile + rb * ROWB + ((chunk ^ fb) << 4) + within;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a1);
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
+__device__ __forceinline__ int swz_dy(int row) { return ((row >> 1) & 1) << 2; }
+__device__ __forceinline__ int swz_x(int row) { return (row & 3) << 2; }
+// byte offset of bf16 column `col` of a swizzled row (swz = swz_dy / swz_x of that row)
+__device__ __forceinline__ int swz_col_bytes(int col, int swz) { return (((col >> 3) ^ swz) << 4) + (col & 7) * 2; }
 
 template <int NT>
-__global__ __launch_bounds__(512) void conv_wgrad_dma_kernel(WgradArgs p, const __bf16* __restrict__ zero_page) {
+__global__ __launch_bounds__(512) void conv_wgrad_dma_kernel(WgradArgs p) {
   typedef __bf16 T;
   constexpr int R = 128, CB = 64, CIB = 128, WNC = 4, NTHR = 512;
   constexpr int DYB = CB * 2, XB = CIB * 2;         // row bytes
@@ -256,30 +244,20 @@ __global__ __launch_bounds__(512) void conv_wgrad_dma_kernel(WgradArgs p, const 
   const int wm = wave / WNC, wn = wave % WNC;
   const int r = lane & 31, hh = lane >> 5;
 
-  const int nblk = p.nblk_ci * p.nblk_co;
-  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-  const int blk = q % nblk;
-  const int cgl = (q / nblk) * 8 + xcd;
-  if (cgl >= p.B * p.rs * p.chunks_per_batch) return;
-  const int co0 = (blk / p.nblk_ci) * CB, ci0 = (blk % p.nblk_ci) * CIB;
-  // dilation classes (see conv_gemm_dma_kernel): rs > 1 runs the dilated conv as rs dense convs over the
-  // row classes t = cls (mod rs); a "batch item" here is one (batch, class) pair
-  const int rs = p.rs;
-  const int bb = cgl / p.chunks_per_batch;
-  const int b = bb / rs, cls = bb - b * rs;
-  const int chunk = cgl % p.chunks_per_batch;
-  const int Tc = (p.Tout - cls + rs - 1) / rs;
+  const WgBlock w = wgrad_block(p.nblk_ci, p.nblk_co);
+  if (w.cgl >= p.B * p.chunks_per_batch) return;
+  const int co0 = (w.blk / p.nblk_ci) * CB, ci0 = (w.blk % p.nblk_ci) * CIB;
+  const int b = w.cgl / p.chunks_per_batch;
+  const int chunk = w.cgl % p.chunks_per_batch;
   const int t_begin = chunk * p.rows_per_chunk;
-  const int t_end = min(Tc, t_begin + p.rows_per_chunk);
+  const int t_end = min(p.Tout, t_begin + p.rows_per_chunk);
 
   const int rows_x = (R - 1) + (p.taps - 1) * p.dil + 1;
   const int rows_x_pad = (rows_x + 3) & ~3;
   const size_t buf_bytes = (size_t)DY_BYTES + (size_t)rows_x_pad * XB;
-  const T* xg = reinterpret_cast<const T*>(p.x) + (long long)b * p.x_bs + (long long)cls * p.ldx;
-  const T* dyg = reinterpret_cast<const T*>(p.dy) + (long long)b * p.dy_bs + (long long)cls * p.ldy;
-  const long long ldx = (long long)p.ldx * rs, ldy = (long long)p.ldy * rs;
-  const int len_full = p.lens_in ? min(p.lens_in[b], p.Tin) : p.Tin;
-  const int len_in = max(0, (len_full - cls + rs - 1) / rs);
+  const T* xg = reinterpret_cast<const T*>(p.x) + (long long)b * p.x_bs;
+  const T* dyg = reinterpret_cast<const T*>(p.dy) + (long long)b * p.dy_bs;
+  const int len_in = max(0, p.lens_in ? min(p.lens_in[b], p.Tin) : p.Tin);
   const bool bias_plane = p.with_bias && (ci0 == 0);
   const int ntaps = p.taps;
 
@@ -289,31 +267,29 @@ __global__ __launch_bounds__(512) void conv_wgrad_dma_kernel(WgradArgs p, const 
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
-  // Round 3: untracked LDS-DMA through range-checked V#s (conv_common.h): the compiler used to put a wait for the NEXT tile's
-  // prefetch in front of the first transposed read of the current tile, so nothing overlapped (it mattered little while the
-  // kernel only ran 5- and 9-tap layers with 40+ MFMAs per tile; in window mode a tile is 8-16 MFMAs).  An offset of ~0 is
-  // out of range of any descriptor: such lanes read zero (rows past the chunk, before the item, past the valid length).
-  const UntrackedRsrc rdy = untracked_rsrc(dyg + co0, 0, (unsigned)min((long long)0xfffffff0ll, (long long)Tc * ldy * 2));
-  const UntrackedRsrc rxx = untracked_rsrc(xg + (p.win ? 0 : ci0), 0, (unsigned)min((long long)0xfffffff0ll, (long long)len_in * ldx * 2));
-  const unsigned pdy = (unsigned)(ldy * 2), pxx = (unsigned)(ldx * 2);
+  // Untracked LDS-DMA through range-checked V#s (conv_common.h): the compiler used to put a wait for the NEXT tile's
+  // prefetch in front of the first transposed read of the current tile, so nothing overlapped.  An offset of ~0 is out of
+  // range of any descriptor: such lanes read zero (rows past the chunk, before the item, past the valid length).
+  const UntrackedRsrc rdy = untracked_rsrc(dyg + co0, 0, (unsigned)min((long long)0xfffffff0ll, (long long)p.Tout * p.ldy * 2));
+  const UntrackedRsrc rxx = untracked_rsrc(xg + ci0, 0, (unsigned)min((long long)0xfffffff0ll, (long long)len_in * p.ldx * 2));
+  const unsigned pdy = (unsigned)(p.ldy * 2), pxx = (unsigned)(p.ldx * 2);
   auto stage = [&](int t0, int buf) {
     unsigned char* base = smem + (size_t)buf * buf_bytes;
     // dy: 128 rows x 8 chunks; one wave-instruction = 8 rows
     for (int g = wave; g < R / 8; g += NTHR / 64) {
       const int row = 8 * g + (lane >> 3), pos = lane & 7;
       const int t = t0 + row;
-      const int ch = pos ^ (((row >> 1) & 1) << 2);
+      const int ch = pos ^ swz_dy(row);
       untracked_dma16(rdy, t < t_end ? (unsigned)t * pdy + (unsigned)(ch << 4) : 0xffffff00u, base + g * 1024);
     }
     // x: rows_x_pad rows x 16 chunks; one wave-instruction = 4 rows
     const int tin0 = t0 - p.pad;
     for (int g = wave; g < rows_x_pad / 4; g += NTHR / 64) {
       const int row = 4 * g + (lane >> 4), pos = lane & 15;
-      const int ch = pos ^ ((row & 3) << 2);
-      int tin = tin0 + row, cch = ch;                     // input row and 16-byte chunk inside the 128-channel block
-      if (p.win) { cch = (ci0 >> 3) + ch; tin = p.xstride * (t0 + row) - p.pad + (cch >> 3); cch &= 7; }
+      const int ch = pos ^ swz_x(row);
+      const int tin = tin0 + row;
       const bool ok = (row < rows_x) && (tin >= 0) && (tin < len_in);
-      untracked_dma16(rxx, ok ? (unsigned)tin * pxx + (unsigned)(cch << 4) : 0xffffff00u, base + DY_BYTES + g * 1024);
+      untracked_dma16(rxx, ok ? (unsigned)tin * pxx + (unsigned)(ch << 4) : 0xffffff00u, base + DY_BYTES + g * 1024);
     }
   };
 
@@ -324,63 +300,43 @@ __global__ __launch_bounds__(512) void conv_wgrad_dma_kernel(WgradArgs p, const 
   // Per-lane fragment offsets, computed ONCE: the k-step advances rows by 16 (a multiple of 4), so the
   // swizzle term of a lane depends only on the tap.  Inside the loop every transposed read is then
   // "base + lane offset + compile-time immediate" -- no address arithmetic between the MFMAs.
-  const int tg = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3, thh = tg >> 1;
-  const int coly = wm * 32 + 16 * (tg & 1) + 4 * tp, colx = wn * 32 + 16 * (tg & 1) + 4 * tp;
-  const int lrow = 8 * thh + tq;
-  const int dyoff = lrow * DYB + (((coly >> 3) ^ (((lrow >> 1) & 1) << 2)) << 4) + (coly & 7) * 2;
+  const int lrow = tr_lane_row(lane);
+  const int coly = wm * 32 + tr_lane_col(lane), colx = wn * 32 + tr_lane_col(lane);
+  const int dyoff = lrow * DYB + swz_col_bytes(coly, swz_dy(lrow));
   int xoff[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     const int rj = lrow + j * p.dil;
-    xoff[j] = rj * XB + (((colx >> 3) ^ ((rj & 3) << 2)) << 4) + (colx & 7) * 2;
+    xoff[j] = rj * XB + swz_col_bytes(colx, swz_x(rj));
   }
-  auto tr2 = [&](const unsigned char* base, int imm, int step4) -> bf16x8 {
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + imm));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + imm + step4));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-  };
 
-  // Window mode runs THREE stage buffers (3 x 48 KiB): a tile is 8-16 MFMAs per wave, far shorter than the 2-3 us a tile takes
-  // to arrive, so one tile of prefetch leaves the kernel waiting on latency (measured: 176 us per launch = 36 tiles x 2.5 us x
-  // two rounds of workgroups).  Its DMA count per wave and tile is a constant (2 dy + 4 x pieces), so the counted wait can leave
-  // the newest tile in flight.  The other modes keep two buffers (their tile size varies with taps and dilation).
-  constexpr int WIN_NDMA = (R / 8 + R / 4) / (NTHR / 64);   // DMA instructions per wave and tile in window mode (taps = 1)
-  const int nbuf = p.win ? 3 : 2;
   stage(t_begin, 0);
-  if (p.win && t_begin + R < t_end) { stage(t_begin + R, 1); vm_wait<WIN_NDMA>(); }
-  else vm_wait<0>();
-  int it = 0;
-  for (int t0 = t_begin; t0 < t_end; t0 += R, ++it) {
-    const int buf = it % nbuf;
+  vm_wait<0>();
+  int buf = 0;
+  for (int t0 = t_begin; t0 < t_end; t0 += R, buf ^= 1) {
     lgkm_wait<0>();
-    __builtin_amdgcn_s_barrier();          // tile `it` has landed for every wave (each waited at the end of the previous
+    __builtin_amdgcn_s_barrier();          // this tile has landed for every wave (each waited at the end of the previous
                                            // iteration); the buffer read in the previous iteration is free
-    const int ahead = nbuf - 1;
-    const bool more = t0 + ahead * R < t_end;
-    if (more) stage(t0 + ahead * R, (it + ahead) % nbuf);
+    if (t0 + R < t_end) stage(t0 + R, buf ^ 1);
     const unsigned char* dyt = smem + (size_t)buf * buf_bytes + dyoff;
     const unsigned char* xbase = smem + (size_t)buf * buf_bytes + DY_BYTES;
 #pragma unroll
     for (int k0 = 0; k0 < R; k0 += 16) {
-      const bf16x8 a = tr2(dyt, k0 * DYB, 4 * DYB);
+      const bf16x8 a = tr_read2(dyt + k0 * DYB, 4 * DYB);
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         if (j < ntaps) {
-          const bf16x8 bfrag = tr2(xbase + xoff[j], k0 * XB, 4 * XB);
+          const bf16x8 bfrag = tr_read2(xbase + xoff[j] + k0 * XB, 4 * XB);
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bfrag, acc[j], 0, 0, 0);
         } else if (j == ntaps && bias_plane) {
           acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, acc[j], 0, 0, 0);
         }
       }
     }
-    __builtin_amdgcn_sched_barrier(0);
-    // the next tile must have landed; in window mode the one after it may still be in flight
-    vm_wait_or_drain<WIN_NDMA>(p.win && more);
+    step_end_wait<0>();                    // the next tile must have landed
   }
   const int planes = ntaps + 1;
-  float* out = p.slab + ((size_t)cgl * nblk + blk) * (size_t)planes * CB * CIB;
+  float* out = p.slab + ((size_t)w.cgl * w.nblk + w.blk) * (size_t)planes * CB * CIB;
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     if (j >= planes) break;
@@ -424,14 +380,11 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
   const int wm = wave / WNC, wn = wave % WNC;
   const int r = lane & 31, hh = lane >> 5;
 
-  const int nblk = p.nblk_ci * p.nblk_co;
-  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-  const int blk = q % nblk;
-  const int cgl = (q / nblk) * 8 + xcd;
-  if (cgl >= p.n_chunks) return;
-  const int co0 = (blk / p.nblk_ci) * CB, ci0 = (blk % p.nblk_ci) * CIB;
+  const WgBlock w = wgrad_block(p.nblk_ci, p.nblk_co);
+  if (w.cgl >= p.n_chunks) return;
+  const int co0 = (w.blk / p.nblk_ci) * CB, ci0 = (w.blk % p.nblk_ci) * CIB;
   const int ntiles = p.tiles_per_item * p.B * p.rs;
-  const int tile_begin = cgl * p.tiles_per_wg;
+  const int tile_begin = w.cgl * p.tiles_per_wg;
   const int tile_end = min(ntiles, tile_begin + p.tiles_per_wg);
   const int rs = p.rs;
   const bool bias_plane = p.with_bias && (ci0 == 0);
@@ -458,8 +411,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
     for (int g = wave; g < SH_R / 8; g += NTHR / 64) {
       const int row = 8 * g + (lane >> 3), pos = lane & 7;
       const int t = t0 + row;
-      const int ch = pos ^ (((row >> 1) & 1) << 2);
-      wg_dma16((t < Tc) ? dyg + (long long)t * ldy + ch * 8 : zero_page + pos * 8, base + g * 1024);
+      const int ch = pos ^ swz_dy(row);
+      lds_dma16((t < Tc) ? dyg + (long long)t * ldy + ch * 8 : zero_page + pos * 8, base + g * 1024);
     }
     // x: 136 rows x 16 chunks; one wave-instruction = 4 rows
     const int tin0 = t0 - p.pad;
@@ -467,8 +420,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
       const int row = 4 * g + (lane >> 4), pos = lane & 15;
       const int tin = tin0 + row;
       const bool ok = (row < SH_R + NTAPS - 1) && (tin >= 0) && (tin < len_in);
-      const int ch = pos ^ ((row & 3) << 2);
-      wg_dma16(ok ? xg + (long long)tin * ldx + ch * 8 : zero_page + pos * 8, base + SH_DY + g * 1024);
+      const int ch = pos ^ swz_x(row);
+      lds_dma16(ok ? xg + (long long)tin * ldx + ch * 8 : zero_page + pos * 8, base + SH_DY + g * 1024);
     }
   };
 
@@ -477,6 +430,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
   for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
 
   // per-lane fragment offsets: the k-step advances rows by 16, which keeps both swizzle terms
+  // (written out: through tr_lane_row / swz_col_bytes the compiler schedules this kernel differently)
   const int tg = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3, thh = tg >> 1;
   const int coly = wm * 32 + 16 * (tg & 1) + 4 * tp, colx = wn * 32 + 16 * (tg & 1) + 4 * tp;
   const int lrow = 8 * thh + tq;
@@ -538,7 +492,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
       if (bias_plane && (k0 & 3) == wn) acc[NTAPS] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, acc[NTAPS], 0, 0, 0);
     }
   }
-  float* out = p.slab + ((size_t)cgl * nblk + blk) * (size_t)PLANES * CB * CIB;
+  float* out = p.slab + ((size_t)w.cgl * w.nblk + w.blk) * (size_t)PLANES * CB * CIB;
 #pragma unroll
   for (int j = 0; j < PLANES; ++j)
 #pragma unroll
@@ -557,8 +511,7 @@ static bool wgrad_shift_plan(const smt_conv_desc* d, ShiftPlan* pl) {
     return false;
   int rs = 1, pad = d->padding;
   if (d->dilation > 1) {
-    static const int min_rows = getenv("SMT_CLASS_MIN_ROWS") ? atoi(getenv("SMT_CLASS_MIN_ROWS")) : 128;
-    if (d->padding % d->dilation != 0 || d->t_out / d->dilation < min_rows) return false;
+    if (d->padding % d->dilation != 0 || d->t_out / d->dilation < class_min_rows()) return false;
     rs = d->dilation; pad = d->padding / d->dilation;
   }
   if (pad < 0 || pad > d->taps - 1) return false;
@@ -579,13 +532,6 @@ static bool wgrad_shift_plan(const smt_conv_desc* d, ShiftPlan* pl) {
   return true;
 }
 
-template <int NTAPS>
-static void launch_shift(const ShiftArgs& a, const void* zero_page, dim3 grid, hipStream_t stream) {
-  (void)hipFuncSetAttribute((const void*)conv_wgrad_shift_kernel<NTAPS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024);
-  conv_wgrad_shift_kernel<NTAPS><<<grid, 512, 2 * SH_STAGE, stream>>>(a, (const __bf16*)zero_page);
-}
-
 // ---- fixed-order reduction of the partial slabs -------------------------------------------------------------------
 // One job = one weight (+ bias) gradient: slab[chunk][blk][plane][64 co][cib ci] -> dw (torch layout), db.  Jobs travel BY
 // VALUE in the kernel arguments (no table upload, capturable in a hipGraph); up to WR_MAXJ jobs share one launch, so a
@@ -594,7 +540,6 @@ struct WreduceJob {
   const float* slab; float* dw; float* db;
   long long so, si, sj;
   int n_chunks, nblk, nblk_ci, planes, taps, Cin, Cout, cib, bias_cols;
-  int vsplit;                      // > 0: window mode -- column ci of the slab is input channel ci % vsplit of tap ci / vsplit
   int block0;                      // first workgroup of this job inside the launch
   int wblocks;                     // workgroups of the weight part (the bias part follows)
   signed char jmap[16];
@@ -645,8 +590,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(WreduceBatch bt)
       f32x4 t = part[0][o];
 #pragma unroll
       for (int k = 1; k < 4; ++k) t += part[k][o];
-      float* dst = p.vsplit > 0 ? p.dw + co * p.so + (ci % p.vsplit) * p.si + p.jmap[ci / p.vsplit] * p.sj
-                                : p.dw + co * p.so + ci * p.si + p.jmap[plane] * p.sj;
+      float* dst = p.dw + co * p.so + ci * p.si + p.jmap[plane] * p.sj;
       dst[0] = t[0]; dst[p.si] = t[1]; dst[2 * p.si] = t[2]; dst[3 * p.si] = t[3];
     }
   } else {
@@ -677,42 +621,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(WreduceBatch bt)
   }
 }
 
-// input channels per workgroup: 128 (8 waves, two per SIMD) while the accumulator planes fit in the
-// 256-register budget of that occupancy, else 64 (4 waves, one per SIMD, 512 registers)
-static int wgrad_cib(const smt_conv_desc* d) {
-  if (d->dtype != SMT_BF16) return 64;
-  return (d->c_in > 64 && d->stride == 1) ? 128 : 64;
-}
-
-// dilation-class decomposition applies to the LDS-DMA variant only (bf16, 128-channel blocks, stride 1)
-static int wgrad_rs(const smt_conv_desc* d) {
-  const bool dma_shape = d->dtype == SMT_BF16 && d->stride == 1 && d->c_in % 128 == 0 && d->c_out % 64 == 0 &&
-                         d->out_stride == 1 && d->out_offset == 0 && d->zero_page != nullptr;
-  // Measured: for the weight gradient the strided class rows cost more than the smaller halo saves
-  // (2.04 vs 1.79 ms at k = 9, dilation 27, T/2 level), so the decomposition stays switched off here.
-  constexpr bool kUseClasses = false;
-  return (kUseClasses && dma_shape && d->dilation >= 8 && d->taps > 1 && d->padding % d->dilation == 0 &&
-          d->t_in == d->t_out) ? d->dilation : 1;
-}
-
-static void wgrad_plan(const smt_conv_desc* d, int* rows_per_chunk, int* chunks_per_batch, int* nblk_co,
-                       int* nblk_ci, int* planes) {
-  const int cib = wgrad_cib(d);
-  const int rs = wgrad_rs(d);
-  *nblk_co = (d->c_out + 63) / 64;
-  *nblk_ci = (d->c_in + cib - 1) / cib;
-  const int R = d->dtype == SMT_BF16 ? 128 : 64;
-  const long long tc = (d->t_out + rs - 1) / rs;                 // rows per (batch, class) item
-  long long total_rows = (long long)d->batch * rs * tc;
-  long long target_wgs = 512;   // two rounds of one workgroup per CU: keeps the partial slabs small
-  long long rows = (total_rows * (*nblk_co) * (*nblk_ci) + target_wgs - 1) / target_wgs;
-  rows = std::max<long long>(R, (rows + R - 1) / R * R);
-  rows = std::min<long long>(rows, (tc + R - 1) / R * R);
-  *rows_per_chunk = (int)rows;
-  *chunks_per_batch = (int)((tc + rows - 1) / rows);
-  *planes = d->taps + 1;
-}
-
 static thread_local bool g_reduce_defer = false;
 static thread_local WreduceBatch g_reduce_batch = {0, 0, {}};
 
@@ -728,7 +636,7 @@ static int reduce_flush(hipStream_t stream) {
 
 int launch_wgrad_reduce(const float* slab, float* dw, float* db, int n_chunks, int nblk_co, int nblk_ci, int taps,
                         int c_in, int c_out, int cib, long long so, long long si, long long sj, const int* jmap,
-                        hipStream_t stream, int bias_cols, int vsplit) {
+                        hipStream_t stream, int bias_cols) {
   SMT_CHECK_ARG(c_in % 4 == 0 && cib % 4 == 0 && taps <= 16, "conv_wgrad_reduce: c_in and the ci block must be multiples of 4");
   if (g_reduce_batch.n_jobs == WR_MAXJ) {
     int rc = reduce_flush(stream);
@@ -736,13 +644,11 @@ int launch_wgrad_reduce(const float* slab, float* dw, float* db, int n_chunks, i
   }
   WreduceJob& r = g_reduce_batch.job[g_reduce_batch.n_jobs];
   r.bias_cols = bias_cols;
-  r.vsplit = vsplit;
   r.slab = slab; r.dw = dw; r.db = db;
   r.n_chunks = n_chunks; r.nblk = nblk_co * nblk_ci; r.nblk_ci = nblk_ci; r.planes = taps + 1; r.taps = taps;
   r.Cin = c_in; r.Cout = c_out; r.cib = cib;
   r.so = so; r.si = si; r.sj = sj;
-  const int n_map = vsplit > 0 ? c_in / vsplit : taps;      // window mode: one entry per real tap
-  for (int t = 0; t < 16; ++t) r.jmap[t] = (signed char)(t < n_map ? jmap[t] : 0);
+  for (int t = 0; t < 16; ++t) r.jmap[t] = (signed char)(t < taps ? jmap[t] : 0);
   const long long total4 = (long long)taps * c_out * (c_in / 4);
   r.wblocks = (int)((total4 + 63) / 64);
   r.block0 = g_reduce_batch.total_blocks;
@@ -763,187 +669,122 @@ extern "C" int smt_wgrad_reduce_defer(int on, smt_stream_t stream_) {
   return on ? 0 : reduce_flush((hipStream_t)stream_);
 }
 
-static bool wgrad_window_desc(const smt_conv_desc* d, smt_conv_desc* v);
+// ---- the plan: which kernel runs for a descriptor, with what launch geometry, over how much workspace -----------------
+// smt_conv1d_wgrad launches what the plan says, smt_conv1d_wgrad_kernel_name and _workspace_bytes report it.
+//
+// Shift: all taps in one launch (conv_wgrad_shift_kernel).  Otherwise tap groups: more than 5 taps would need more
+// accumulator registers than two waves per SIMD allow, so wide kernels are processed as consecutive groups of <= 5 taps (a
+// group of taps j0.. is the same convolution with padding reduced by j0*dilation), each on the LDS-DMA or the generic kernel.
+constexpr int WG_GROUP = 5, WG_MAX_TAPS = 16, WG_MAX_GROUPS = (WG_MAX_TAPS + WG_GROUP - 1) / WG_GROUP;
+constexpr size_t WG_MAX_LDS = 160 * 1024;
+enum WgradVariant { WG_GENERIC, WG_DMA, WG_SHIFT };
+static const char* const kWgradName[] = {"conv_wgrad", "conv_wgrad_dma", "conv_wgrad_shift"};
 
-static size_t wgrad_group_ws(const smt_conv_desc* d) {
-  int rpc, cpb, nco, nci, planes;
-  wgrad_plan(d, &rpc, &cpb, &nco, &nci, &planes);
-  return (size_t)d->batch * wgrad_rs(d) * cpb * nco * nci * planes * 64 * wgrad_cib(d) * sizeof(float);
+struct WgradLaunch {
+  WgradVariant variant;
+  int j0, taps, pad;                     // tap group (shift: all taps) and its left padding
+  int cib;                               // input channels per workgroup = slab block width
+  int rows_per_chunk, chunks_per_batch;  // generic / LDS-DMA chunking (shift: see ShiftPlan)
+  int n_chunks, nblk_co, nblk_ci;        // partial slabs and their (co, ci) blocks
+  unsigned grid; size_t lds;
+  size_t ws_off, ws_bytes;               // this launch's region of the workspace (256-byte aligned)
+};
+struct WgradPlan {
+  int n; WgradLaunch l[WG_MAX_GROUPS];   // launches in order; the first one names the conv
+  ShiftPlan sh;                          // valid when l[0].variant == WG_SHIFT
+  size_t ws_bytes;
+};
+
+static unsigned wgrad_grid(const WgradLaunch& l) { return (unsigned)(8 * ((l.n_chunks + 7) / 8) * l.nblk_co * l.nblk_ci); }
+static size_t wgrad_slab_bytes(const WgradLaunch& l) {
+  return (size_t)l.n_chunks * l.nblk_co * l.nblk_ci * (l.taps + 1) * 64 * l.cib * sizeof(float);
 }
 
-// Tap groups: more than 5 taps would need more accumulator registers than two waves per SIMD allow,
-// so wide kernels are processed as consecutive groups of <= 5 taps (a group of taps j0.. is the same
-// convolution with padding reduced by j0*dilation).
-constexpr int WG_GROUP = 5;
-static smt_conv_desc wgrad_group_desc(const smt_conv_desc* d, int j0, int n) {
-  smt_conv_desc g = *d;
-  g.taps = n;
-  g.padding = d->padding - j0 * d->dilation;
-  return g;
+// one tap group on the LDS-DMA or the generic kernel
+static WgradLaunch wgrad_group_plan(const smt_conv_desc* d, int j0, int taps) {
+  WgradLaunch l = {};
+  const bool bf = d->dtype == SMT_BF16;
+  l.j0 = j0; l.taps = taps; l.pad = d->padding - j0 * d->dilation;
+  // input channels per workgroup: 128 (8 waves, two per SIMD) while the accumulator planes fit in the 256-register
+  // budget of that occupancy, else 64 (4 waves, one per SIMD, 512 registers)
+  l.cib = (bf && d->c_in > 64 && d->stride == 1) ? 128 : 64;
+  l.nblk_co = (d->c_out + 63) / 64;
+  l.nblk_ci = (d->c_in + l.cib - 1) / l.cib;
+  const int R = bf ? 128 : 64;
+  const long long target_wgs = 512;   // two rounds of one workgroup per CU: keeps the partial slabs small
+  long long rows = ((long long)d->batch * d->t_out * l.nblk_co * l.nblk_ci + target_wgs - 1) / target_wgs;
+  rows = std::min<long long>((rows + R - 1) / R * R, ((long long)d->t_out + R - 1) / R * R);
+  rows = std::max<long long>(R, rows);
+  l.rows_per_chunk = (int)rows;
+  l.chunks_per_batch = (int)((d->t_out + rows - 1) / rows);
+  l.n_chunks = d->batch * l.chunks_per_batch;
+  l.grid = wgrad_grid(l);
+  // (dilation classes, as in conv_gemm_dma_kernel, were measured slower for these kernels: 2.04 vs 1.79 ms at k = 9, dilation 27)
+  const int rows_x = (R - 1) * d->stride + (taps - 1) * d->dilation + 1;
+  const size_t lds_dma = 2 * ((size_t)128 * 128 + (size_t)((rows_x + 3) & ~3) * 256);
+  const bool dma = bf && l.cib == 128 && d->zero_page && d->c_in % 128 == 0 && d->c_out % 64 == 0 && d->out_stride == 1 &&
+                   d->out_offset == 0 && lds_dma <= WG_MAX_LDS;
+  l.variant = dma ? WG_DMA : WG_GENERIC;
+  l.lds = dma ? lds_dma
+        : bf  ? ((size_t)R * WTr<__bf16>::pitch(64) + (size_t)rows_x * WTr<__bf16>::pitch(l.cib)) * 2
+              : ((size_t)R * WTr<float>::pitch(64) + (size_t)rows_x * WTr<float>::pitch(l.cib)) * 4;
+  l.ws_bytes = align_up(wgrad_slab_bytes(l), 256);
+  return l;
 }
 
-extern "C" size_t smt_conv1d_wgrad_workspace_bytes(const smt_conv_desc* d) {
-  size_t best = 0;
-  ShiftPlan pl;
-  if (wgrad_shift_plan(d, &pl))
-    best = (size_t)pl.n_chunks * pl.nblk_co * pl.nblk_ci * (d->taps + 1) * 64 * 128 * sizeof(float);
-  smt_conv_desc wv;
-  if (wgrad_window_desc(d, &wv)) return std::max(best, align_up(wgrad_group_ws(&wv), 256));
-  // tap groups get consecutive regions (their reductions may be deferred: smt_wgrad_reduce_defer)
-  size_t groups = 0;
+static bool wgrad_plan(const smt_conv_desc* d, WgradPlan* pl) {
+  if (!d || d->taps < 1 || d->taps > WG_MAX_TAPS) return false;
+  size_t groups_ws = 0;
+  pl->n = 0;
   for (int j0 = 0; j0 < d->taps; j0 += WG_GROUP) {
-    smt_conv_desc g = wgrad_group_desc(d, j0, std::min(WG_GROUP, d->taps - j0));
-    groups += align_up(wgrad_group_ws(&g), 256);
+    WgradLaunch& l = pl->l[pl->n++];
+    l = wgrad_group_plan(d, j0, std::min(WG_GROUP, d->taps - j0));
+    l.ws_off = groups_ws;            // consecutive regions: the groups' reductions may be deferred (smt_wgrad_reduce_defer)
+    groups_ws += l.ws_bytes;
   }
-  return std::max(best, groups);
-}
-
-template <typename T, int CIB, bool STRIDED>
-static int launch_wgrad(const WgradArgs& a, dim3 grid, size_t lds, int planes, hipStream_t stream) {
-#define SMT_WG_CASE(NT)                                                                                  \
-  case NT:                                                                                               \
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_kernel<T, NT, CIB, STRIDED>,                       \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                   \
-    conv_wgrad_kernel<T, NT, CIB, STRIDED><<<grid, CIB * 4, lds, stream>>>(a);                           \
-    break;
-  switch (planes) {
-    SMT_WG_CASE(2) SMT_WG_CASE(3) SMT_WG_CASE(4) SMT_WG_CASE(5) SMT_WG_CASE(6)
-    default:
-      set_error("conv_wgrad: unsupported tap count %d", planes - 1);
-      return 1;
+  pl->ws_bytes = groups_ws;
+  if (wgrad_shift_plan(d, &pl->sh)) {
+    WgradLaunch l = {};
+    l.variant = WG_SHIFT; l.taps = d->taps; l.pad = pl->sh.pad; l.cib = 128;
+    l.n_chunks = pl->sh.n_chunks; l.nblk_co = pl->sh.nblk_co; l.nblk_ci = pl->sh.nblk_ci;
+    l.grid = wgrad_grid(l); l.lds = 2 * SH_STAGE;
+    l.ws_bytes = wgrad_slab_bytes(l);
+    pl->n = 1; pl->l[0] = l;
+    pl->ws_bytes = std::max(l.ws_bytes, groups_ws);   // callers size their workspace for either choice
   }
-#undef SMT_WG_CASE
-  SMT_CHECK_LAUNCH("conv_wgrad");
-  return 0;
-}
-
-static int wgrad_group(const smt_conv_desc* d, float* dweight, int64_t stride_out, int64_t stride_in,
-                       int64_t stride_tap, const int* tap_map, float* dbias, void* workspace,
-                       size_t workspace_bytes, hipStream_t stream) {
-  SMT_CHECK_ARG(d && d->x && d->y && dweight && tap_map && workspace, "smt_conv1d_wgrad: null pointer");
-  SMT_CHECK_ARG(d->dtype == SMT_BF16 || d->dtype == SMT_F32, "smt_conv1d_wgrad: bad dtype");
-  const int epv = d->dtype == SMT_BF16 ? 8 : 4;
-  SMT_CHECK_ARG(d->c_in % epv == 0 && d->c_out % epv == 0 && d->ld_x % epv == 0 && d->ld_y % epv == 0,
-                "smt_conv1d_wgrad: channels / pitches must keep 16-byte alignment");
-  SMT_CHECK_ARG(d->taps >= 1 && d->taps <= WG_GROUP, "smt_conv1d_wgrad: internal tap group too large");
-  SMT_CHECK_ARG(workspace_bytes >= wgrad_group_ws(d), "smt_conv1d_wgrad: workspace too small");
-  int rpc, cpb, nco, nci, planes;
-  wgrad_plan(d, &rpc, &cpb, &nco, &nci, &planes);
-  const int cib = wgrad_cib(d);
-  WgradArgs a;
-  a.x = d->x; a.dy = d->y; a.slab = (float*)workspace; a.lens_in = d->lens_in;
-  a.x_bs = d->bs_x; a.dy_bs = d->bs_y; a.ldx = d->ld_x; a.ldy = d->ld_y;
-  a.B = d->batch; a.Tin = d->t_in; a.Tout = d->t_out; a.Ty = d->t_y; a.Cin = d->c_in; a.Cout = d->c_out;
-  a.taps = d->taps; a.stride = d->stride; a.dil = d->dilation; a.pad = d->padding;
-  a.out_stride = d->out_stride; a.out_offset = d->out_offset;
-  a.rows_per_chunk = rpc; a.chunks_per_batch = cpb; a.nblk_ci = nci; a.nblk_co = nco; a.with_bias = dbias ? 1 : 0;
-  const int rs = wgrad_rs(d);
-  a.rs = rs; a.win = 0; a.xstride = 1;
-  if (rs > 1) { a.pad = d->padding / rs; a.dil = 1; }
-  if (d->batch > 0 && d->t_out > 0) {
-    const int n_chunks = d->batch * rs * cpb;
-    dim3 grid((unsigned)(8 * ((n_chunks + 7) / 8) * nco * nci));
-    const bool bf = d->dtype == SMT_BF16;
-    const int R = bf ? 128 : 64;
-    const int rows_x = (R - 1) * d->stride + (d->taps - 1) * a.dil + 1;
-    const size_t lds = bf ? ((size_t)R * WTr<__bf16>::pitch(64) + (size_t)rows_x * WTr<__bf16>::pitch(cib)) * 2
-                          : ((size_t)R * WTr<float>::pitch(64) + (size_t)rows_x * WTr<float>::pitch(cib)) * 4;
-    SMT_CHECK_ARG(lds <= 160 * 1024, "conv_wgrad: tile needs %zu B of LDS", lds);
-    int rc;
-    const bool strided = d->stride > 1;
-    const int rows_xp = (rows_x + 3) & ~3;
-    const size_t lds_dma = 2 * ((size_t)128 * 128 + (size_t)rows_xp * 256);
-    const bool dma = bf && cib == 128 && !strided && d->zero_page && d->c_in % 128 == 0 && d->c_out % 64 == 0 &&
-                     d->out_stride == 1 && d->out_offset == 0 && lds_dma <= 160 * 1024;
-    SMT_CHECK_ARG(rs == 1 || dma, "conv_wgrad: dilation classes need the LDS-DMA variant");
-    if (dma) {
-#define SMT_WGD_CASE(NT)                                                                                 \
-  case NT:                                                                                               \
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_dma_kernel<NT>,                                    \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                   \
-    conv_wgrad_dma_kernel<NT><<<grid, 512, lds_dma, stream>>>(a, (const __bf16*)d->zero_page);           \
-    break;
-      switch (planes) {
-        SMT_WGD_CASE(2) SMT_WGD_CASE(3) SMT_WGD_CASE(4) SMT_WGD_CASE(5) SMT_WGD_CASE(6)
-        default: set_error("conv_wgrad_dma: unsupported tap count"); return 1;
-      }
-#undef SMT_WGD_CASE
-      SMT_CHECK_LAUNCH("conv_wgrad_dma");
-      rc = 0;
-    } else
-    if (bf && cib == 128) rc = launch_wgrad<__bf16, 128, false>(a, grid, lds, planes, stream);
-    else if (bf) rc = strided ? launch_wgrad<__bf16, 64, true>(a, grid, lds, planes, stream)
-                              : launch_wgrad<__bf16, 64, false>(a, grid, lds, planes, stream);
-    else rc = strided ? launch_wgrad<float, 64, true>(a, grid, lds, planes, stream)
-                      : launch_wgrad<float, 64, false>(a, grid, lds, planes, stream);
-    if (rc) return rc;
-  }
-  const int n_chunks = (d->batch == 0 || d->t_out == 0) ? 0 : d->batch * rs * cpb;
-  return launch_wgrad_reduce((const float*)workspace, dweight, dbias, n_chunks, nco, nci, d->taps, d->c_in, d->c_out,
-                             cib, stride_out, stride_in, stride_tap, tap_map, stream);
-}
-
-// Window mode of the LDS-DMA kernel (round 3): the weight gradients of the k = 4 / stride-2 resampling convs of a
-// 64-channel level and of the two-tap phases of their transposes.  dW[co][ci][j] = sum_t dy[t][co] x[s t - pad + j][ci] is a
-// 1 x 1 weight gradient over 64 * taps "virtual" channels whose 64-wide groups are consecutive ROWS of x; the kernel gathers
-// them chunk by chunk while staging, the reducer scatters virtual columns back to (ci, tap).  MEASURED SLOWER than the
-// register-staged generic kernel on the layers it was built for (k2/out_stride 2, 64 -> 128: 221 vs 176 us per launch;
-// 64 -> 64: 89 vs 73; k4/stride 2: 138 vs 116 -- both forms already move their bytes at 5-6 TB/s: each phase of a transpose
-// re-reads x, each 64-channel output block re-reads it again), so it is OFF unless SMT_WGRAD_WINDOW=1 (read per call).
-static bool wgrad_window_desc(const smt_conv_desc* d, smt_conv_desc* v) {
-  const char* env = getenv("SMT_WGRAD_WINDOW");
-  const bool off = !env || atoi(env) == 0;
-  const bool shape = (d->stride == 2 && d->taps == 4 && d->out_stride == 1 && d->out_offset == 0) ||
-                     (d->stride == 1 && d->taps == 2 && d->out_stride >= 1);
-  if (off || d->dtype != SMT_BF16 || d->c_in != 64 || d->c_out % 64 != 0 || !d->zero_page || d->dilation != 1 || !shape ||
-      d->ld_x % 8 != 0 || d->ld_y % 8 != 0 || d->t_out < 1)
-    return false;
-  *v = *d;
-  v->c_in = 64 * d->taps; v->taps = 1; v->stride = 1; v->dilation = 1; v->padding = 0;
-  v->out_stride = 1; v->out_offset = 0;                   // folded into the dy pointer and pitch by the launcher
   return true;
 }
 
-static int wgrad_window(const smt_conv_desc* d, const smt_conv_desc* v, float* dweight, int64_t stride_out, int64_t stride_in,
-                        int64_t stride_tap, const int* tap_map, float* dbias, void* workspace, size_t workspace_bytes,
-                        hipStream_t stream) {
-  SMT_CHECK_ARG(d->x && d->y && dweight && workspace, "smt_conv1d_wgrad: null pointer");
-  SMT_CHECK_ARG(workspace_bytes >= wgrad_group_ws(v), "smt_conv1d_wgrad: workspace too small");
-  SMT_CHECK_ARG((long long)(d->t_out - 1) * d->out_stride + d->out_offset < d->t_y, "smt_conv1d_wgrad: output rows out of range");
-  int rpc, cpb, nco, nci, planes;
-  wgrad_plan(v, &rpc, &cpb, &nco, &nci, &planes);
-  WgradArgs a;
-  a.x = d->x; a.slab = (float*)workspace; a.lens_in = d->lens_in;
-  a.dy = reinterpret_cast<const __bf16*>(d->y) + (long long)d->out_offset * d->ld_y;
-  a.x_bs = d->bs_x; a.dy_bs = d->bs_y; a.ldx = d->ld_x; a.ldy = d->ld_y * d->out_stride;
-  a.B = d->batch; a.Tin = d->t_in; a.Tout = d->t_out; a.Ty = d->t_y; a.Cin = v->c_in; a.Cout = d->c_out;
-  a.taps = 1; a.stride = 1; a.dil = 1; a.pad = d->padding; a.out_stride = 1; a.out_offset = 0;
-  a.rows_per_chunk = rpc; a.chunks_per_batch = cpb; a.nblk_ci = nci; a.nblk_co = nco; a.with_bias = dbias ? 1 : 0;
-  a.rs = 1; a.win = 1; a.xstride = d->stride;
-  const int n_chunks = d->batch * cpb;
-  if (d->batch > 0) {
-    dim3 grid((unsigned)(8 * ((n_chunks + 7) / 8) * nco * nci));
-    const size_t lds_dma = 3 * ((size_t)128 * 128 + (size_t)128 * 256);      // three stage buffers in window mode
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_dma_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    conv_wgrad_dma_kernel<2><<<grid, 512, lds_dma, stream>>>(a, (const __bf16*)d->zero_page);
-    SMT_CHECK_LAUNCH("conv_wgrad_dma");
-  }
-  return launch_wgrad_reduce((const float*)workspace, dweight, dbias, d->batch > 0 ? n_chunks : 0, nco, nci, 1, v->c_in,
-                             d->c_out, 128, stride_out, stride_in, stride_tap, tap_map, stream, 1, /*vsplit=*/64);
+extern "C" size_t smt_conv1d_wgrad_workspace_bytes(const smt_conv_desc* d) {
+  WgradPlan pl;
+  return wgrad_plan(d, &pl) ? pl.ws_bytes : 0;
 }
 
 extern "C" const char* smt_conv1d_wgrad_kernel_name(const smt_conv_desc* d) {
-  if (!d) return "";
-  ShiftPlan pl;
-  if (wgrad_shift_plan(d, &pl)) return "conv_wgrad_shift";
-  smt_conv_desc wv;
-  if (wgrad_window_desc(d, &wv)) return "conv_wgrad_dma";
-  const smt_conv_desc g = wgrad_group_desc(d, 0, std::min(WG_GROUP, d->taps));
-  const int rows_x = 127 * g.stride + (g.taps - 1) * (wgrad_rs(&g) > 1 ? 1 : g.dilation) + 1;
-  const size_t lds_dma = 2 * ((size_t)128 * 128 + (size_t)((rows_x + 3) & ~3) * 256);
-  const bool dma = g.dtype == SMT_BF16 && wgrad_cib(&g) == 128 && g.stride == 1 && g.zero_page && g.c_in % 128 == 0 &&
-                   g.c_out % 64 == 0 && g.out_stride == 1 && g.out_offset == 0 && lds_dma <= 160 * 1024;
-  return dma ? "conv_wgrad_dma" : "conv_wgrad";
+  WgradPlan pl;
+  return wgrad_plan(d, &pl) ? kWgradName[pl.l[0].variant] : "";
+}
+
+// every kernel here takes its tiles in dynamic LDS beyond the 64 KiB default
+template <typename... P, typename... A>
+static void launch_lds(void (*kernel)(P...), unsigned grid, unsigned threads, size_t lds, hipStream_t stream, A... args) {
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_MAX_LDS);
+  kernel<<<dim3(grid), dim3(threads), lds, stream>>>(args...);
+}
+
+typedef void (*WgradKernel)(WgradArgs);
+static_assert(WG_GROUP == 5, "the kernels are instantiated for 2 .. 6 accumulator planes (1 .. 5 taps + bias)");
+#define SMT_WG_BY_PLANES(planes, K) \
+  ((planes) == 2 ? K(2) : (planes) == 3 ? K(3) : (planes) == 4 ? K(4) : (planes) == 5 ? K(5) : K(6))
+template <typename T, int CIB, bool STRIDED> static WgradKernel generic_kernel(int planes) {
+#define SMT_WG_K(NT) (WgradKernel)conv_wgrad_kernel<T, NT, CIB, STRIDED>
+  return SMT_WG_BY_PLANES(planes, SMT_WG_K);
+#undef SMT_WG_K
+}
+static WgradKernel dma_kernel(int planes) {
+#define SMT_WG_K(NT) (WgradKernel)conv_wgrad_dma_kernel<NT>
+  return SMT_WG_BY_PLANES(planes, SMT_WG_K);
+#undef SMT_WG_K
 }
 
 extern "C" int smt_conv1d_wgrad(const smt_conv_desc* d, float* dweight, int64_t stride_out, int64_t stride_in,
@@ -951,41 +792,59 @@ extern "C" int smt_conv1d_wgrad(const smt_conv_desc* d, float* dweight, int64_t 
                                 size_t workspace_bytes, smt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SMT_CHECK_ARG(d && tap_map, "smt_conv1d_wgrad: null pointer");
-  SMT_CHECK_ARG(d->taps >= 1 && d->taps <= 16, "smt_conv1d_wgrad: taps must be in [1, 16]");
-  ShiftPlan pl;
-  if (wgrad_shift_plan(d, &pl)) {      // all taps in one launch, fragments shifted in registers
-    SMT_CHECK_ARG(d->x && d->y && dweight && workspace, "smt_conv1d_wgrad: null pointer");
-    SMT_CHECK_ARG(d->ld_x % 8 == 0 && d->ld_y % 8 == 0, "smt_conv1d_wgrad: pitches must keep 16-byte alignment");
-    SMT_CHECK_ARG(workspace_bytes >= smt_conv1d_wgrad_workspace_bytes(d), "smt_conv1d_wgrad: workspace too small");
-    ShiftArgs a;
-    a.x = d->x; a.dy = d->y; a.slab = (float*)workspace; a.lens_in = d->lens_in;
-    a.x_bs = d->bs_x; a.dy_bs = d->bs_y; a.ldx = d->ld_x; a.ldy = d->ld_y;
-    a.B = d->batch; a.Tin = d->t_in; a.Tout = d->t_out; a.pad = pl.pad; a.rs = pl.rs;
-    a.tiles_per_item = pl.tiles_per_item; a.tiles_per_wg = pl.tiles_per_wg; a.n_chunks = pl.n_chunks;
-    a.nblk_ci = pl.nblk_ci; a.nblk_co = pl.nblk_co; a.with_bias = dbias ? 1 : 0;
-    dim3 grid((unsigned)(8 * ((pl.n_chunks + 7) / 8) * pl.nblk_co * pl.nblk_ci));
-    switch (d->taps) {
-      case 3: launch_shift<3>(a, d->zero_page, grid, stream); break;
-      case 5: launch_shift<5>(a, d->zero_page, grid, stream); break;
-      case 7: launch_shift<7>(a, d->zero_page, grid, stream); break;
-      default: launch_shift<9>(a, d->zero_page, grid, stream); break;
+  SMT_CHECK_ARG(d->taps >= 1 && d->taps <= WG_MAX_TAPS, "smt_conv1d_wgrad: taps must be in [1, 16]");
+  SMT_CHECK_ARG(d->x && d->y && dweight && workspace, "smt_conv1d_wgrad: null pointer");
+  SMT_CHECK_ARG(d->dtype == SMT_BF16 || d->dtype == SMT_F32, "smt_conv1d_wgrad: bad dtype");
+  const bool bf = d->dtype == SMT_BF16;
+  const int epv = bf ? 8 : 4;
+  SMT_CHECK_ARG(d->c_in % epv == 0 && d->c_out % epv == 0 && d->ld_x % epv == 0 && d->ld_y % epv == 0,
+                "smt_conv1d_wgrad: channels / pitches must keep 16-byte alignment");
+  WgradPlan pl;
+  wgrad_plan(d, &pl);
+  SMT_CHECK_ARG(workspace_bytes >= pl.ws_bytes, "smt_conv1d_wgrad: workspace too small");
+  const bool empty = d->batch <= 0 || d->t_out <= 0;
+  for (int i = 0; i < pl.n; ++i) {
+    const WgradLaunch& l = pl.l[i];
+    float* slab = reinterpret_cast<float*>((char*)workspace + l.ws_off);
+    float* db = i == 0 ? dbias : nullptr;
+    if (l.variant == WG_SHIFT) {      // fragments shifted in registers
+      ShiftArgs a;
+      a.x = d->x; a.dy = d->y; a.slab = slab; a.lens_in = d->lens_in;
+      a.x_bs = d->bs_x; a.dy_bs = d->bs_y; a.ldx = d->ld_x; a.ldy = d->ld_y;
+      a.B = d->batch; a.Tin = d->t_in; a.Tout = d->t_out; a.pad = l.pad; a.rs = pl.sh.rs;
+      a.tiles_per_item = pl.sh.tiles_per_item; a.tiles_per_wg = pl.sh.tiles_per_wg; a.n_chunks = l.n_chunks;
+      a.nblk_ci = l.nblk_ci; a.nblk_co = l.nblk_co; a.with_bias = db ? 1 : 0;
+      const __bf16* zp = (const __bf16*)d->zero_page;
+      switch (d->taps) {
+        case 3: launch_lds(conv_wgrad_shift_kernel<3>, l.grid, 512, l.lds, stream, a, zp); break;
+        case 5: launch_lds(conv_wgrad_shift_kernel<5>, l.grid, 512, l.lds, stream, a, zp); break;
+        case 7: launch_lds(conv_wgrad_shift_kernel<7>, l.grid, 512, l.lds, stream, a, zp); break;
+        default: launch_lds(conv_wgrad_shift_kernel<9>, l.grid, 512, l.lds, stream, a, zp); break;
+      }
+      SMT_CHECK_LAUNCH(kWgradName[l.variant]);
+    } else if (!empty) {
+      SMT_CHECK_ARG(l.lds <= WG_MAX_LDS, "conv_wgrad: tile needs %zu B of LDS", l.lds);
+      WgradArgs a;
+      a.x = d->x; a.dy = d->y; a.slab = slab; a.lens_in = d->lens_in;
+      a.x_bs = d->bs_x; a.dy_bs = d->bs_y; a.ldx = d->ld_x; a.ldy = d->ld_y;
+      a.B = d->batch; a.Tin = d->t_in; a.Tout = d->t_out; a.Ty = d->t_y; a.Cin = d->c_in; a.Cout = d->c_out;
+      a.taps = l.taps; a.stride = d->stride; a.dil = d->dilation; a.pad = l.pad;
+      a.out_stride = d->out_stride; a.out_offset = d->out_offset;
+      a.rows_per_chunk = l.rows_per_chunk; a.chunks_per_batch = l.chunks_per_batch;
+      a.nblk_ci = l.nblk_ci; a.nblk_co = l.nblk_co; a.with_bias = db ? 1 : 0;
+      const bool strided = d->stride > 1;
+      const int planes = l.taps + 1;
+      const WgradKernel k = l.variant == WG_DMA ? dma_kernel(planes)
+                          : bf && l.cib == 128  ? generic_kernel<__bf16, 128, false>(planes)
+                          : bf ? (strided ? generic_kernel<__bf16, 64, true>(planes) : generic_kernel<__bf16, 64, false>(planes))
+                               : (strided ? generic_kernel<float, 64, true>(planes) : generic_kernel<float, 64, false>(planes));
+      launch_lds(k, l.grid, l.variant == WG_DMA ? 512 : l.cib * 4, l.lds, stream, a);
+      SMT_CHECK_LAUNCH(kWgradName[l.variant]);
     }
-    SMT_CHECK_LAUNCH("conv_wgrad_shift");
-    return launch_wgrad_reduce((const float*)workspace, dweight, dbias, pl.n_chunks, pl.nblk_co, pl.nblk_ci, d->taps,
-                               d->c_in, d->c_out, 128, stride_out, stride_in, stride_tap, tap_map, stream, 4);
-  }
-  SMT_CHECK_ARG(workspace_bytes >= smt_conv1d_wgrad_workspace_bytes(d), "smt_conv1d_wgrad: workspace too small");
-  smt_conv_desc wv;
-  if (wgrad_window_desc(d, &wv))
-    return wgrad_window(d, &wv, dweight, stride_out, stride_in, stride_tap, tap_map, dbias, workspace, workspace_bytes, stream);
-  size_t off = 0;
-  for (int j0 = 0; j0 < d->taps; j0 += WG_GROUP) {
-    smt_conv_desc g = wgrad_group_desc(d, j0, std::min(WG_GROUP, d->taps - j0));
-    const size_t need = align_up(wgrad_group_ws(&g), 256);
-    int rc = wgrad_group(&g, dweight, stride_out, stride_in, stride_tap, tap_map + j0, j0 == 0 ? dbias : nullptr,
-                         (char*)workspace + off, need, stream);
+    const int bias_cols = l.variant == WG_SHIFT ? 4 : 1;   // the shift kernel leaves four partial bias columns
+    int rc = launch_wgrad_reduce(slab, dweight, db, empty ? 0 : l.n_chunks, l.nblk_co, l.nblk_ci, l.taps, d->c_in, d->c_out,
+                                 l.cib, stride_out, stride_in, stride_tap, tap_map + l.j0, stream, bias_cols);
     if (rc) return rc;
-    off += need;
   }
   return 0;
 }

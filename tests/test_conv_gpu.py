@@ -599,14 +599,13 @@ def test_fused_gate_conv_backward_matches_separate_kernels(b, t):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,c_out,b,t", [("down", 64, 3, 2000), ("down", 128, 2, 9002), ("up0", 64, 3, 1500), ("up1", 128, 2, 7001),
                                             ("down", 64, 1, 2)])
-def test_window_mode_weight_gradient_of_the_resampling_convs(kind, c_out, b, t, monkeypatch):
+def test_weight_gradient_of_the_resampling_convs(kind, c_out, b, t):
     """Weight / bias gradients of the 64-channel k = 4, stride-2 conv ("down": dW[co][ci][j] = sum dy[t][co] x[2t - 1 + j][ci])
     and of the two 2-tap phases of its transpose ("up0": rows x[m - 1], x[m] against dy[2m]; "up1": x[m], x[m + 1] against
-    dy[2m + 1]) on the LDS-DMA kernel's window mode, against float64 sums and against the generic kernel (descriptor without
-    zero_page); ragged input lengths, one-hot dy picks out the input rows exactly."""
+    dy[2m + 1]) on the generic kernel, which they run on with or without a zero page, against float64 sums; ragged input
+    lengths, one-hot dy picks out the input rows exactly."""
     import ctypes
     from smt_amd import convops as C
-    monkeypatch.setenv("SMT_WGRAD_WINDOW", "1")            # opt-in: measured slower than the generic kernel (DESIGN section 3)
     g = torch.Generator(device="cuda").manual_seed(7 * t + c_out)
     bf = torch.bfloat16
     if kind == "down":
@@ -620,12 +619,12 @@ def test_window_mode_weight_gradient_of_the_resampling_convs(kind, c_out, b, t, 
     dy = torch.randn(b, t_y, c_out, device="cuda", generator=g).to(bf)
     lens = torch.tensor([t_in, max(1, t_in // 3), 1][:b], device="cuda", dtype=torch.int32)
 
-    def run(fast, dout):
+    def run(zero_page, dout):
         dw = torch.full((c_out, 64, taps), 9.0, device="cuda")
         db = torch.full((c_out,), 9.0, device="cuda")
         d = C._base_desc(x, dout, lens, 64, c_out, taps, stride, 1, pad, t_out, t_y=t_y, out_stride=os_, out_offset=oo)
         lib = C.N.lib()
-        if fast:
+        if zero_page:
             d.zero_page = C._p(C._zero_page(x.device))
         name = lib.smt_conv1d_wgrad_kernel_name(ctypes.byref(d)).decode()
         ws = torch.empty(max(16, lib.smt_conv1d_wgrad_workspace_bytes(ctypes.byref(d))), dtype=torch.uint8, device="cuda")
@@ -637,7 +636,7 @@ def test_window_mode_weight_gradient_of_the_resampling_convs(kind, c_out, b, t, 
 
     n0, dw0, db0 = run(False, dy)
     n1, dw1, db1 = run(True, dy)
-    assert (n0, n1) == ("conv_wgrad", "conv_wgrad_dma")
+    assert (n0, n1) == ("conv_wgrad", "conv_wgrad")
     # float64 reference
     xm = x.double().clone()
     for i in range(b):
@@ -653,7 +652,8 @@ def test_window_mode_weight_gradient_of_the_resampling_convs(kind, c_out, b, t, 
     tol = 2e-6 * float(ref.abs().max()) * (b * t_out) ** 0.5 + 1e-4
     assert float((dw1.double() - ref).abs().max()) <= tol and float((dw0.double() - ref).abs().max()) <= tol
     dbr = dyr.sum((0, 1))
-    assert float((db1.double() - dbr).abs().max()) <= 2e-6 * float(dbr.abs().max()) * (b * t_out) ** 0.5 + 1e-3
+    tol_b = 2e-6 * float(dbr.abs().max()) * (b * t_out) ** 0.5 + 1e-3
+    assert float((db1.double() - dbr).abs().max()) <= tol_b and float((db0.double() - dbr).abs().max()) <= tol_b
     if t_out >= 1000:                                       # one-hot dy: the gradient IS the shifted input rows
         hot = torch.zeros_like(dy)
         m = 777
@@ -664,6 +664,52 @@ def test_window_mode_weight_gradient_of_the_resampling_convs(kind, c_out, b, t, 
             want = x[1, r].float() if r < int(lens[1]) else torch.zeros(64, device="cuda")
             assert torch.equal(dwh[5, :, j], want)
         assert float(dwh[:5].abs().max()) == 0 and float(dbh.sum()) == 1.0
+
+
+WGRAD_DMA_CASES = [
+    # b, t, c_in, c_out, k, dil, pad, lens
+    (3, 700, 128, 128, 3, 1, 1, [700, 233, 1]),            # single-tile chunks; a partial last tile
+    (3, 700, 128, 128, 9, 27, 108, [700, 233, 1]),         # two tap groups (5 + 4); halo wider than item 2's valid length
+    (3, 50021, 128, 128, 4, 1, 1, [50021, 33333, 1]),      # three tiles per chunk: steady-state prefetch, last-tile drain
+    (2, 3000, 256, 192, 3, 1, 1, None),                    # 2 x 3 blocks of (ci, co); the bias plane only in ci0 == 0
+    (1, 1, 128, 128, 3, 1, 1, None),                       # one row
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("b,t,c_in,c_out,k,dil,pad,lens", WGRAD_DMA_CASES)
+def test_lds_dma_wgrad_matches_float64(b, t, c_in, c_out, k, dil, pad, lens):
+    """conv_wgrad_dma_kernel (double-buffered LDS-DMA staging through range-checked descriptors, swizzled transposed
+    fragments, tap groups of <= 5) against a float64 evaluation of the same bf16 operands.  Where lens are given the
+    operands are channel slices of wider tensors.  An even tap count (k = 4, one output row fewer) keeps the long case off
+    the shift kernel."""
+    import ctypes
+    from smt_amd import convops as C
+    g = torch.Generator(device="cuda").manual_seed(300 + 7 * k + t)
+    t_out = t + 2 * pad - dil * (k - 1)
+    if lens is not None:
+        xb = torch.randn(b, t, c_in + 128, device="cuda", generator=g).to(torch.bfloat16)
+        dyb = torch.randn(b, t_out, c_out + 256, device="cuda", generator=g).to(torch.bfloat16)
+        x, dy = xb[:, :, 128:128 + c_in], dyb[:, :, 128:128 + c_out]
+        lens = torch.tensor(lens, device="cuda", dtype=torch.int32)
+    else:
+        x = torch.randn(b, t, c_in, device="cuda", generator=g).to(torch.bfloat16)
+        dy = torch.randn(b, t_out, c_out, device="cuda", generator=g).to(torch.bfloat16)
+    dw, db = torch.empty(c_out, c_in, k, device="cuda"), torch.empty(c_out, device="cuda")
+    d = C._base_desc(x, dy, lens, c_in, c_out, k, 1, dil, pad, t_out)
+    C._wgrad(d, dw, c_in * k, k, 1, list(range(k)), db)      # sets the zero page
+    torch.cuda.synchronize()
+    assert C.N.lib().smt_conv1d_wgrad_kernel_name(ctypes.byref(d)).decode() == "conv_wgrad_dma"
+    xm = x.double()
+    if lens is not None:
+        mask = (torch.arange(t, device="cuda")[None, :] < lens[:, None])[:, :, None]
+        xm = torch.where(mask, xm, torch.zeros_like(xm))
+    xp = torch.nn.functional.pad(xm, (0, 0, pad, pad))
+    ref = torch.stack([torch.einsum("bto,bti->oi", dy.double(), xp[:, s * dil:s * dil + t_out]) for s in range(k)], dim=2)
+    tol = 2e-6 * float(ref.abs().max()) * (b * t) ** 0.5 + 1e-4     # fp32 accumulation over b*t rows
+    assert float((dw.double() - ref).abs().max()) <= tol
+    dbr = dy.double().sum((0, 1))
+    assert float((db.double() - dbr).abs().max()) <= 2e-6 * float(dbr.abs().max()) * (b * t) ** 0.5 + 1e-3
 
 
 @pytest.mark.gpu
