@@ -58,6 +58,8 @@ int smt_vq_prepare(const float* codebook, int k_bins, int dim, void* prep, size_
  *   x_d      [n_rows, dim]   k[idx] * row_mask   (may be NULL)
  *   sums     [4] f32: {sum_all min_dist, sum_masked min_dist, sum mask,
  *                      number of rows that needed exact (fp64) re-scoring}
+ * A row of x that holds a NaN has no finite distance: it gets idx 0, a NaN min_dist and x_d = k[0] * row_mask (what the
+ * reference's min over a NaN distance row dequantises, and what the grouped quantiser writes); the sums over it are NaN.
  * dim in {32, 64, 128}; k_bins >= 1. */
 size_t smt_vq_forward_workspace_bytes(int64_t n_rows, int k_bins, int dim);
 int smt_vq_forward(const float* x, const float* codebook, void* prep, const float* row_mask,

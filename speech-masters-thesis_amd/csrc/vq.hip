@@ -365,15 +365,14 @@ __global__ __launch_bounds__(256) void vq_exact_kernel(const float* __restrict__
       const int oc = __shfl_xor(code, o, 64);
       if (od < d || (od == d && oc < code)) { d = od; code = oc; }
     }
-    if (rvalid && code != 0x7fffffff) {
-      if (x_d) {
-        const float m = row_mask ? row_mask[row] : 1.f;
-        for (int i = l; i < D; i += 32) x_d[row * D + i] = cb[(size_t)code * D + i] * m;
-      }
-      if (l == 0) { idx[row] = code; min_dist[row] = (float)d; }   // the exact distance, rounded once
-    } else if (rvalid && l == 0) {                                 // NaN row: keep the outputs defined
-      idx[row] = 0; min_dist[row] = __builtin_nanf("");
+    if (!rvalid) continue;
+    const bool found = code != 0x7fffffff;                   // false on a NaN row: keep the outputs defined (code 0, as
+    const int cc = found ? code : 0;                         // vqg_exact_kernel and the reference's min over NaNs do)
+    if (x_d) {
+      const float m = row_mask ? row_mask[row] : 1.f;
+      for (int i = l; i < D; i += 32) x_d[row * D + i] = cb[(size_t)cc * D + i] * m;
     }
+    if (l == 0) { idx[row] = cc; min_dist[row] = found ? (float)d : __builtin_nanf(""); }   // the exact distance, rounded once
   }
 }
 
