@@ -167,6 +167,34 @@ int smt_recon_loss_bwd(const float* y, const float* yh, const int* lens, const f
 int smt_maximum_path(const float* value, const float* mask, int batch, int t_x, int t_y, float max_neg_val, float* path,
                      smt_stream_t stream);
 
+/* ------------------------------------------------------ VQTTS alignment ---- */
+/* Text-audio alignment of VQTTS (models/vqtts/vqtts.py:133-137, 150-156; ABI 9).  All tensors channels-last fp32:
+ * x_enc [batch, t_x, dim] (text encoder means), y_enc [batch, t_q, dim] (audio encoder output), x_lens / q_lens [batch]
+ * int32 on the device; nothing synchronises with the host.  Limits of every entry: dim a multiple of 4 up to 256,
+ * t_x <= 512, t_q <= 32768, batch <= 65535 -- an argument error that names the limit otherwise.  Inputs are finite.
+ *
+ * distance: dist[b, i, j] = sqrtf(sum_d (x[b, i, d] - y[b, j, d])^2), the squared differences accumulated with fmaf in
+ *   ascending d (no |x|^2 + |y|^2 - 2xy expansion).  Dense; for tests and small shapes.
+ * align: the distance fused with the monotonic search, no [batch, t_x, t_q] tensor anywhere.  idx [batch, t_q] int32 =
+ *   the token of each frame, -1 = none (the convention of smt_glow_align_index); dur [batch, t_x] = frames per token.
+ *   For every item, whatever its lengths (0 and q_len < x_len included), both are bit-identical to
+ *   smt_glow_align_index(smt_maximum_path(value = -dist, mask, max_neg_val = -inf)) with dist from smt_vqtts_distance and
+ *   mask[b, i, j] = (i < x_lens[b]) (j < q_lens[b]); rows of x_enc / y_enc at or past the lengths are never read.
+ *   workspace: smt_vqtts_align_workspace_bytes = batch * t_q * ceil(t_x / 64) * 8 bytes (direction bits), 8-byte aligned.
+ * align_loss: frame_dist[b, j] = dist(x[b, idx[b, j]], y[b, j]) (0 where idx < 0), sum[0] = their sum in a fixed order
+ *   (equal inputs give equal bits).  bwd with the DEVICE scalar coef = g / denom: dy[b, j] = coef (y_j - x_i) / dist,
+ *   dx[b, i] = -(sum of dy over the frames of token i, in frame order; idx must be a monotonic path, as align returns).
+ *   A frame with dist == 0 contributes 0 to both (the reference's sqrt backward gives NaN there); idx < 0 gives dy = 0. */
+int smt_vqtts_distance(const float* x_enc, const float* y_enc, float* dist, int batch, int t_x, int t_q, int dim,
+                       smt_stream_t stream);
+size_t smt_vqtts_align_workspace_bytes(int batch, int t_x, int t_q);
+int smt_vqtts_align(const float* x_enc, const float* y_enc, const int* x_lens, const int* q_lens, int batch, int t_x, int t_q,
+                    int dim, int* idx, float* dur, void* workspace, size_t workspace_bytes, smt_stream_t stream);
+int smt_vqtts_align_loss(const float* x_enc, const float* y_enc, const int* idx, int batch, int t_x, int t_q, int dim,
+                         float* frame_dist, float* sum, smt_stream_t stream);
+int smt_vqtts_align_loss_bwd(const float* x_enc, const float* y_enc, const int* idx, const float* frame_dist, const float* coef,
+                             int batch, int t_x, int t_q, int dim, float* dx, float* dy, smt_stream_t stream);
+
 /* ------------------------------------------------------------ conv stack ---- */
 /* Counter-based dropout ("dropout" spec).  The reference draws dropout masks from torch's global
  * RNG (models/vqvae/resnet.py:22,25), which no other device can reproduce; this build defines a

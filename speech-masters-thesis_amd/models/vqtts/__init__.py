@@ -1,3 +1,4 @@
+from .align import TextAudioAlignment
 from .bottleneck import Bottleneck
 
-__all__ = ["Bottleneck"]
+__all__ = ["Bottleneck", "TextAudioAlignment"]
