@@ -195,6 +195,42 @@ int smt_vqtts_align_loss(const float* x_enc, const float* y_enc, const int* idx,
 int smt_vqtts_align_loss_bwd(const float* x_enc, const float* y_enc, const int* idx, const float* frame_dist, const float* coef,
                              int batch, int t_x, int t_q, int dim, float* dx, float* dy, smt_stream_t stream);
 
+/* ------------------------------------------------------ VQTTS code head ---- */
+/* The code predictor's projection fused with its cross-entropy (models/vqtts/vqtts.py:86-87, 142-144, 157, 175-178, 190;
+ * ABI 10): logits = h . weight^T + bias are formed tile by tile on the MFMA and never stored, nor is their gradient.
+ * h [rows, channels] fp32 channels-last rows, weight [bins, channels] and bias [bins] fp32, target [rows] int64 with
+ * target < 0 = "not scored" (the convention of smt_lm_ce_fwd; a scored target must be < bins).  Nothing synchronises with
+ * the host.  Limits of every entry: channels a multiple of 16 up to 256, bins a multiple of 32 up to 1024, rows up to
+ * 2^31 - 1 -- an argument error that names the limit otherwise.  h, dh and both workspaces are 16-byte aligned.
+ *
+ * Arithmetic of a logit: every fp32 operand is split into a bf16 pair, hi = bf16(x), lo = bf16(x - hi), and bias +
+ *   sum (w_lo h_hi + w_hi h_lo + w_hi h_hi) is accumulated in fp32 by v_mfma_f32_32x32x16_bf16, 16 channels per step in
+ *   ascending order -- the same instruction sequence for every column, so equal weight rows give equal logits.
+ *   |logit - exact| <= 2^-15 (sum_c |h_c||w_c| + |b|).
+ * prepare: splits weight into `workspace` (smt_vqtts_code_head_workspace_bytes = 8 * bins * padded channels, channels
+ *   padded to 32 / 64 / 128 / 256); once per weight version, the workspace is read-only afterwards.
+ * fwd: per row lse = logsumexp(logits) (online, stable), pred = argmax (lowest index on ties, int32),
+ *   row_loss = lse - logit[target] and correct = (pred == target) as 0/1, both 0 on unscored rows; then
+ *   sums[0..2] = sum of row_loss, sum of correct, number of scored rows as DOUBLES, added in a fixed order in two stages
+ *   (equal inputs give equal bits); `sums` holds 3 + 3 * 256 doubles, the rest is the first stage's partial sums.
+ *   target == NULL is the synthesis form: only pred and, if lse != NULL, lse are written.  rows == 0 writes three zeros
+ *   (nothing in the synthesis form) and takes NULL for h and the per-row outputs.
+ * bwd: with the DEVICE scalar coef = g / count and the saved lse it recomputes the logits with the same arithmetic,
+ *   p = exp(logit - lse), G = coef (p - onehot(target)), 0 on unscored rows, and writes dh = G . weight [rows, channels],
+ *   dweight = G^T . h [bins, channels], dbias = sum_r G; G's bf16 pair feeds the MFMAs the same way.  dweight / dbias:
+ *   one slab per row slice in `scratch` (smt_vqtts_code_head_bwd_workspace_bytes), added in slice order in fp64 -- no
+ *   float atomics, equal inputs give equal bits. */
+size_t smt_vqtts_code_head_workspace_bytes(int channels, int bins);
+int smt_vqtts_code_head_prepare(const float* weight, int channels, int bins, void* workspace, size_t workspace_bytes,
+                                smt_stream_t stream);
+int smt_vqtts_code_head_fwd(const float* h, const void* workspace, size_t workspace_bytes, const float* bias,
+                            const int64_t* target, int64_t rows, int channels, int bins, float* lse, float* row_loss, int* pred,
+                            float* correct, double* sums, smt_stream_t stream);
+size_t smt_vqtts_code_head_bwd_workspace_bytes(int64_t rows, int channels, int bins);
+int smt_vqtts_code_head_bwd(const float* h, const void* workspace, size_t workspace_bytes, const float* bias,
+                            const int64_t* target, const float* lse, const float* coef, int64_t rows, int channels, int bins,
+                            float* dh, float* dweight, float* dbias, void* scratch, size_t scratch_bytes, smt_stream_t stream);
+
 /* ------------------------------------------------------------ conv stack ---- */
 /* Counter-based dropout ("dropout" spec).  The reference draws dropout masks from torch's global
  * RNG (models/vqvae/resnet.py:22,25), which no other device can reproduce; this build defines a

@@ -1,4 +1,5 @@
 from .align import TextAudioAlignment
 from .bottleneck import Bottleneck
+from .predictor import CodePredictor
 
-__all__ = ["Bottleneck", "TextAudioAlignment"]
+__all__ = ["Bottleneck", "CodePredictor", "TextAudioAlignment"]

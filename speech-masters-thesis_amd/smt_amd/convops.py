@@ -122,7 +122,7 @@ class _PackCache:
         self.order = []          # keys in table order
         self.table = None        # {device: (table_dev, block_entry_dev, block_local_dev, n_blocks)}
         self.dirty = False       # set by mark_packed_weights_dirty(): repack on the next use whatever the versions say
-        self.generation = 0      # number of mark_packed_weights_dirty() calls (tests)
+        self.generation = 0      # number of mark_packed_weights_dirty() calls (packed_weights_generation)
         self.epoch = 0           # moves when copies are thrown away (pruning / overflow): captured graphs check it
         self.repacks = 0         # batched repack launches so far (tests)
 
@@ -286,6 +286,12 @@ def invalidate_packed_weights():
     captured hipGraph that points at them (smt_amd/graph.py) stays valid; only an overflow of the cache (MAX_ENTRIES)
     throws them away, which ``pack_epoch()`` reports."""
     mark_packed_weights_dirty()
+
+
+def packed_weights_generation():
+    """Moves whenever the parameters have or may have changed (``mark_packed_weights_dirty``): other per-weight caches of
+    this build key on it beside ``_version`` (smt_amd.vqtts.WeightSplit)."""
+    return _pack_cache.generation
 
 
 def pack_epoch():

@@ -9,7 +9,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SMT_HIP_LIB: an alternative build of the same ABI (tools/ablate_*.sh link their -D ablation builds to libsmt_hip_abl.so)
 LIB_PATH = os.environ.get("SMT_HIP_LIB") or os.path.join(_HERE, "libsmt_hip.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _lib = None
 _lock = threading.Lock()
@@ -78,6 +78,13 @@ _SIGNATURES = {
     "smt_vqtts_align": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "smt_vqtts_align_loss": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
     "smt_vqtts_align_loss_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "smt_vqtts_code_head_workspace_bytes": (c_size, [c_int, c_int]),
+    "smt_vqtts_code_head_prepare": (c_int, [c_ptr, c_int, c_int, c_ptr, c_size, c_ptr]),
+    "smt_vqtts_code_head_fwd": (c_int, [c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                        c_ptr]),
+    "smt_vqtts_code_head_bwd_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
+    "smt_vqtts_code_head_bwd": (c_int, [c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr,
+                                        c_ptr, c_size, c_ptr]),
     "smt_recon_loss_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
     "smt_recon_loss_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
     "smt_stft_num_frames": (c_int, [c_int, c_int, c_int]),

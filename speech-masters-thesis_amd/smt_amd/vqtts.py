@@ -1,15 +1,23 @@
 """VQTTS text-audio alignment on the HIP library (include/smt_hip.h, "VQTTS alignment"): the Euclidean distance between
 text-encoder means and audio-encoder frames, the monotonic search over it and the loss on the found path.  fp32,
 channels-last rows [B, T, D], prefix masks as int32 lengths on the device, no host synchronisation.
-Reference: models/vqtts/vqtts.py:133-137, 150-156."""
+Reference: models/vqtts/vqtts.py:133-137, 150-156.
+
+The code head ("VQTTS code head" of the header, csrc/vqtts_codes.hip): the projection to l_bins logits fused with the
+cross-entropy or the argmax -- reference models/vqtts/vqtts.py:144, 157, 176, 190."""
 import torch
 
+from . import convops
 from . import native as N
 from . import profiler
 
 # the fused search's own constants (csrc/vqtts_align.hip): columns per distance slab, columns per backtrack chunk,
 # columns per walk step, rows per ballot word
 ALIGN_SLAB, ALIGN_CHUNK, ALIGN_WALK, ALIGN_WORD = 32, 512, 64, 64
+# the code head's constants (csrc/vqtts_codes.hip, CH_*): rows per workgroup of the row kernels, weight rows staged per step,
+# columns of V per workgroup and rows per slice of the weight-gradient kernel, the most slabs its reduce adds, the most
+# partial sums of the forward's reduce, the limits
+CH_ROWS, CH_VT, CH_VCOLS, CH_SLICE, CH_MAX_SLICES, CH_SUM_PARTS, CH_MAX_C, CH_MAX_V = 128, 64, 64, 4096, 256, 256, 256, 1024
 
 
 def _f(t):
@@ -89,3 +97,110 @@ def align_loss(x_enc, y_enc, idx, denom):
     ``(distances * attn).sum() / attn_mask.sum()`` of the reference on the path.  Gradients to both encodings; a frame at
     distance exactly 0 contributes none (the reference's sqrt backward gives NaN there)."""
     return _AlignLoss.apply(x_enc, y_enc, idx, denom)
+
+
+# ------------------------------------------------------------------------------------------------------- code head
+class WeightSplit:
+    """The bf16-pair split of one projection weight (smt_vqtts_code_head_prepare), kept by whoever owns the weight and
+    redone when the weight has or may have changed.  The key is the weight's (data_ptr, _version) -- the rule of
+    ``Bottleneck._search_prep`` -- and the generation of ``convops.mark_packed_weights_dirty``: a fused optimizer step
+    writes the parameters without moving ``_version``, and every optimizer step, every training forward of a module of this
+    build, ``EMA.swap`` and ``load_checkpoint`` announce themselves there (the packed conv operands obey the same signal)."""
+
+    def __init__(self):
+        self.key, self.buf = None, None
+
+    def get(self, weight):
+        key = (weight.data_ptr(), weight._version, convops.packed_weights_generation(), tuple(weight.shape), weight.device)
+        if self.key != key:
+            v, c = weight.shape
+            lib = N.lib()
+            need = max(int(lib.smt_vqtts_code_head_workspace_bytes(c, v)), 16)
+            if self.buf is None or self.buf.numel() < need or self.buf.device != weight.device:
+                self.buf = torch.empty(need, dtype=torch.uint8, device=weight.device)
+            N.check(lib.smt_vqtts_code_head_prepare(N.ptr(weight), c, v, N.ptr(self.buf), self.buf.numel(), N.stream_ptr()),
+                    "smt_vqtts_code_head_prepare")
+            self.key = key
+        return self.buf
+
+
+def _split_of(weight, split):
+    """Without a ``WeightSplit`` of the caller's the weight is split for this call alone (one small launch)."""
+    return (split if split is not None else WeightSplit()).get(weight)
+
+
+def _head_args(h, weight, bias):
+    h, weight, bias = _f(h), _f(weight.reshape(weight.shape[0], -1)), _f(bias)
+    v, c = weight.shape
+    assert h.shape[-1] == c and bias.shape == (v,), "h [..., C], weight [V, C] (or [V, C, 1]) and bias [V]"
+    return h, weight, bias, h.numel() // c if c else 0, c, v
+
+
+def _head_fwd(h, weight, bias, target, want_lse, split=None):
+    h, weight, bias, n, c, v = _head_args(h, weight, bias)
+    ws = _split_of(weight.detach(), split)
+    dev = h.device
+    pred = torch.empty(n, dtype=torch.int32, device=dev)
+    lse = torch.empty(n, device=dev) if want_lse or target is not None else None
+    row_loss = correct = sums = None
+    if target is not None:
+        assert target.dtype == torch.int64 and target.numel() == n and target.is_cuda
+        target = target.reshape(n).contiguous()
+        row_loss, correct = torch.empty(n, device=dev), torch.empty(n, device=dev)
+        # three sums, then the partial sums of the reduce's first stage; no rows: no target pointer, the sums are zero
+        sums = (torch.empty if n else torch.zeros)(3 + 3 * CH_SUM_PARTS, dtype=torch.float64, device=dev)
+    with profiler.region("vqtts_code_head:fwd", flops=6.0 * n * c * v, bound="mfma", dtype="bf16"):
+        N.check(N.lib().smt_vqtts_code_head_fwd(N.ptr(h), N.ptr(ws), ws.numel(), N.ptr(bias), N.ptr(target), n, c, v, N.ptr(lse),
+                                                N.ptr(row_loss), N.ptr(pred), N.ptr(correct), N.ptr(sums), N.stream_ptr()),
+                "smt_vqtts_code_head_fwd")
+    return h, weight, bias, target, ws, lse, row_loss, correct, sums, pred
+
+
+class _CodeHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, weight, bias, target, split):
+        shape = h.shape[:-1]
+        h2, w2, bias, target, ws, lse, row_loss, _, sums, pred = _head_fwd(h, weight, bias, target, True, split)
+        count = sums[2]
+        denom = torch.clamp(count, min=1.0)
+        loss = (sums[0] / denom).float()
+        acc = (sums[1] / denom).float()
+        ctx.save_for_backward(h2, w2, bias, target, lse, denom, ws)
+        ctx.shapes = (h.shape, weight.shape)
+        pred = pred.view(shape)
+        count = count.to(torch.int64)
+        ctx.mark_non_differentiable(acc, count, pred)
+        return loss, acc, count, pred
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        h, weight, bias, target, lse, denom, ws = ctx.saved_tensors
+        n, c = h.numel() // h.shape[-1], h.shape[-1]
+        v = weight.shape[0]
+        coef = (g.double() / denom).float().reshape(1).contiguous()
+        dh, dw, db = torch.empty_like(h), torch.empty_like(weight), torch.empty_like(bias)
+        lib = N.lib()
+        scratch = N.workspace.get(max(int(lib.smt_vqtts_code_head_bwd_workspace_bytes(n, c, v)), 16), h.device)
+        with profiler.region("vqtts_code_head:bwd", flops=18.0 * n * c * v, bound="mfma", dtype="bf16"):
+            N.check(lib.smt_vqtts_code_head_bwd(N.ptr(h), N.ptr(ws), ws.numel(), N.ptr(bias), N.ptr(target), N.ptr(lse), N.ptr(coef), n,
+                                                c, v, N.ptr(dh), N.ptr(dw), N.ptr(db), N.ptr(scratch), scratch.numel(),
+                                                N.stream_ptr()), "smt_vqtts_code_head_bwd")
+        h_shape, w_shape = ctx.shapes
+        return dh.view(h_shape), dw.view(w_shape), db, None, None
+
+
+def code_head(h, weight, bias, target, split=None):
+    """(loss, accuracy, count, pred): the mean over the rows with ``target >= 0`` of the cross-entropy of
+    ``h @ weight.T + bias`` against ``target``, the share of those rows whose argmax is the target, their number (int64)
+    and the argmax of every row (int32, lowest index on ties) -- ``F.cross_entropy(quant_proj(y_qh), y_q)`` and ``q_acc`` of
+    the reference without the logits.  h [..., C] fp32, weight [V, C] or the conv layout [V, C, 1], target int64 of h's
+    leading shape; no rows give loss 0 and count 0.  Gradients to h, weight and bias; the other three results are not
+    differentiable.  ``split``: the owner's ``WeightSplit`` (the split is then kept until the weight changes)."""
+    return _CodeHead.apply(h, weight, bias, target, split)
+
+
+@torch.no_grad()
+def code_head_predict(h, weight, bias, split=None):
+    """pred [...] int32 = argmax of ``h @ weight.T + bias`` over the bins, lowest index on ties (the synthesis form)."""
+    shape = h.shape[:-1]
+    return _head_fwd(h, weight, bias, None, False, split)[-1].view(shape)
