@@ -231,6 +231,21 @@ int smt_vqtts_code_head_bwd(const float* h, const void* workspace, size_t worksp
                             const int64_t* target, const float* lse, const float* coef, int64_t rows, int channels, int bins,
                             float* dh, float* dweight, float* dbias, void* scratch, size_t scratch_bytes, smt_stream_t stream);
 
+/* ------------------------------------------------------ VQTTS code emission ---- */
+/* The synthesis side of the grouped bottleneck (models/vqtts/vqtts.py:170-174; an addition to ABI 10): the predicted
+ * relative code of a frame becomes its absolute code and its codebook row.  pred [batch, t_q] int32 (the code head's
+ * argmax), x_id [batch, t_x] int64 token ids, idx [batch, t_q] int32 frame -> token (-1 = none), q_lens [batch] int32,
+ * codebook [n_vocab * l_bins, dim] fp32; outputs q_abs [batch, t_q] int64 (may be NULL) and y_d [batch, t_q, dim] fp32.
+ * Per frame (b, j): i = idx[b, j], tok = x_id[b, i], q = tok * l_bins + pred[b, j].  The frame HAS A CODE iff
+ * j < q_lens[b], 0 <= i < t_x, 0 <= tok < n_vocab and 0 <= pred[b, j] < l_bins.  With a code q_abs[b, j] = q and
+ * y_d[b, j, :] = codebook[q, :] bit for bit; without one q_abs[b, j] = -1 and the row is exactly 0.0f.  Nothing outside
+ * the arrays is read: x_id is not read when i is out of range, codebook is not read when the frame has no code.
+ * One launch on `stream`, no host synchronisation, no atomics, no workspace; equal inputs give equal bits.  dim must be
+ * a multiple of 4 and codebook / y_d 16-byte aligned (a row moves as 16-byte loads and stores) -- an argument error
+ * otherwise.  batch, t_q or dim of 0 is a no-op that returns 0. */
+int smt_vqtts_emit(const int* pred, const int64_t* x_id, const int* idx, const int* q_lens, const float* codebook, int batch,
+                   int t_x, int t_q, int n_vocab, int l_bins, int dim, int64_t* q_abs, float* y_d, smt_stream_t stream);
+
 /* ------------------------------------------------------------ conv stack ---- */
 /* Counter-based dropout ("dropout" spec).  The reference draws dropout masks from torch's global
  * RNG (models/vqvae/resnet.py:22,25), which no other device can reproduce; this build defines a
@@ -394,7 +409,9 @@ int smt_conv_gate_bwd(const void* dy, int64_t bs_dy, int ld_dy, const void* g, i
                       void* workspace, size_t workspace_bytes, smt_stream_t stream);
 
 /* sum_d tanh(t_d) * softmax_d(s_d) over `depth` branches laid side by side along the channel axis
- * (z[.., d*2w + c] = t_d, z[.., d*2w + w + c] = s_d) -- GatedHiFiBlock.forward, resnet.py:229-237. */
+ * (z[.., d*2w + c] = t_d, z[.., d*2w + w + c] = s_d) -- GatedHiFiBlock.forward, resnet.py:229-237.  depth <= 8.  The
+ * backward exchanges the softmax statistics between lanes when depth and width / (16 bytes) are powers of two whose
+ * product divides 64, and holds all branches in one lane otherwise (three branches: VQTTS). */
 int smt_gate_mix_fwd(const void* z, void* g, int dtype, int64_t rows, int width, int depth, int ld_z, int ld_g,
                      smt_stream_t stream);
 int smt_gate_mix_bwd(const void* z, const void* dg, void* dz, int dtype, int64_t rows, int width, int depth,

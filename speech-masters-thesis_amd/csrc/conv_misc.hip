@@ -141,6 +141,62 @@ __global__ __launch_bounds__(256) void gate_mix_bwd_kernel(const T* __restrict__
   }
 }
 
+// Backward for the geometries the shuffle kernel above cannot take (depth not a power of two -- VQTTS runs three branches --
+// or depth * w / EPV no divisor of 64): one lane per (row, channel vector) holds all branches, as the forward does.
+template <typename T>
+__global__ __launch_bounds__(256) void gate_mix_bwd_rows_kernel(const T* __restrict__ z, const T* __restrict__ dg,
+                                                                T* __restrict__ dz, long long rows, int w, int depth, int ldz,
+                                                                int ldg, int lddz) {
+  constexpr int EPV = Tr<T>::EPV;
+  const int vpr = w / EPV;
+  const long long total = rows * vpr;
+  for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < total; f += (long long)gridDim.x * 256) {
+    const long long row = f / vpr;
+    const int c = (int)(f % vpr) * EPV;
+    float th[GM_MAX_DEPTH][EPV], sv[GM_MAX_DEPTH][EPV];
+#pragma unroll
+    for (int d = 0; d < GM_MAX_DEPTH; ++d) {
+      if (d < depth) {
+        Vec<T, EPV> a = *reinterpret_cast<const Vec<T, EPV>*>(z + row * ldz + d * 2 * w + c);
+        Vec<T, EPV> b = *reinterpret_cast<const Vec<T, EPV>*>(z + row * ldz + d * 2 * w + w + c);
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) { th[d][e] = gate_tanh((float)a.v[e]); sv[d][e] = (float)b.v[e]; }
+      }
+    }
+    const Vec<T, EPV> gv = *reinterpret_cast<const Vec<T, EPV>*>(dg + row * ldg + c);
+    float inv[EPV], dot[EPV];
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) {
+      float m = -INFINITY;
+#pragma unroll
+      for (int d = 0; d < GM_MAX_DEPTH; ++d) if (d < depth) m = fmaxf(m, sv[d][e]);
+      float den = 0.f, num = 0.f;
+#pragma unroll
+      for (int d = 0; d < GM_MAX_DEPTH; ++d) if (d < depth) {
+        sv[d][e] = __expf(sv[d][e] - m);
+        den += sv[d][e];
+        num += sv[d][e] * th[d][e];
+      }
+      inv[e] = 1.f / den;
+      dot[e] = num * inv[e];                       // sum_d softmax_d * tanh_d
+    }
+#pragma unroll
+    for (int d = 0; d < GM_MAX_DEPTH; ++d) {
+      if (d < depth) {
+        Vec<T, EPV> dt, ds;
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) {
+          const float gs = (float)gv.v[e] * sv[d][e] * inv[e];
+          dt.v[e] = (T)(gs * (1.f - th[d][e] * th[d][e]));
+          ds.v[e] = (T)(gs * (th[d][e] - dot[e]));
+        }
+        *reinterpret_cast<Vec<T, EPV>*>(dz + row * lddz + d * 2 * w + c) = dt;
+        *reinterpret_cast<Vec<T, EPV>*>(dz + row * lddz + d * 2 * w + w + c) = ds;
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ conv_in -----
 // y[b,t,co] = bias[co] + sum_j x[b, t*s + j - pad] * w[co][j];  x fp32 [B,Tin], rows >= lens[b] read 0
 template <typename T>
@@ -401,8 +457,18 @@ extern "C" int smt_gate_mix_bwd(const void* z, const void* dg, void* dz, int dty
                     ld_dz % epv == 0, "smt_gate_mix_bwd: bad geometry");
   if (rows == 0) return 0;
   const int lpr = (width / epv) * depth;
-  SMT_CHECK_ARG((depth & (depth - 1)) == 0 && lpr <= 64 && 64 % lpr == 0 && ((width / epv) & (width / epv - 1)) == 0,
-                "smt_gate_mix_bwd: depth and width/%d must be powers of two with depth*width/%d <= 64", epv, epv);
+  if (!((depth & (depth - 1)) == 0 && lpr <= 64 && 64 % lpr == 0 && ((width / epv) & (width / epv - 1)) == 0)) {
+    // no lane-per-branch layout inside a wave for this geometry: the lane-per-channel-vector kernel takes any depth <= 8
+    unsigned rows_grid = ew_grid(rows * (width / epv));
+    if (dtype == SMT_BF16)
+      gate_mix_bwd_rows_kernel<__bf16><<<rows_grid, 256, 0, stream>>>((const __bf16*)z, (const __bf16*)dg, (__bf16*)dz, rows, width,
+                                                                     depth, ld_z, ld_g, ld_dz);
+    else
+      gate_mix_bwd_rows_kernel<float><<<rows_grid, 256, 0, stream>>>((const float*)z, (const float*)dg, (float*)dz, rows, width, depth,
+                                                                    ld_z, ld_g, ld_dz);
+    SMT_CHECK_LAUNCH("gate_mix_bwd");
+    return 0;
+  }
   unsigned grid = ew_grid(rows * lpr);
   if (dtype == SMT_BF16 && width == 64 && depth == 4)      // the reference configuration: four branches of width 64
     gate_mix_bwd_kernel<__bf16, 8, 4><<<grid, 256, 0, stream>>>((const __bf16*)z, (const __bf16*)dg, (__bf16*)dz, rows, width,

@@ -84,3 +84,52 @@ class SyntheticTTS(Dataset):
         return token, tx, spect, ty, None, None, None
 
     collate = staticmethod(LJSpeech.collate)
+
+
+class SyntheticTTSAudio(Dataset):
+    """Token ids + a waveform that depends on them, for the token-to-waveform models (VQTTS): item = (token [Tx] int64, Tx,
+    None, None, audio [T] fp32, T, None), T a multiple of TRUNC_MOD.  Every token id owns an f0 in [90, 250] Hz; the clip is
+    cut into Tx segments of drawn lengths (each at least ``min_segment`` samples, so that every token keeps more than one
+    frame of a x256 encoder) and a segment is ``synth_clip``'s signal at its token's f0: eight harmonics with the clip's
+    phases, continuous in time, plus the clip's noise.  So an alignment exists to be found, and it is not uniform."""
+
+    def __init__(self, config, split):
+        super().__init__()
+        ds = config.dataset
+        self.n = int(ds.get("num_clips", 256)) if split == "train" else 10
+        self.offset = 0 if split == "val" else 10
+        self.fixed_length = int(ds.get("clip_length", 145408))
+        self.ragged = bool(ds.get("ragged", False))
+        self.sample_rate = int(ds.get("sample_rate", 22050))
+        self.max_tokens = int(ds.get("max_tokens", 160))
+        self.min_segment = int(ds.get("min_segment", 512))
+        self.n_vocab = int(ds.get("n_vocab", 148)) + int(bool(ds.get("intersperse_blanks", False)))
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, index):
+        seed = self.offset + index
+        g = torch.Generator().manual_seed(70_000 + seed)
+        length = self.fixed_length
+        if self.ragged:
+            length = int(torch.randint(24064, 222720 + 1, (1,), generator=g))
+        length -= length % TRUNC_MOD
+        tx_max = max(1, min(self.max_tokens, length // self.min_segment))
+        tx = int(torch.randint(max(1, tx_max // 2), tx_max + 1, (1,), generator=g))
+        token = torch.randint(1, self.n_vocab, (tx,), generator=g)
+        # segment lengths: min_segment each, the rest of the clip shared out in proportion to drawn weights
+        w = 0.25 + torch.rand(tx, generator=g, dtype=torch.float64)
+        ends = torch.round(torch.cumsum(w, 0) / w.sum() * (length - tx * self.min_segment)).long()
+        ends = ends + self.min_segment * torch.arange(1, tx + 1)
+        ends[-1] = length
+        owner = torch.searchsorted(ends, torch.arange(length), right=True).clamp(max=tx - 1)
+        f0 = 90.0 + 160.0 * token.double() / max(self.n_vocab - 1, 1)
+        phi = 2 * math.pi * torch.rand(8, generator=g, dtype=torch.float64)
+        phase = 2 * math.pi * torch.cumsum(f0[owner], 0) / self.sample_rate          # continuous across segment borders
+        tone = sum(torch.sin(h * phase + phi[h - 1]) / h for h in range(1, 9))
+        noise = torch.rand(length, generator=g, dtype=torch.float64) * 2 - 1
+        audio = (0.5 * (0.6 * tone + 0.4 * noise)).clamp(-1, 1).to(torch.float32)
+        return token, tx, None, None, audio, length, None
+
+    collate = staticmethod(LJSpeech.collate)

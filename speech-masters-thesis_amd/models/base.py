@@ -6,6 +6,7 @@ speaker)`` onto ``forward`` and returning ``(loss_dict, metrics_dict)``.
 utils/commons.get_model and the validation artefact type in train.py, so the
 class names and the slot mapping are part of the drop-in contract.
 """
+import torch
 import torch.nn as nn
 
 _SLOTS = ("token", "token_len", "spect", "spect_len", "audio", "audio_len", "speaker")
@@ -41,3 +42,33 @@ class TokenToSpectrogramModel(_SlotModel):
 
 class SpectrogramReconstructionModel(_SlotModel):
     inputs, target = ("spect", "spect_len"), "spect"
+
+
+def token_batch(x, x_lengths, n_vocab):
+    """The checks of a synthesis call's token ids, shared by ``GlowTTS.infer`` and ``VQTTS.infer``: x [B, Tx] integer ids with
+    B >= 1, x_lengths [B] integers in [1, Tx] (None = full width), every id inside its length in [0, n_vocab) -- ValueError
+    otherwise, on the host, as the ids come from outside the program.  Returns (ids int64 [B, Tx], lengths int64 [B], valid
+    bool [B, Tx]), all on the CPU."""
+    x = torch.as_tensor(x).detach()
+    if x.dim() != 2 or x.shape[0] == 0:
+        raise ValueError(f"x must be token ids [B, Tx] with B >= 1, got shape {tuple(x.shape)}")
+    b, tx = x.shape
+    if x_lengths is None:
+        lens = torch.full((b,), tx, dtype=torch.int64)
+    else:
+        lens = torch.as_tensor(x_lengths).detach().cpu()
+        if lens.shape != (b,) or lens.is_floating_point() or lens.is_complex():
+            raise ValueError(f"x_lengths must be {b} integers, got {lens.dtype} of shape {tuple(lens.shape)}")
+        lens = lens.long()
+    for i, n in enumerate(lens.tolist()):
+        if not 1 <= n <= tx:
+            raise ValueError(f"item {i} has {n} tokens: every item needs 1 to {tx} (the width of x)")
+    if x.is_floating_point() or x.is_complex() or x.dtype == torch.bool:
+        raise ValueError(f"x must hold integer token ids, got {x.dtype}")
+    xc = x.cpu().long()
+    valid = torch.arange(tx)[None, :] < lens[:, None]
+    bad = valid & ((xc < 0) | (xc >= n_vocab))
+    if bad.any():
+        i, t = (int(v) for v in bad.nonzero()[0])
+        raise ValueError(f"item {i}, token {t}: id {int(xc[i, t])} is outside [0, {n_vocab})")
+    return xc, lens, valid

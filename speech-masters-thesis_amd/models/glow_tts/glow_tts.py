@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 import models.glow_tts.submodules as submodules
-from models.base import TokenToSpectrogramModel
+from models.base import TokenToSpectrogramModel, token_batch
 from models.glow_tts.modules import FlowSpecDecoder, TextEncoder
 from smt_amd import glow
 
@@ -118,28 +118,8 @@ class GlowTTS(TokenToSpectrogramModel):
             raise ValueError(f"noise_scale must be a finite number >= 0, got {noise_scale}")
         dev, n_vocab = self.encoder.emb.weight.device, self.encoder.emb.num_embeddings
         n_mels, n_sqz = self.decoder.flows[0].channels // self.decoder.n_sqz, self.decoder.n_sqz
-        x = torch.as_tensor(x).detach()
-        if x.dim() != 2 or x.shape[0] == 0:
-            raise ValueError(f"x must be token ids [B, Tx] with B >= 1, got shape {tuple(x.shape)}")
-        b, tx = x.shape
-        if x_lengths is None:
-            lens = torch.full((b,), tx, dtype=torch.int64)
-        else:
-            lens = torch.as_tensor(x_lengths).detach().cpu()
-            if lens.shape != (b,) or lens.is_floating_point() or lens.is_complex():
-                raise ValueError(f"x_lengths must be {b} integers, got {lens.dtype} of shape {tuple(lens.shape)}")
-            lens = lens.long()
-        for i, n in enumerate(lens.tolist()):
-            if not 1 <= n <= tx:
-                raise ValueError(f"item {i} has {n} tokens: every item needs 1 to {tx} (the width of x)")
-        if x.is_floating_point() or x.is_complex() or x.dtype == torch.bool:
-            raise ValueError(f"x must hold integer token ids, got {x.dtype}")
-        xc = x.cpu().long()
-        valid = torch.arange(tx)[None, :] < lens[:, None]
-        bad = valid & ((xc < 0) | (xc >= n_vocab))
-        if bad.any():
-            i, t = (int(v) for v in bad.nonzero()[0])
-            raise ValueError(f"item {i}, token {t}: id {int(xc[i, t])} is outside [0, {n_vocab})")
+        xc, lens, valid = token_batch(x, x_lengths, n_vocab)
+        b, tx = xc.shape
         if noise is not None and (noise.dim() != 3 or tuple(noise.shape[:2]) != (b, n_mels)):
             raise ValueError(f"noise must be [B={b}, n_mels={n_mels}, T_out], got shape {tuple(noise.shape)}")
 

@@ -1,4 +1,5 @@
-"""Mel spectrograms from token ids with a trained GlowTTS (the reference's `GlowTTS.infer_step`, batched).
+"""Synthesis from token ids with a trained token-to-spectrogram or token-to-waveform model (the reference's `infer_step`,
+batched): mel spectrograms from a GlowTTS, waveforms from a VQTTS.
 
     python -m scripts.synthesize --log_dir ./logs/glow_tts --ckpt_num 5000 --tokens utterances.txt --dump_dir ./outputs \
         [--batch_size 16] [--noise_scale 0.667] [--length_scale 1.0] [--seed 0]
@@ -6,7 +7,11 @@
 ``--tokens`` holds one utterance per line as whitespace-separated integer ids (the ids of datasets/synthetic.py, and the ones
 the reference's CMUDict parser would emit; the text front end itself is not built).  Writes
 ``<dump_dir>/<ModelClass>@<ckpt>/mel_<i>.npy`` (float32 [n_mels, frames], trimmed to the utterance's length) and one
-``mel_spectrograms.png``.  Synthesis runs on MI355X through libsmt_hip.so (`GlowTTS.infer`); there is no vocoder."""
+``mel_spectrograms.png``.  Synthesis runs on MI355X through libsmt_hip.so (`GlowTTS.infer`); there is no vocoder.
+
+A token-to-waveform model (VQTTS, `VQTTS.infer`) writes ``wav_<i>.wav`` (16-bit mono at the dataset's sample rate, trimmed to
+the utterance's length) and the log-mel spectrograms of the waveforms as ``mel_spectrograms.png``; it has no prior noise,
+so ``--noise_scale`` other than 1 is refused for it."""
 import argparse
 import logging
 import os
@@ -17,7 +22,7 @@ import torch
 from scripts.sample_from_lm import mel_grid
 from utils import config as cfglib
 from utils.commons import get_model
-from utils.train_utils import write_png_gray
+from utils.train_utils import write_png_gray, write_wav
 
 logger = logging.getLogger(__name__)
 
@@ -45,12 +50,51 @@ def read_tokens(path):
         raise ValueError(f"{path}: every line must hold whitespace-separated integer token ids ({e})") from None
 
 
+def batches(utterances, batch_size):
+    """(padded ids [B, Tx] int64, lengths [B]) per batch."""
+    for lo in range(0, len(utterances), batch_size):
+        part = utterances[lo:lo + batch_size]
+        x = torch.zeros(len(part), max(len(t) for t in part), dtype=torch.int64)
+        for i, t in enumerate(part):
+            x[i, :len(t)] = torch.tensor(t, dtype=torch.int64)
+        yield x, torch.tensor([len(t) for t in part])
+
+
+def draw_mels(dump_dir, mels):
+    drawn = [m for m in mels if m.shape[1] > 0]
+    if drawn:
+        width = max(m.shape[1] for m in drawn)
+        write_png_gray(os.path.join(dump_dir, "mel_spectrograms.png"),
+                       mel_grid([np.pad(m, ((0, 0), (0, width - m.shape[1])), constant_values=m.min()) for m in drawn]))
+
+
+def synthesize_waveforms(model, config, utterances, args, dump_dir, device):
+    """The token-to-waveform branch: wav files and the log-mel image of what was synthesized."""
+    from datasets.transforms import MelSpectrogram
+    if args.noise_scale != 1.0:
+        raise ValueError(f"--noise_scale applies to GlowTTS's prior; {type(model).__name__} has no noise input")
+    ds = config.dataset
+    mel = MelSpectrogram(sample_rate=ds.sample_rate, n_fft=ds.n_fft, win_length=ds.win_length, hop_length=ds.hop_length,
+                         n_mels=ds.n_mels, f_min=0.0, f_max=8000.0).to(device)
+    mels, count = [], 0
+    for x, x_lengths in batches(utterances, args.batch_size):
+        wave, wave_lengths = model.infer(x, x_lengths, length_scale=args.length_scale)
+        for i, n in enumerate(wave_lengths.tolist()):
+            write_wav(os.path.join(dump_dir, f"wav_{count}.wav"), wave[i, :n].clamp(-1, 1).cpu().numpy(), ds.sample_rate)
+            count += 1
+            if n >= ds.n_fft:
+                mels.append(mel(wave[i:i + 1, :n].clamp(-1, 1))[0].cpu().numpy())
+    draw_mels(dump_dir, mels)
+    logger.info("Saved %d waveforms under %s", count, dump_dir)
+    return dump_dir
+
+
 def main(argv=None):
     args = parse_args(argv)
     if args.batch_size < 1:
         raise ValueError("--batch_size must be >= 1")
     if not torch.cuda.is_available():
-        raise RuntimeError("synthesize runs GlowTTS on MI355X (libsmt_hip.so); no GPU is visible")
+        raise RuntimeError("synthesize runs the model on MI355X (libsmt_hip.so); no GPU is visible")
     utterances = read_tokens(args.tokens)
     if not utterances:
         raise ValueError(f"{args.tokens} holds no utterance")
@@ -64,24 +108,18 @@ def main(argv=None):
     dump_dir = os.path.join(args.dump_dir, f"{type(model).__name__}@{args.ckpt_num}")
     os.makedirs(dump_dir, exist_ok=True)
 
+    from models.base import TokenToWaveformModel
+    if isinstance(model, TokenToWaveformModel):
+        return synthesize_waveforms(model, config, utterances, args, dump_dir, device)
     torch.manual_seed(args.seed)
     mels = []
-    for lo in range(0, len(utterances), args.batch_size):
-        part = utterances[lo:lo + args.batch_size]
-        x = torch.zeros(len(part), max(len(t) for t in part), dtype=torch.int64)
-        for i, t in enumerate(part):
-            x[i, :len(t)] = torch.tensor(t, dtype=torch.int64)
-        yh, y_lengths = model.infer(x, torch.tensor([len(t) for t in part]), noise_scale=args.noise_scale,
-                                    length_scale=args.length_scale)
+    for x, x_lengths in batches(utterances, args.batch_size):
+        yh, y_lengths = model.infer(x, x_lengths, noise_scale=args.noise_scale, length_scale=args.length_scale)
         yh = yh.cpu().numpy()
         mels += [np.ascontiguousarray(yh[i, :, :n], dtype=np.float32) for i, n in enumerate(y_lengths.tolist())]
     for i, m in enumerate(mels):
         np.save(os.path.join(dump_dir, f"mel_{i}.npy"), m)
-    drawn = [m for m in mels if m.shape[1] > 0]
-    if drawn:
-        width = max(m.shape[1] for m in drawn)
-        write_png_gray(os.path.join(dump_dir, "mel_spectrograms.png"),
-                       mel_grid([np.pad(m, ((0, 0), (0, width - m.shape[1])), constant_values=m.min()) for m in drawn]))
+    draw_mels(dump_dir, mels)
     logger.info("Saved %d spectrograms under %s", len(mels), dump_dir)
     return dump_dir
 

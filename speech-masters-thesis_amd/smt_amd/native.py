@@ -85,6 +85,7 @@ _SIGNATURES = {
     "smt_vqtts_code_head_bwd_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
     "smt_vqtts_code_head_bwd": (c_int, [c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr,
                                         c_ptr, c_size, c_ptr]),
+    "smt_vqtts_emit": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
     "smt_recon_loss_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
     "smt_recon_loss_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
     "smt_stft_num_frames": (c_int, [c_int, c_int, c_int]),

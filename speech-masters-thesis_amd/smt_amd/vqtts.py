@@ -4,7 +4,10 @@ channels-last rows [B, T, D], prefix masks as int32 lengths on the device, no ho
 Reference: models/vqtts/vqtts.py:133-137, 150-156.
 
 The code head ("VQTTS code head" of the header, csrc/vqtts_codes.hip): the projection to l_bins logits fused with the
-cross-entropy or the argmax -- reference models/vqtts/vqtts.py:144, 157, 176, 190."""
+cross-entropy or the argmax -- reference models/vqtts/vqtts.py:144, 157, 176, 190.
+
+The code emission ("VQTTS code emission", csrc/vqtts_emit.hip): predicted code -> absolute code and codebook row, the
+synthesis side of the grouped bottleneck -- reference models/vqtts/vqtts.py:170-174."""
 import torch
 
 from . import convops
@@ -204,3 +207,37 @@ def code_head_predict(h, weight, bias, split=None):
     """pred [...] int32 = argmax of ``h @ weight.T + bias`` over the bins, lowest index on ties (the synthesis form)."""
     shape = h.shape[:-1]
     return _head_fwd(h, weight, bias, None, False, split)[-1].view(shape)
+
+
+# --------------------------------------------------------------------------------------------------- code emission
+@torch.no_grad()
+def emit_codes(pred, x_id, align_idx, q_lens, codebook, n_vocab, l_bins):
+    """(y_d [B, Tq, D] fp32, q_abs [B, Tq] int64): frame (b, j) with a code -- j < q_lens[b], a token index in
+    [0, Tx), a token id in [0, n_vocab) and pred in [0, l_bins) -- gets q_abs = token * l_bins + pred and the codebook row
+    of it, every other frame -1 and an exactly zero row ("VQTTS code emission" of the header, csrc/vqtts_emit.hip).  One
+    launch for ``CodePredictor.synthesize_codes`` -> ``Bottleneck.decode`` -> the length mask.  pred [B, Tq] int32,
+    x_id [B, Tx] int64, align_idx [B, Tq] int32, q_lens [B] int32, codebook [n_vocab * l_bins, D] fp32 with D % 4 == 0;
+    anything else raises ValueError before the launch."""
+    def need(cond, what):
+        if not cond:
+            raise ValueError(f"emit_codes: {what}")
+    for name, t, dtype, dim in (("pred", pred, torch.int32, 2), ("x_id", x_id, torch.int64, 2), ("align_idx", align_idx, torch.int32, 2),
+                                ("q_lens", q_lens, torch.int32, 1), ("codebook", codebook, torch.float32, 2)):
+        need(isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == dim and t.is_cuda,
+             f"{name} must be a {dim}-D {dtype} device tensor, got "
+             f"{(t.dtype, tuple(t.shape), t.device.type) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    b, tq = pred.shape
+    tx, (rows, d) = x_id.shape[1], codebook.shape
+    need(x_id.shape[0] == b and tuple(align_idx.shape) == (b, tq) and tuple(q_lens.shape) == (b,),
+         f"pred {tuple(pred.shape)}, x_id {tuple(x_id.shape)}, align_idx {tuple(align_idx.shape)} and q_lens {tuple(q_lens.shape)} "
+         "do not agree on [B, Tq] / [B, Tx] / [B]")
+    need(n_vocab >= 0 and l_bins >= 0 and rows == n_vocab * l_bins, f"codebook has {rows} rows, n_vocab * l_bins = {n_vocab * l_bins}")
+    need(d % 4 == 0, f"the code width {d} is not a multiple of 4")
+    dev = codebook.device
+    y_d = torch.empty(b, tq, d, device=dev)
+    q_abs = torch.empty(b, tq, dtype=torch.int64, device=dev)
+    pred, x_id, align_idx, q_lens, codebook = (t.detach().contiguous() for t in (pred, x_id, align_idx, q_lens, codebook))
+    with profiler.region("vqtts_emit", nbytes=2 * y_d.numel() * 4, bound="hbm"):
+        N.check(N.lib().smt_vqtts_emit(N.ptr(pred), N.ptr(x_id), N.ptr(align_idx), N.ptr(q_lens), N.ptr(codebook), b, tx, tq, n_vocab,
+                                       l_bins, d, N.ptr(q_abs), N.ptr(y_d), N.stream_ptr()), "smt_vqtts_emit")
+    return y_d, q_abs

@@ -94,15 +94,21 @@ def save_checkpoint(config, global_step, epoch, model, ema, optimizer, scheduler
     return path
 
 
+def _codebooks(model):
+    """(state name, block) of every EMA codebook of a model: the VQ-VAE's per-level blocks, VQTTS's grouped one."""
+    blocks = [(f"bottleneck.level_blocks.{i}", blk) for i, blk in enumerate(getattr(getattr(model, "bottleneck", None), "level_blocks", []))]
+    if hasattr(model, "quant_bottleneck"):
+        blocks.append(("quant_bottleneck", model.quant_bottleneck))
+    return blocks
+
+
 def extra_train_state(model):
     """Training state that lives outside ``state_dict()``: per codebook ``k_sum`` / ``k_elem`` / ``init``, and the
     dropout step counter."""
     out = {}
-    bottleneck = getattr(model, "bottleneck", None)
-    for i, blk in enumerate(getattr(bottleneck, "level_blocks", [])):
+    for name, blk in _codebooks(model):
         if getattr(blk, "init", False) and blk.k_sum is not None:
-            out[f"bottleneck.level_blocks.{i}"] = {"k_sum": blk.k_sum.detach().clone(), "k_elem": blk.k_elem.detach().clone(),
-                                                   "threshold": float(blk.threshold)}
+            out[name] = {"k_sum": blk.k_sum.detach().clone(), "k_elem": blk.k_elem.detach().clone(), "threshold": float(blk.threshold)}
     if hasattr(model, "_drop_seed"):
         out["drop_seed"] = int(model._drop_seed)
     return out
@@ -113,9 +119,8 @@ def restore_extra_train_state(model, extra):
     that was trained (non-zero ``k``) is kept with ``restore_k()`` (bottleneck.py:48-58) instead of being re-drawn from
     the first batch, which is what the reference's resume path silently does (``init`` is False after loading)."""
     extra = extra or {}
-    bottleneck = getattr(model, "bottleneck", None)
-    for i, blk in enumerate(getattr(bottleneck, "level_blocks", [])):
-        st = extra.get(f"bottleneck.level_blocks.{i}")
+    for name, blk in _codebooks(model):
+        st = extra.get(name)
         if st is not None:
             blk.k_sum = st["k_sum"].to(blk.k.device, torch.float32).clone()
             blk.k_elem = st["k_elem"].to(blk.k.device, torch.float32).clone()

@@ -2,7 +2,7 @@
 0.4 s -- at least 20 calls -- per line, everything in ONE process).
 
 C = 128 channels, V = 512 bins, a tenth of the rows unscored, at two sizes:
-  * N = 581,632 rows (B = 32 items of 18,176 frames, the training clip at stride 8);
+  * N = 581,632 rows (B = 32 items of 18,176 frames: the 145,408-sample clip at stride 8, the largest shape the head is sized for);
   * N = 36,352 rows (two such items).
 The fused ``vqtts.code_head`` (forward, and forward + backward to h, weight and bias) beside the unfused path on the same
 device, ``F.linear`` followed by ``smt_amd.lm.cross_entropy``, which writes the [N, V] logits and their gradient.  It

@@ -2,7 +2,7 @@
 everything in ONE process).
 
 Two shapes with ragged lengths, D = 128, B = 32:
-  * large  Tx 200, Tq 18,176 (the 145,408-sample training clip at stride 8): the fused ``vqtts.align``, and as the CPU leg
+  * large  Tx 200, Tq 18,176 (the 145,408-sample clip at stride 8, the largest lattice the search is sized for): the fused ``vqtts.align``, and as the CPU leg
     the numpy search of oracle/mas_oracle.py on ONE item's distance matrix (what the reference runs per item on the host);
   * small  Tx 150, Tq 800 (a GlowTTS-sized lattice): the fused ``vqtts.align`` beside the dense chain on the same device,
     ``vqtts.distance`` + ``smt_maximum_path`` + ``glow.align_index``.
