@@ -219,13 +219,31 @@ int smt_vqtts_align_loss_bwd(const float* x_enc, const float* y_enc, const int* 
  *   p = exp(logit - lse), G = coef (p - onehot(target)), 0 on unscored rows, and writes dh = G . weight [rows, channels],
  *   dweight = G^T . h [bins, channels], dbias = sum_r G; G's bf16 pair feeds the MFMAs the same way.  dweight / dbias:
  *   one slab per row slice in `scratch` (smt_vqtts_code_head_bwd_workspace_bytes), added in slice order in fp64 -- no
- *   float atomics, equal inputs give equal bits. */
+ *   float atomics, equal inputs give equal bits.
+ * sample (an addition to ABI 10): the synthesis form with a draw instead of the argmax.  rows = batch * t_q; row r is frame
+ *   j = r % t_q of item b = r / t_q; seeds [batch] int32 in device memory.  Per row, with the logits of fwd bit for bit:
+ *     key   = fmix32(fmix32((uint32)seeds[b]) + (uint32)j * 0x9E3779B1)          (fmix32 of the dropout spec below)
+ *     bits  = fmix32(key + (uint32)v * 0x85EBCA77)                               per bin v
+ *     u     = ((bits >> 9) + 0.5) * 2^-23                                        exact in fp32, strictly inside (0, 1)
+ *     g     = -logf(-logf(u))                                                    Gumbel noise
+ *     score = fmaf(logit, inv_temperature, g)
+ *     M = max_v logit_v;  bin v is KEPT iff logit_v >= M + cut (fp32)
+ *     pred  = the kept bin with the highest score, lowest index on ties;  n_kept = number of kept bins (may be NULL)
+ *   -- a sample of softmax(logit * inv_temperature) restricted to the bins with p_v / p_max >= min_p (min-p), where
+ *   cut = T ln(min_p) <= 0 is computed by the host in double and rounded once; cut = -inf keeps every bin (one sweep over
+ *   the weight; a finite cut takes two, and the maximum is always kept: n_kept >= 1).  A frame's draw depends on
+ *   (seeds[b], j, v) only, not on t_q, the batch position or the launch geometry.  inv_temperature finite and > 0,
+ *   t_q >= 1, rows % t_q == 0 -- an argument error otherwise.  One launch, no atomics, no workspace beyond the split;
+ *   equal inputs give equal bits.  rows == 0 launches nothing. */
 size_t smt_vqtts_code_head_workspace_bytes(int channels, int bins);
 int smt_vqtts_code_head_prepare(const float* weight, int channels, int bins, void* workspace, size_t workspace_bytes,
                                 smt_stream_t stream);
 int smt_vqtts_code_head_fwd(const float* h, const void* workspace, size_t workspace_bytes, const float* bias,
                             const int64_t* target, int64_t rows, int channels, int bins, float* lse, float* row_loss, int* pred,
                             float* correct, double* sums, smt_stream_t stream);
+int smt_vqtts_code_head_sample(const float* h, const void* workspace, size_t workspace_bytes, const float* bias,
+                               const int* seeds, int64_t rows, int t_q, int channels, int bins, float inv_temperature, float cut,
+                               int* pred, int* n_kept, smt_stream_t stream);
 size_t smt_vqtts_code_head_bwd_workspace_bytes(int64_t rows, int channels, int bins);
 int smt_vqtts_code_head_bwd(const float* h, const void* workspace, size_t workspace_bytes, const float* bias,
                             const int64_t* target, const float* lse, const float* coef, int64_t rows, int channels, int bins,

@@ -10,6 +10,9 @@
 //   ch_rows_kernel<true>   data gradient: the same logits (ch_logits2, the ONE place a logit is computed with V on the
 //                          accumulator), p = exp(logit - lse), G = coef (p - onehot); the G tile is the B operand of the
 //                          next MFMAs as it stands (it sums over V, the accumulator's row index): dh^T = W^T G.
+//   ch_sample_kernel<TRUNC> synthesis with a draw: the forward's geometry and logits; per logit a counter-based Gumbel noise,
+//                          the running argmax of logit / T + g is a sample of softmax(logit / T).  TRUNC (min-p): a first
+//                          sweep for the row maximum, the draw among the bins within `cut` of it in a second.
 //   ch_dw_kernel           weight gradient: one workgroup = CH_VCOLS columns of V and a slice of rows.  It recomputes its
 //                          columns' logits with the ROW on the accumulator's row index (same split, same three products in
 //                          the same order), so G sums over the accumulator's row index again: dW = G^T h with h^T staged
@@ -292,6 +295,115 @@ __global__ __launch_bounds__(256) void ch_rows_kernel(const float* __restrict__ 
           }
         }
     }
+  }
+}
+
+// ---- sampling ("VQTTS code head" of the header, smt_vqtts_code_head_sample) ---------------------------------------------
+constexpr unsigned CH_NOISE_ROW = 0x9E3779B1u;   // odd multiplier of the frame index in a row's key
+constexpr unsigned CH_NOISE_BIN = 0x85EBCA77u;   // ... of the bin index in a logit's counter
+
+// Gumbel noise of bin v under the row's key: u = ((bits >> 9) + 0.5) 2^-23 is exact in fp32 and strictly inside (0, 1)
+__device__ __forceinline__ float ch_gumbel(unsigned key, int v) {
+  const unsigned bits = fmix32(key + (unsigned)v * CH_NOISE_BIN);
+  const float u = ((float)(bits >> 9) + 0.5f) * 1.1920928955078125e-07f;
+  return -logf(-logf(u));
+}
+
+// The staging step of ch_rows_kernel: weight rows v0 .. v0 + CH_VT - 1 (zeros past V) into [hi | lo][CH_VT][PITCH].  A copy,
+// not a shared helper: factoring the loop out of ch_rows_kernel changes that kernel's register allocation.
+template <int CP>
+__device__ __forceinline__ void ch_stage_w(const __bf16* __restrict__ wh, const __bf16* __restrict__ wl, int v0, int V, int tid,
+                                           char* wt) {
+  constexpr int PITCH = 2 * CP + 16, TILE = CH_VT * PITCH;
+  for (int p = tid; p < CH_VT * (CP / 8); p += 256) {
+    const int r = p / (CP / 8), pc = p - r * (CP / 8);
+    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
+    if (v0 + r < V) {
+      a = *reinterpret_cast<const uint4*>(wh + (size_t)(v0 + r) * CP + 8 * pc);
+      b = *reinterpret_cast<const uint4*>(wl + (size_t)(v0 + r) * CP + 8 * pc);
+    }
+    *reinterpret_cast<uint4*>(wt + r * PITCH + 16 * pc) = a;
+    *reinterpret_cast<uint4*>(wt + TILE + r * PITCH + 16 * pc) = b;
+  }
+}
+
+// One draw per row from softmax(logit / T) by Gumbel-max, in the forward's geometry (one row per MFMA lane, V on the
+// accumulator's row index, the logits of ch_logits2 bit for bit).  TRUNC: a first sweep finds the row's maximum M, the second
+// recomputes the logits -- the same instructions on the same operands, so M itself is met again and kept -- and only the
+// bins with logit >= M + cut compete.  The winner is the kept bin with the highest score = fma(logit, 1/T, g), lowest index
+// on ties: ascending index inside a lane, the tie rule across the two lane halves.
+template <int CP, bool TRUNC>
+__global__ __launch_bounds__(256) void ch_sample_kernel(const float* __restrict__ h, const __bf16* __restrict__ wh,
+                                                        const __bf16* __restrict__ wl, const float* __restrict__ bias,
+                                                        const int* __restrict__ seeds, long long N, int t_q, int C, int V,
+                                                        float inv_t, float cut, int* __restrict__ pred, int* __restrict__ n_kept) {
+  using L = ChRowsLds<CP, false>;
+  constexpr int NS = CP / 16;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* bl = reinterpret_cast<float*>(smem);
+  char* wt = reinterpret_cast<char*>(smem) + L::WT;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, hf = lane >> 5;
+  const long long row = (long long)blockIdx.x * CH_ROWS + wave * 32 + j;
+  const long long rowc = row < N ? row : N - 1;                  // a row past the end reads the last one and stores nothing
+
+  vq_bf16x8 xh[NS], xl[NS];
+  ch_load_row<NS>(h, C, rowc, hf, xh, xl);
+  for (int i = tid; i < CH_MAX_V; i += 256) bl[i] = i < V ? bias[i] : 0.f;
+  const int item = (int)(rowc / t_q), frame = (int)(rowc - (long long)item * t_q);
+  const unsigned key = fmix32(fmix32((unsigned)seeds[item]) + (unsigned)frame * CH_NOISE_ROW);
+
+  const float NEG_INF = -__builtin_huge_valf();
+  float thr = NEG_INF;
+  if (TRUNC) {
+    float m = NEG_INF;
+    for (int v0 = 0; v0 < V; v0 += CH_VT) {
+      const bool two = v0 + CH_VT <= V;
+      __syncthreads();                                           // the previous tile is consumed
+      ch_stage_w<CP>(wh, wl, v0, V, tid, wt);
+      __syncthreads();
+      f32x16 acc[2];
+      ch_logits2<CP>(wt, bl + v0, j, hf, xh, xl, acc);
+#pragma unroll
+      for (int ch = 0; ch < 2; ++ch)
+        if (ch == 0 || two) {
+#pragma unroll
+          for (int q = 0; q < 16; ++q) m = fmaxf(m, acc[ch][q]);
+        }
+    }
+    thr = fmaxf(m, __shfl_xor(m, 32, 64)) + cut;
+  }
+
+  float best = NEG_INF;
+  int bidx = 0, kept = 0;
+  for (int v0 = 0; v0 < V; v0 += CH_VT) {
+    const bool two = v0 + CH_VT <= V;                            // V is a multiple of 32: the last tile may hold one chunk
+    __syncthreads();
+    ch_stage_w<CP>(wh, wl, v0, V, tid, wt);
+    __syncthreads();
+    f32x16 acc[2];
+    ch_logits2<CP>(wt, bl + v0, j, hf, xh, xl, acc);
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch)
+      if (ch == 0 || two) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {                           // ascending index inside a lane: '>' keeps the lowest
+          const int vi = v0 + 32 * ch + ch_accrow(q, hf);
+          const float a = acc[ch][q];
+          if (!TRUNC || a >= thr) {
+            const float s = fmaf(a, inv_t, ch_gumbel(key, vi));
+            ++kept;
+            if (s > best) { best = s; bidx = vi; }
+          }
+        }
+      }
+  }
+  // the two lane halves hold interleaved columns of the same row; a half that kept nothing stands at -inf
+  const float ob = __shfl_xor(best, 32, 64);
+  const int oi = __shfl_xor(bidx, 32, 64), ok = __shfl_xor(kept, 32, 64);
+  if (ob > best || (ob == best && oi < bidx)) bidx = oi;
+  if (hf == 0 && row < N) {
+    pred[row] = bidx;
+    if (n_kept) n_kept[row] = kept + ok;
   }
 }
 
@@ -611,6 +723,47 @@ extern "C" int smt_vqtts_code_head_fwd(const float* h, const void* workspace, si
     ch_fwd_final_kernel<<<1, CH_SUM_PARTS, 0, stream>>>(part, parts, sums);
     SMT_CHECK_LAUNCH("ch_fwd_final");
   }
+  return 0;
+}
+
+template <int CP, bool TRUNC>
+static void ch_launch_sample(hipStream_t stream, const float* h, const __bf16* ws, const float* bias, const int* seeds, long long N,
+                             int t_q, int C, int V, float inv_t, float cut, int* pred, int* n_kept) {
+  using L = ChRowsLds<CP, false>;
+  const size_t n = (size_t)V * CP;
+  static unsigned long long allowed = 0;
+  ch_allow_lds((const void*)ch_sample_kernel<CP, TRUNC>, L::TOTAL, &allowed);
+  ch_sample_kernel<CP, TRUNC><<<(unsigned)((N + CH_ROWS - 1) / CH_ROWS), 256, L::TOTAL, stream>>>(h, ws, ws + n, bias, seeds, N, t_q, C,
+                                                                                               V, inv_t, cut, pred, n_kept);
+}
+
+extern "C" int smt_vqtts_code_head_sample(const float* h, const void* workspace, size_t workspace_bytes, const float* bias,
+                                          const int* seeds, int64_t rows, int t_q, int channels, int bins, float inv_temperature,
+                                          float cut, int* pred, int* n_kept, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  CH_CHECK_SHAPE("smt_vqtts_code_head_sample");
+  SMT_CHECK_ARG(t_q >= 1, "smt_vqtts_code_head_sample: t_q=%d must be at least 1", t_q);
+  SMT_CHECK_ARG(rows % t_q == 0, "smt_vqtts_code_head_sample: rows=%lld must be a multiple of t_q=%d", (long long)rows, t_q);
+  SMT_CHECK_ARG(inv_temperature > 0.f && inv_temperature <= 3.402823466e38f,
+                "smt_vqtts_code_head_sample: inv_temperature=%g must be finite and > 0", (double)inv_temperature);
+  SMT_CHECK_ARG(cut <= 0.f, "smt_vqtts_code_head_sample: cut=%g must be <= 0 (T ln(min_p); -inf = no truncation)", (double)cut);
+  SMT_CHECK_ARG(workspace && bias && ((seeds && pred) || rows == 0), "smt_vqtts_code_head_sample: null pointer");
+  SMT_CHECK_ARG(workspace_bytes >= smt_vqtts_code_head_workspace_bytes(channels, bins),
+                "smt_vqtts_code_head_sample: workspace of %zu B, %zu B needed", workspace_bytes,
+                smt_vqtts_code_head_workspace_bytes(channels, bins));
+  SMT_CHECK_ARG(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)h & 15) == 0,
+                "smt_vqtts_code_head_sample: h and workspace must be 16-byte aligned");
+  if (rows == 0) return 0;
+  SMT_CHECK_ARG(h, "smt_vqtts_code_head_sample: null pointer");
+  const __bf16* ws = reinterpret_cast<const __bf16*>(workspace);
+  if (cut >= -3.402823466e38f) {                                  // a finite cut: two sweeps
+    CH_DISPATCH(ch_pad(channels), (ch_launch_sample<CP, true>(stream, h, ws, bias, seeds, rows, t_q, channels, bins, inv_temperature,
+                                                              cut, pred, n_kept)));
+  } else {
+    CH_DISPATCH(ch_pad(channels), (ch_launch_sample<CP, false>(stream, h, ws, bias, seeds, rows, t_q, channels, bins,
+                                                               inv_temperature, cut, pred, n_kept)));
+  }
+  SMT_CHECK_LAUNCH("ch_sample");
   return 0;
 }
 

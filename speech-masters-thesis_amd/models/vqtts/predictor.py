@@ -1,6 +1,6 @@
 """Code predictor of VQTTS: the text-encoder means, gathered onto the frames, go through a four-layer residual stack
 (``quant_decoder``) and a projection to ``l_bins`` logits (``quant_proj``) that is trained with the cross-entropy against
-the codes the quantiser chose; at synthesis its argmax picks the code.
+the codes the quantiser chose; at synthesis its argmax picks the code, or a draw from its tempered distribution does.
 
 Reference: models/vqtts/vqtts.py:77-87 (the two modules), 142-144 (forward), 157 and 190 (loss, accuracy), 175-178
 (synthesis).  The parameter tree keeps the reference's keys (``quant_decoder.model.{i}.model.{2,5}``, ``quant_proj``), so
@@ -55,11 +55,20 @@ class CodePredictor(nn.Module):
         return x * valid[..., None].to(x.dtype), valid
 
     @convops.forward_scope
-    def forward(self, x_enc, align_idx, q_lens, target=None, drop_seed=0):
+    def forward(self, x_enc, align_idx, q_lens, target=None, drop_seed=0, sample=None):
         """With ``target`` (q_rel [B, Tq] of the bottleneck): (loss_ce, q_acc, pred); frames without a token or at or past
-        q_lens are not scored.  Without: pred [B, Tq] int32."""
+        q_lens are not scored.  Without: pred [B, Tq] int32, the argmax of the code head or, with
+        ``sample = (temperature, min_p, seeds)`` (seeds [B] int32 on the device), one draw per frame
+        (``smt_amd.vqtts.code_head_sample``)."""
+        if sample is not None and target is not None:
+            raise ValueError("CodePredictor.forward: sample= draws codes at synthesis; it cannot be combined with target=")
         h, valid = self.hidden(x_enc, align_idx, q_lens, drop_seed)
         if target is None:
+            if sample is not None:
+                temperature, min_p, seeds = sample
+                pred = vqtts.code_head_sample(h, self.quant_proj.weight, self.quant_proj.bias, seeds, h.shape[1], temperature, min_p,
+                                              split=self._split)
+                return pred.view(h.shape[:-1])
             return vqtts.code_head_predict(h, self.quant_proj.weight, self.quant_proj.bias, split=self._split)
         scored = valid & (align_idx >= 0)
         target = torch.where(scored, target.to(torch.int64), torch.full_like(target, -1, dtype=torch.int64))

@@ -152,7 +152,7 @@ class VQTTS(TokenToWaveformModel):
         return out, metrics
 
     @torch.no_grad()
-    def infer(self, x, x_lengths=None, *, length_scale=1.0):
+    def infer(self, x, x_lengths=None, *, length_scale=1.0, temperature=0.0, min_p=0.0, seed=None):
         """Waveforms from token ids: x [B, Tx] integer ids, ragged with x_lengths [B] -> (wave [B, T_out * stride] fp32,
         wave_lengths [B] int64), T_out = the longest item's frames, wave exactly 0 at or past wave_lengths[b].
 
@@ -160,14 +160,37 @@ class VQTTS(TokenToWaveformModel):
         lengths -> smt_glow_duration_index (frame -> token) -> code predictor (argmax of the code head) -> smt_vqtts_emit
         (absolute code and codebook row of every frame) -> audio decoder.  Invalid inputs raise ValueError before the
         launch they would corrupt: the checks of ``models.base.token_batch``, length_scale <= 0, and an item whose
-        durations are not finite or sum past 2^24 frames."""
+        durations are not finite or sum past 2^24 frames.
+
+        ``temperature`` > 0 draws every frame's code from softmax(logits / temperature) instead (inside the code head,
+        smt_vqtts_code_head_sample), among the codes with p >= ``min_p`` * p_max; it needs ``seed``: an int (item b draws
+        with (seed + b) mod 2^31) or a sequence of B ints.  Equal seeds give equal waveforms; a frame's draw depends on its item's
+        seed, its index and its own logits only, not on the batch around it.  ``temperature`` = 0 is the argmax and takes
+        neither."""
         if self.training:
             raise RuntimeError(f"{type(self).__name__}.infer needs evaluation mode: call .eval() first")
         if not (math.isfinite(length_scale) and length_scale > 0):
             raise ValueError(f"length_scale must be a finite number > 0, got {length_scale}")
+        if not (math.isfinite(temperature) and temperature >= 0):
+            raise ValueError(f"temperature must be a finite number >= 0, got {temperature}")
+        if not 0.0 <= min_p <= 1.0:
+            raise ValueError(f"min_p must lie in [0, 1], got {min_p}")
+        if temperature == 0 and (min_p != 0 or seed is not None):
+            raise ValueError("min_p and seed apply to sampling: temperature = 0 is the argmax of the code head")
+        if temperature > 0 and seed is None:
+            raise ValueError("temperature > 0 draws the codes and needs seed= (an int, or one int per item)")
         dev = self.text_encoder.emb.weight.device
         xc, lens, valid = token_batch(x, x_lengths, self.n_vocab)
         b = xc.shape[0]
+        seeds = None
+        if temperature > 0:
+            if isinstance(seed, int) and not isinstance(seed, bool):
+                seeds = [(seed + i) % 2 ** 31 for i in range(b)]
+            else:
+                seeds = list(seed.tolist() if isinstance(seed, torch.Tensor) else seed)
+                if len(seeds) != b or not all(isinstance(v, int) and not isinstance(v, bool) for v in seeds):
+                    raise ValueError(f"seed must be an int or a sequence of {b} ints (one per item), got {len(seeds)} values")
+                seeds = [v % 2 ** 31 for v in seeds]
         x_dev = torch.where(valid, xc, 0).to(dev)
         x_enc, _, logw, lens32 = self.text_encoder(x_dev, lens.to(dev))
         _, z_lens, cum = glow.durations(logw, lens32, length_scale, 1)
@@ -181,7 +204,8 @@ class VQTTS(TokenToWaveformModel):
         if t_out == 0:
             return torch.zeros(b, 0, device=dev), wave_lengths
         idx = glow.duration_index(cum, lens32, z_lens, t_out)
-        pred = self.predictor(x_enc, idx, z_lens)
+        sample = (temperature, min_p, torch.tensor(seeds, dtype=torch.int32).to(dev)) if seeds is not None else None
+        pred = self.predictor(x_enc, idx, z_lens, sample=sample)
         y_d, _ = vqtts.emit_codes(pred, x_dev, idx, z_lens, self.quant_bottleneck.k, self.n_vocab, self.l_bins)
         wave, _ = self.audio_decoder(y_d.to(self.compute_dtype), z_lens)
         keep = torch.arange(wave.shape[1], device=dev)[None, :] < wave_lengths[:, None]

@@ -2,7 +2,7 @@
 batched): mel spectrograms from a GlowTTS, waveforms from a VQTTS.
 
     python -m scripts.synthesize --log_dir ./logs/glow_tts --ckpt_num 5000 --tokens utterances.txt --dump_dir ./outputs \
-        [--batch_size 16] [--noise_scale 0.667] [--length_scale 1.0] [--seed 0]
+        [--batch_size 16] [--noise_scale 0.667] [--length_scale 1.0] [--seed 0] [--temperature 0] [--min_p 0]
 
 ``--tokens`` holds one utterance per line as whitespace-separated integer ids (the ids of datasets/synthetic.py, and the ones
 the reference's CMUDict parser would emit; the text front end itself is not built).  Writes
@@ -11,9 +11,12 @@ the reference's CMUDict parser would emit; the text front end itself is not buil
 
 A token-to-waveform model (VQTTS, `VQTTS.infer`) writes ``wav_<i>.wav`` (16-bit mono at the dataset's sample rate, trimmed to
 the utterance's length) and the log-mel spectrograms of the waveforms as ``mel_spectrograms.png``; it has no prior noise,
-so ``--noise_scale`` other than 1 is refused for it."""
+so ``--noise_scale`` other than 1 is refused for it.  ``--temperature`` > 0 draws its codes instead of taking the argmax
+(``--min_p`` truncates the draw); utterance i of the tokens file draws with seed ``--seed`` + i whatever ``--batch_size``.  GlowTTS
+has no codes and refuses both flags."""
 import argparse
 import logging
+import math
 import os
 
 import numpy as np
@@ -36,7 +39,9 @@ def parse_args(argv=None):
     p.add_argument("--batch_size", type=int, default=16, help="Utterances per inference call")
     p.add_argument("--noise_scale", type=float, default=1.0, help="Scale of the prior noise (1 = the reference)")
     p.add_argument("--length_scale", type=float, default=1.0, help="Scale of the predicted durations (1 = the reference)")
-    p.add_argument("--seed", type=int, default=0, help="Seed of the prior noise")
+    p.add_argument("--seed", type=int, default=0, help="Seed of the prior noise (GlowTTS) or of the code draws (VQTTS, --temperature > 0)")
+    p.add_argument("--temperature", type=float, default=0.0, help="VQTTS: temperature of the code draw (0 = argmax)")
+    p.add_argument("--min_p", type=float, default=0.0, help="VQTTS: draw among the codes with p >= min_p * p_max (0 = all)")
     return p.parse_args(argv)
 
 
@@ -78,7 +83,9 @@ def synthesize_waveforms(model, config, utterances, args, dump_dir, device):
                          n_mels=ds.n_mels, f_min=0.0, f_max=8000.0).to(device)
     mels, count = [], 0
     for x, x_lengths in batches(utterances, args.batch_size):
-        wave, wave_lengths = model.infer(x, x_lengths, length_scale=args.length_scale)
+        draw = dict(temperature=args.temperature, min_p=args.min_p,
+                    seed=[args.seed + count + i for i in range(x.shape[0])]) if args.temperature > 0 else {}
+        wave, wave_lengths = model.infer(x, x_lengths, length_scale=args.length_scale, **draw)
         for i, n in enumerate(wave_lengths.tolist()):
             write_wav(os.path.join(dump_dir, f"wav_{count}.wav"), wave[i, :n].clamp(-1, 1).cpu().numpy(), ds.sample_rate)
             count += 1
@@ -93,6 +100,10 @@ def main(argv=None):
     args = parse_args(argv)
     if args.batch_size < 1:
         raise ValueError("--batch_size must be >= 1")
+    if not (math.isfinite(args.temperature) and args.temperature >= 0):
+        raise ValueError(f"--temperature must be a finite number >= 0, got {args.temperature}")
+    if not 0.0 <= args.min_p <= 1.0 or (args.temperature == 0 and args.min_p != 0):
+        raise ValueError(f"--min_p must lie in [0, 1] and applies to --temperature > 0 only, got {args.min_p}")
     if not torch.cuda.is_available():
         raise RuntimeError("synthesize runs the model on MI355X (libsmt_hip.so); no GPU is visible")
     utterances = read_tokens(args.tokens)
@@ -111,6 +122,8 @@ def main(argv=None):
     from models.base import TokenToWaveformModel
     if isinstance(model, TokenToWaveformModel):
         return synthesize_waveforms(model, config, utterances, args, dump_dir, device)
+    if args.temperature != 0.0 or args.min_p != 0.0:
+        raise ValueError(f"--temperature and --min_p apply to a token-to-waveform model's code draw; {type(model).__name__} has no codes")
     torch.manual_seed(args.seed)
     mels = []
     for x, x_lengths in batches(utterances, args.batch_size):

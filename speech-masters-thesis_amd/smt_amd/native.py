@@ -82,6 +82,8 @@ _SIGNATURES = {
     "smt_vqtts_code_head_prepare": (c_int, [c_ptr, c_int, c_int, c_ptr, c_size, c_ptr]),
     "smt_vqtts_code_head_fwd": (c_int, [c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                         c_ptr]),
+    "smt_vqtts_code_head_sample": (c_int, [c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_ptr, c_ptr,
+                                           c_ptr]),
     "smt_vqtts_code_head_bwd_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
     "smt_vqtts_code_head_bwd": (c_int, [c_ptr, c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr,
                                         c_ptr, c_size, c_ptr]),

@@ -4,10 +4,12 @@ channels-last rows [B, T, D], prefix masks as int32 lengths on the device, no ho
 Reference: models/vqtts/vqtts.py:133-137, 150-156.
 
 The code head ("VQTTS code head" of the header, csrc/vqtts_codes.hip): the projection to l_bins logits fused with the
-cross-entropy or the argmax -- reference models/vqtts/vqtts.py:144, 157, 176, 190.
+cross-entropy, the argmax or a draw (``code_head_sample``) -- reference models/vqtts/vqtts.py:144, 157, 176, 190.
 
 The code emission ("VQTTS code emission", csrc/vqtts_emit.hip): predicted code -> absolute code and codebook row, the
 synthesis side of the grouped bottleneck -- reference models/vqtts/vqtts.py:170-174."""
+import math
+
 import torch
 
 from . import convops
@@ -207,6 +209,42 @@ def code_head_predict(h, weight, bias, split=None):
     """pred [...] int32 = argmax of ``h @ weight.T + bias`` over the bins, lowest index on ties (the synthesis form)."""
     shape = h.shape[:-1]
     return _head_fwd(h, weight, bias, None, False, split)[-1].view(shape)
+
+
+def sample_cut(temperature, min_p):
+    """(1 / T, cut = T ln(min_p)) as the floats the C entry takes; the cut is computed in double and rounded once (by the
+    binding's conversion to float), -inf for min_p = 0.  ValueError for a temperature that is not finite and > 0 or a min_p
+    outside [0, 1]."""
+    temperature, min_p = float(temperature), float(min_p)
+    if not (math.isfinite(temperature) and temperature > 0):
+        raise ValueError(f"code_head_sample: temperature must be a finite number > 0, got {temperature}")
+    if not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"code_head_sample: min_p must lie in [0, 1], got {min_p}")
+    return 1.0 / temperature, (temperature * math.log(min_p) if min_p > 0 else -math.inf)
+
+
+@torch.no_grad()
+def code_head_sample(h, weight, bias, seeds, t_q, temperature, min_p=0.0, split=None, want_kept=False):
+    """pred [N] int32: one draw per row of ``h`` [..., C] from softmax((h @ weight.T + bias) / temperature), restricted to
+    the bins with p >= min_p * p_max (min-p; 0 keeps all) -- "VQTTS code head", sample, of the header: Gumbel-max inside
+    the fused sweep, no [N, V] tensor.  Row r is frame r % t_q of item r // t_q and draws with (seeds[r // t_q], r % t_q)
+    alone; seeds [N / t_q] int32 on the device.  ``want_kept`` adds n_kept [N] int32, the size of each row's kept set.  Not
+    differentiable.  ``split``: the owner's ``WeightSplit``."""
+    inv_t, cut = sample_cut(temperature, min_p)
+    h, weight, bias, n, c, v = _head_args(h, weight, bias)
+    t_q = int(t_q)
+    if t_q < 1 or n % t_q:
+        raise ValueError(f"code_head_sample: {n} rows are not a whole number of items of t_q = {t_q} frames")
+    if not (isinstance(seeds, torch.Tensor) and seeds.dtype == torch.int32 and seeds.is_cuda and tuple(seeds.shape) == (n // t_q,)):
+        raise ValueError(f"code_head_sample: seeds must be an int32 device tensor of shape ({n // t_q},)")
+    ws = _split_of(weight.detach(), split)
+    pred = torch.empty(n, dtype=torch.int32, device=h.device)
+    kept = torch.empty(n, dtype=torch.int32, device=h.device) if want_kept else None
+    with profiler.region("vqtts_code_head:sample", flops=(12.0 if min_p > 0 else 6.0) * n * c * v, bound="mfma", dtype="bf16"):
+        N.check(N.lib().smt_vqtts_code_head_sample(N.ptr(h), N.ptr(ws), ws.numel(), N.ptr(bias), N.ptr(seeds.contiguous()), n, t_q, c, v,
+                                                   inv_t, cut, N.ptr(pred), N.ptr(kept), N.stream_ptr()),
+                "smt_vqtts_code_head_sample")
+    return (pred, kept) if want_kept else pred
 
 
 # --------------------------------------------------------------------------------------------------- code emission

@@ -10,9 +10,17 @@ prints ms per call, the achieved rate against the algorithmic 2 N C V FLOP of on
 3 products; the fused path executes 3 bf16 MFMAs per product and recomputes the logits twice in the backward), and the
 peak device memory each path allocates above its inputs (its gradients included).
 
-    python tools/bench_code_head.py [--out FILE]
+Sampling lines (``--lines sample`` for these alone): the fused draw ``vqtts.code_head_sample`` at N = 18,176 (32 items of 568
+frames, the configuration's shape) and N = 581,632, without truncation (one sweep) and with min_p = 0.05 (two sweeps), beside
+(a) the argmax form ``vqtts.code_head_predict`` and (b) the unfused draw on the same device: ``F.linear``, Gumbel noise from
+torch's generator, ``argmax``, which writes the [N, V] logits and the noise.  The four are timed in ALTERNATING windows (five
+rounds of about 0.2 s per line, after warming every line up); a line reports the median over the rounds and the spread
+(min .. max), and the peak memory above the inputs.
+
+    python tools/bench_code_head.py [--out FILE] [--lines all|head|sample]
 """
 import argparse
+import math
 import os
 import sys
 
@@ -57,9 +65,64 @@ def peak(fn, reset):
     return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
 
 
+def alternate(fns, rounds=5, window_ms=200.0, warmup=5):
+    """{name: ms per call, one per round}: every line warmed up first, then `rounds` rounds in which the lines take turns."""
+    iters = {}
+    for name, fn in fns.items():
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        iters[name] = max(10, int(window_ms / _window(fn, 5)))
+    times = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            times[name].append(_window(fn, iters[name]))
+    return times
+
+
+def sample_lines(emit, gen, w, b, split):
+    w, b = w.detach(), b.detach()
+    for n, t_q in ((18176, 568), (581632, 18176)):
+        h = torch.randn(n, C, generator=gen).cuda()
+        seeds = torch.arange(n // t_q, dtype=torch.int32).cuda()
+        gflop = 2.0 * n * C * V / 1e9
+        emit(f"--- sampling, N={n} ({n // t_q} items of {t_q} frames): one product is {gflop:.1f} GFLOP; fp32 logits would be "
+             f"{4 * n * V / 2 ** 20:.0f} MiB")
+
+        def unfused(min_p):
+            def fn():
+                with torch.no_grad():
+                    logits = F.linear(h, w, b)
+                    u = torch.rand_like(logits).clamp_(min=2.0 ** -24)
+                    if min_p > 0:
+                        logits = logits.masked_fill(logits < logits.max(-1, keepdim=True).values + math.log(min_p), float("-inf"))
+                    return (logits - torch.log(-torch.log(u))).argmax(-1)
+            return fn
+
+        fns = {"fused    argmax (code_head_predict)": lambda: vqtts.code_head_predict(h, w, b, split=split),
+               "fused    draw, no truncation": lambda: vqtts.code_head_sample(h, w, b, seeds, t_q, 1.0, 0.0, split=split),
+               "fused    draw, min_p 0.05": lambda: vqtts.code_head_sample(h, w, b, seeds, t_q, 1.0, 0.05, split=split),
+               "unfused  draw, no truncation": unfused(0.0), "unfused  draw, min_p 0.05": unfused(0.05)}
+        times = alternate(fns)
+        med = {}
+        for name, fn in fns.items():
+            t = sorted(times[name])
+            med[name] = t[len(t) // 2]
+            sweeps = 2 if name.startswith("fused") and "min_p" in name else 1
+            emit(f"{name:36s}: {med[name]:9.3f} ms  (min {t[0]:.3f} .. max {t[-1]:.3f} over {len(t)} alternating windows)  "
+                 f"{sweeps * gflop / med[name]:7.1f} algorithmic TFLOP/s  peak {peak(fn, lambda: None):8.1f} MiB")
+        g = med["fused    argmax (code_head_predict)"]
+        emit(f"draw / argmax: {med['fused    draw, no truncation'] / g:.2f} without truncation, {med['fused    draw, min_p 0.05'] / g:.2f} with "
+             f"min_p; unfused / fused: {med['unfused  draw, no truncation'] / med['fused    draw, no truncation']:.2f} without, "
+             f"{med['unfused  draw, min_p 0.05'] / med['fused    draw, min_p 0.05']:.2f} with min_p")
+        del h
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also append the lines to this file")
+    ap.add_argument("--lines", default="all", choices=("all", "head", "sample"), help="which lines to measure")
     args = ap.parse_args()
     lines = []
 
@@ -72,7 +135,7 @@ def main():
     w = ((torch.rand(V, C, generator=gen) * 2 - 1) / C ** 0.5).cuda().requires_grad_(True)
     b = ((torch.rand(V, generator=gen) * 2 - 1) / C ** 0.5).cuda().requires_grad_(True)
     split = vqtts.WeightSplit()
-    for n in (581632, 36352):
+    for n in (581632, 36352) if args.lines != "sample" else ():
         h = torch.randn(n, C, generator=gen).cuda().requires_grad_(True)
         t = torch.randint(0, V, (n,), generator=gen)
         t[torch.rand(n, generator=gen) < 0.1] = -1
@@ -110,6 +173,8 @@ def main():
              f"{res['unfused  forward + backward'] / res['fused    forward + backward']:.2f}; loss fused {lf:.6f} unfused {lu:.6f}")
         del h, t
         torch.cuda.empty_cache()
+    if args.lines != "head":
+        sample_lines(emit, gen, w, b, split)
     if args.out:
         with open(args.out, "a") as f:
             f.write("\n".join(lines) + "\n")
