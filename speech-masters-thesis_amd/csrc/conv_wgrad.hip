@@ -369,14 +369,39 @@ struct ShiftArgs {
   int tiles_per_item, tiles_per_wg, n_chunks, nblk_ci, nblk_co, with_bias;
 };
 
+#ifndef SMT_WGRAD_STAMP
+#define SMT_WGRAD_STAMP 0   // diagnostic build (tools/wgrad_phases.sh): per-wave cycle sums of the phases of conv_wgrad_shift_kernel
+#endif
+#if SMT_WGRAD_STAMP
+// [workgroup < 256][wave][barrier | stage | k-loop | slab store | tiles]: written here, read by smt_wgrad_debug_dump only
+__device__ unsigned long long wg_dbg[256 * 8 * 8];
+__device__ __forceinline__ unsigned long long wg_stamp() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+// the sums stay in scalar registers during the tile loop and leave the kernel once, after the slab store
+#define WG_SUMS unsigned long long wg_sum[5] = {0, 0, 0, 0, 0}
+#define WG_T(var) const unsigned long long var = wg_stamp()
+#define WG_ACC(k, a, b) wg_sum[k] += (b) - (a)
+#define WG_DUMP do { if (lane == 0 && blockIdx.x < 256) for (int k_ = 0; k_ < 5; ++k_) wg_dbg[(blockIdx.x * 8 + wave) * 8 + k_] += wg_sum[k_]; } while (0)
+#else
+#define WG_SUMS do {} while (0)
+#define WG_T(var) do {} while (0)
+#define WG_ACC(k, a, b) do {} while (0)
+#define WG_DUMP do {} while (0)
+#endif
+
 constexpr int SH_R = 128, SH_XROWS = SH_R + 8, SH_DY = SH_R * 128, SH_X = SH_XROWS * 256, SH_STAGE = SH_DY + SH_X;
 
 template <int NTAPS>
 __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, const __bf16* __restrict__ zero_page) {
-  typedef __bf16 T;
-  constexpr int CB = 64, CIB = 128, WNC = 4, NTHR = 512, DYB = CB * 2, XB = CIB * 2, PLANES = NTAPS + 1;
+  constexpr int CB = 64, CIB = 128, WNC = 4, DYB = CB * 2, XB = CIB * 2, PLANES = NTAPS + 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: the LDS base of a piece goes to M0 without a VALU detour
   const int wm = wave / WNC, wn = wave % WNC;
   const int r = lane & 31, hh = lane >> 5;
 
@@ -395,34 +420,44 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
-  auto stage = [&](int tile, int buf) {
-    const int item = tile / p.tiles_per_item;
+  // Staging through range-checked V#s (conv_common.h: ws_rsrc / ws_dma16), as in conv_ws.hip: one descriptor per operand
+  // and tile covers the valid class-domain rows of the tile's item (dy: Tc rows, x: len_in rows), a lane's source is a 32-bit
+  // byte offset = tile-invariant lane part + a scalar per tile, and whatever lies outside -- rows before the item (the offset
+  // wraps to ~4 GiB), rows at or past Tc / len_in, rows no tap reads -- is out of range and lands in LDS as zero.  (The plan
+  // keeps every in-range offset below 2^31.)  A wave stages SH_PIECES pieces per tile, each one DMA instruction = 1 KiB:
+  //   pieces 0, 1: dy rows 8 wave + 64 i + (lane >> 3), 8 chunks of 16 B per row
+  //   pieces 2..5: x rows 4 wave + 32 (i - 2) + (lane >> 4), 16 chunks per row;  piece 6: x rows 128 + ..., waves 0 and 1 only
+  constexpr int SH_PIECES = 7;
+  // pieces per k-step of the k-loop: two, behind the first two MFMAs of k-steps 0..3, so that the last piece has half a tile
+  // to land (one per k-step measured the same at 7 and 9 taps and 2-5 % slower per tile at 3 and 5: the wait at the top of
+  // the next tile grows)
+  constexpr int SH_PPS = 2;
+  static_assert(SH_PPS <= NTAPS && SH_PPS * (SH_R / 16) >= SH_PIECES, "the pieces fit the k-loop");
+  const unsigned pdy = (unsigned)p.ldy * rs * 2u, pxx = (unsigned)p.ldx * rs * 2u;      // byte pitches of the class-domain rows
+  const int dyrow = 8 * wave + (lane >> 3), xrow = 4 * wave + (lane >> 4);              // + 64 i / + 32 i: the swizzle terms stay
+  const unsigned voff_dy = (unsigned)dyrow * pdy + (unsigned)(((lane & 7) ^ swz_dy(dyrow)) << 4);
+  const unsigned voff_x = (unsigned)xrow * pxx + (unsigned)(((lane & 15) ^ swz_x(xrow)) << 4);
+  const unsigned voff_x6 = (128 + xrow < SH_R + NTAPS - 1) ? voff_x + 128u * pxx : 0x80000000u;   // rows no tap reads: out of range
+  struct Src { __amdgpu_buffer_rsrc_t rdy, rxx; unsigned sdy, sx; };
+  // The descriptors change with the (batch, class) item only -- a workgroup's run of tiles crosses few item borders -- so
+  // the divisions and the scalar load of lens_in[b] are paid per item; per tile only the two scalar offsets move.
+  auto item_source = [&](int item, Src& s) {
     const int b = item / rs, cls = item - b * rs;
-    const int t0 = (tile - item * p.tiles_per_item) * SH_R;
     const int Tc = (p.Tout - cls + rs - 1) / rs;
-    const T* xg = reinterpret_cast<const T*>(p.x) + (long long)b * p.x_bs + (long long)cls * p.ldx + ci0;
-    const T* dyg = reinterpret_cast<const T*>(p.dy) + (long long)b * p.dy_bs + (long long)cls * p.ldy + co0;
-    const long long ldx = (long long)p.ldx * rs, ldy = (long long)p.ldy * rs;
     const int len_full = p.lens_in ? min(scalar_load_i32(p.lens_in + b), p.Tin) : p.Tin;
     const int len_in = max(0, (len_full - cls + rs - 1) / rs);
+    s.rdy = ws_rsrc(p.dy, ((long long)b * p.dy_bs + (long long)cls * p.ldy + co0) * 2, (unsigned)Tc * pdy);
+    s.rxx = ws_rsrc(p.x, ((long long)b * p.x_bs + (long long)cls * p.ldx + ci0) * 2, (unsigned)len_in * pxx);
+  };
+  auto tile_source = [&](int t0, Src& s) {
+    s.sdy = (unsigned)t0 * pdy;
+    s.sx = (unsigned)(t0 - p.pad) * pxx;
+  };
+  auto piece = [&](const Src& s, int i, int buf) {       // i is a compile-time constant wherever this is called
     unsigned char* base = smem + (size_t)buf * SH_STAGE;
-    // dy: 128 rows x 8 chunks; one wave-instruction = 8 rows
-#pragma unroll
-    for (int g = wave; g < SH_R / 8; g += NTHR / 64) {
-      const int row = 8 * g + (lane >> 3), pos = lane & 7;
-      const int t = t0 + row;
-      const int ch = pos ^ swz_dy(row);
-      lds_dma16((t < Tc) ? dyg + (long long)t * ldy + ch * 8 : zero_page + pos * 8, base + g * 1024);
-    }
-    // x: 136 rows x 16 chunks; one wave-instruction = 4 rows
-    const int tin0 = t0 - p.pad;
-    for (int g = wave; g < SH_XROWS / 4; g += NTHR / 64) {
-      const int row = 4 * g + (lane >> 4), pos = lane & 15;
-      const int tin = tin0 + row;
-      const bool ok = (row < SH_R + NTAPS - 1) && (tin >= 0) && (tin < len_in);
-      const int ch = pos ^ swz_x(row);
-      lds_dma16(ok ? xg + (long long)tin * ldx + ch * 8 : zero_page + pos * 8, base + SH_DY + g * 1024);
-    }
+    if (i < 2) ws_dma16(s.rdy, voff_dy + s.sdy + (unsigned)(64 * i) * pdy, base + (wave + 8 * i) * 1024);
+    else if (i < 6) ws_dma16(s.rxx, voff_x + s.sx + (unsigned)(32 * (i - 2)) * pxx, base + SH_DY + (wave + 8 * (i - 2)) * 1024);
+    else if (wave < 2) ws_dma16(s.rxx, voff_x6 + s.sx, base + SH_DY + (wave + 32) * 1024);
   };
 
   bf16x8 ones;
@@ -454,12 +489,38 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.q1) : "v"(px), "n"(12 * XB));
   };
 
-  if (tile_begin < tile_end) stage(tile_begin, 0);
+  WG_SUMS;
+  // (item, first row) of the tile staged next, and its source
+  const int item_rows = p.tiles_per_item * SH_R;
+  int n_item = tile_begin / p.tiles_per_item, n_t0 = (tile_begin - n_item * p.tiles_per_item) * SH_R;
+  Src sn;
+  sn.rdy = sn.rxx = ws_rsrc(p.x, 0, 0);
+  if (tile_begin < tile_end) {
+    item_source(n_item, sn);
+    tile_source(n_t0, sn);
+#pragma unroll
+    for (int i = 0; i < SH_PIECES; ++i) piece(sn, i, 0);
+  }
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     const int buf = (tile - tile_begin) & 1;
+    WG_T(c0);
     vm_wait<0>();
     __syncthreads();                       // this tile has landed for every wave; the other buffer is free
-    if (tile + 1 < tile_end) stage(tile + 1, buf ^ 1);
+    WG_T(c1);
+    // The next tile's pieces go out behind the MFMAs of the k-loop (as one burst here, with both waves of a SIMD in lockstep
+    // and the matrix pipe idle, the 6-7 pieces with their 64-bit addresses cost 2,100-2,200 cycles per tile:
+    // profiles/dma_placement_phases.txt).  Descriptors, lens_in[b] and scalar offsets are ready before the k-loop, whose
+    // lgkmcnt counts must see LDS reads only.  The last tile issues the same pieces through descriptors of zero records,
+    // which the range check drops (zeros land in the idle buffer): one code path.
+    const bool more = tile + 1 < tile_end;
+    n_t0 += SH_R;
+    if (n_t0 == item_rows) {
+      n_t0 = 0; ++n_item;
+      if (more) item_source(n_item, sn);
+    }
+    if (!more) sn.rdy = sn.rxx = ws_rsrc(p.x, 0, 0);
+    tile_source(n_t0, sn);
+    WG_T(c2);
     const unsigned base = lds0 + (unsigned)buf * SH_STAGE;
     Frags fr[2];
     request(fr[0], base, 0);
@@ -486,12 +547,21 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
           bw = u32x4{w[m], w[m + 1], w[m + 2], w[m + 3]};
         }
         acc[s] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, bw), acc[s], 0, 0, 0);
+        if (s < SH_PPS && SH_PPS * k0 + s < SH_PIECES) {   // fenced, so that the piece stays behind this MFMA
+          __builtin_amdgcn_sched_barrier(0);
+          piece(sn, SH_PPS * k0 + s, buf ^ 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
       // bias gradient: the four waves of a row share the k-steps (each column block of the bias plane then holds a
       // PARTIAL sum; the reduce kernel adds columns 0, 32, 64, 96)
       if (bias_plane && (k0 & 3) == wn) acc[NTAPS] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, acc[NTAPS], 0, 0, 0);
     }
+    WG_T(c3);
+    WG_ACC(0, c0, c1); WG_ACC(1, c1, c2); WG_ACC(2, c2, c3); WG_ACC(4, c0, c0 + 1);
   }
+  vm_wait<0>();                            // the last tile's dropped pieces still write (zeros) to this workgroup's LDS
+  WG_T(c4);
   float* out = p.slab + ((size_t)w.cgl * w.nblk + w.blk) * (size_t)PLANES * CB * CIB;
 #pragma unroll
   for (int j = 0; j < PLANES; ++j)
@@ -500,6 +570,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
       const int row = wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
       out[((size_t)j * CB + row) * CIB + wn * 32 + r] = acc[j][e];
     }
+  WG_T(c5);
+  WG_ACC(3, c4, c5);
+  WG_DUMP;
 }
 
 // plan of the shifted-fragment variant; false = not applicable
@@ -516,6 +589,10 @@ static bool wgrad_shift_plan(const smt_conv_desc* d, ShiftPlan* pl) {
   }
   if (pad < 0 || pad > d->taps - 1) return false;
   const long long tc_max = (d->t_out + rs - 1) / rs;
+  // 32-bit buffer offsets: an item's rows plus a tile beyond them stay below 2^31 bytes, so that rows before the item
+  // (offsets that wrap) and the out-of-range marker of the kernel are beyond every descriptor's range
+  const long long span = (tc_max + 2 * SH_R) * rs * 2;
+  if (span * d->ld_x >= (1ll << 31) || span * d->ld_y >= (1ll << 31)) return false;
   const int tpi = (int)((tc_max + SH_R - 1) / SH_R);
   const long long ntiles = (long long)tpi * d->batch * rs;
   static const int min_tiles = getenv("SMT_SHIFT_MIN_TILES") ? atoi(getenv("SMT_SHIFT_MIN_TILES")) : 256;
@@ -660,6 +737,14 @@ int launch_wgrad_reduce(const float* slab, float* dw, float* db, int n_chunks, i
 }  // namespace smt
 
 using namespace smt;
+
+#if SMT_WGRAD_STAMP
+extern "C" int smt_wgrad_debug_dump(unsigned long long* host, int n, int reset) {
+  int rc = (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(wg_dbg), sizeof(unsigned long long) * n);
+  if (reset) { static unsigned long long z[256 * 8 * 8]; rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(wg_dbg), z, sizeof(z)); }
+  return rc;
+}
+#endif
 
 extern "C" int smt_wgrad_reduce_defer(int on, smt_stream_t stream_) {
   // on = 1: the weight-gradient calls that follow on this thread (smt_conv1d_wgrad, smt_conv1x1_bwd, smt_conv_k1_bwd,

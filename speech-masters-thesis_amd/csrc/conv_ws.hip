@@ -27,7 +27,7 @@
 namespace smt {
 
 #ifndef SMT_WS_STAMP
-#define SMT_WS_STAMP 0   // diagnostic build (tools/ws_phases.sh): per-wave cycle sums of the phases of conv_ws2_kernel
+#define SMT_WS_STAMP 0   // diagnostic build (tools/ws_phases.sh): per-wave cycle sums of the phases of the three kernels
 #endif
 #if SMT_WS_STAMP
 __device__ unsigned long long ws_dbg[256 * 8 * 8];
@@ -203,10 +203,54 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_kernel(ConvArgs p, const __bf16
     WS_T(c0);
     __syncthreads();
     WS_T(c1);
-    if (tile + 1 < tile_end) stage_a(tile + 1, buf ^ 1);
+    // MODE 2 (the data gradient) issues none of its pieces here: issued as one burst, with the matrix pipe idle, a piece
+    // cost 140-190 cycles of issue time (profiles/dma_placement_phases.txt), so they go out one per k-step behind that
+    // step's first MFMA (dma_slot below).  What the burst built per tile is built here: descriptors, lens_in[b] (a scalar
+    // load, which must not sit inside the counted lgkmcnt pipeline) and the per-lane offsets, which then advance by scalars.
+    // The last tile of the run has no next tile: n_in = 0 skips its input pieces.
+    __amdgpu_buffer_rsrc_t rx_n = ws_rsrc(p.x, 0, 0), re_res = rx_n, re_act = rx_n;
+    unsigned vo_in = 0, vo_res = 0, vo_act = 0, pitch_res = 0, pitch_act = 0;
+    int n_in = 0;
+    // the wave index as a SCALAR: with the per-lane value in a descriptor's base the compiler keeps the descriptor in
+    // VGPRs and wraps every piece in a waterfall loop (four v_readfirstlane and a branch per piece: what stage_epi pays)
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    if constexpr (MODE == 2) {
+      if (tile + 1 < tile_end) {
+        int nb, ncls, nt0;
+        decode(tile + 1, nb, ncls, nt0);
+        const int len_full = p.lens_in ? min(scalar_load_i32(p.lens_in + nb), p.Tin) : p.Tin;
+        const int len_in = max(0, (len_full - ncls + rs - 1) / rs);
+        rx_n = ws_rsrc(p.x, ((long long)nb * p.x_bs + (long long)ncls * p.ldx) * 2, (unsigned)len_in * pitch_x);
+        vo_in = voff_a0 + (unsigned)(nt0 - p.pad) * pitch_x;
+        n_in = ngroups;
+      }
+      pitch_res = (unsigned)p.ldr * rs * 2u; pitch_act = (unsigned)p.ldgh * rs * 2u;
+      re_res = ws_rsrc(p.res, ((long long)b * p.res_bs + (long long)cls * p.ldr + n0 + wave_s * 32) * 2, (unsigned)Tc * pitch_res);
+      re_act = ws_rsrc(p.gate_h, ((long long)b * p.gh_bs + (long long)cls * p.ldgh + n0 + wave_s * 32) * 2, (unsigned)Tc * pitch_act);
+      vo_res = (unsigned)(t0 + (lane >> 2)) * pitch_res + echunk;
+      vo_act = (unsigned)(t0 + (lane >> 2)) * pitch_act + echunk;
+    } else {
+      if (tile + 1 < tile_end) stage_a(tile + 1, buf ^ 1);
+    }
     WS_T(c2);
-    if (has_res) stage_epi(p.res, p.res_bs, p.ldr, b, cls, t0, Tc, lds_res);
-    if (has_epi_act) stage_epi(p.gate_h, p.gh_bs, p.ldgh, b, cls, t0, Tc, lds_act);
+    if constexpr (MODE != 2) {
+      if (has_res) stage_epi(p.res, p.res_bs, p.ldr, b, cls, t0, Tc, lds_res);
+      if (has_epi_act) stage_epi(p.gate_h, p.gh_bs, p.ldgh, b, cls, t0, Tc, lds_act);
+    }
+    // slot q of the tap loop: the 8 + 8 epilogue-operand pieces first (the epilogue reads them right after the loop), then
+    // up to WS_IN_SLOTS input pieces of the next tile (12 = 192 rows, more than the LDS budget of the plan allows)
+    constexpr int WS_EPI_SLOTS = BM / 16, WS_IN_SLOTS = 12, WS_SLOTS = 2 * WS_EPI_SLOTS + WS_IN_SLOTS;
+    static_assert(MODE != 2 || WS_SLOTS <= NTAPS * (KC / 16), "one piece per k-step");
+    unsigned char* const dst_in = smem + (size_t)(buf ^ 1) * buf_bytes + wave_s * 1024;
+    unsigned char* const dst_res = smem + 2 * (size_t)buf_bytes + wave_s * (WS_EPI / 4), * const dst_act = dst_res + WS_EPI;   // = lds_res, lds_act
+    auto dma_slot = [&](int s) {
+      if (s < WS_EPI_SLOTS) ws_dma16(re_res, vo_res + (unsigned)(16 * s) * pitch_res, dst_res + s * 1024);
+      else if (s < 2 * WS_EPI_SLOTS) ws_dma16(re_act, vo_act + (unsigned)(16 * (s - WS_EPI_SLOTS)) * pitch_act, dst_act + (s - WS_EPI_SLOTS) * 1024);
+      else {
+        const int j = s - 2 * WS_EPI_SLOTS;
+        if (wave_s + 4 * j < n_in) ws_dma16(rx_n, vo_in + (unsigned)(16 * j) * pitch_x, dst_in + j * 4096);
+      }
+    };
 
     WS_T(c4);
     f32x16 acc[MW];
@@ -234,6 +278,11 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_kernel(ConvArgs p, const __bf16
       for (int i = 0; i < MW; ++i) {
         if (q == 0) ws_first_use(acc[i]);
         ws_mfma(acc[i], wfrag[q / (KC / 16)][q % (KC / 16)], afr[q & 1][i], q / (KC / 16) < WS_AGPR_TAPS);
+        if (MODE == 2 && i == 0 && q < WS_SLOTS) {   // one piece behind the step's first MFMA, fenced so that it stays there
+          __builtin_amdgcn_sched_barrier(0);
+          dma_slot(q);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
     }
     ws_drain(acc);
@@ -246,7 +295,7 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_kernel(ConvArgs p, const __bf16
     // Stores go through range-checked buffer descriptors (rows >= Tc are dropped by the hardware, 32-bit offsets).
     const int len_out = p.lens_out ? scalar_load_i32(p.lens_out + b) : 0x7fffffff;
     const unsigned pitch_y = (unsigned)p.ldy * rs * 2u, pitch_u = (unsigned)p.ldya * rs * 2u;
-    const __amdgpu_buffer_rsrc_t ry = ws_rsrc(has_y ? p.y : p.x, has_y ? ((long long)b * p.y_bs + (long long)cls * p.ldy + n0 + wave * 32) * 2 : 0,
+    const __amdgpu_buffer_rsrc_t ry = ws_rsrc(has_y ? p.y : p.x, has_y ? ((long long)b * p.y_bs + (long long)cls * p.ldy + n0 + (MODE == 2 ? wave_s : wave) * 32) * 2 : 0,
                                               has_y ? (unsigned)Tc * pitch_y : 0u);
     const __amdgpu_buffer_rsrc_t ru = ws_rsrc(has_act_out ? p.y_act : p.x,
                                               has_act_out ? ((long long)b * p.ya_bs + (long long)cls * p.ldya + n0 + wave * 32) * 2 : 0,
@@ -475,6 +524,9 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_pipe_kernel(ConvArgs p, const _
 
   stage_a(tile_begin, 0);
   vm_wait<0>();
+  // the wave index as a SCALAR for what goes into descriptors and LDS bases (a per-lane value there puts the descriptor in
+  // VGPRs and a waterfall loop around every instruction that uses it)
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
 #pragma unroll
   for (int i = 0; i < MW; ++i)
 #pragma unroll
@@ -483,8 +535,28 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_pipe_kernel(ConvArgs p, const _
     const int buf = (tile - tile_begin) & 1;
     int b, cls, t0;
     decode(tile, b, cls, t0);
+    WS_T(c0);
     __syncthreads();                 // tile `tile` is in LDS for every wave; every wave is done with the other buffer
-    if (tile + 1 < tile_end) stage_a(tile + 1, buf ^ 1);
+    WS_T(c1);
+    // The next tile's input pieces go out behind the first MFMA of every second k-step (as in conv_ws_kernel<.., 2>: one
+    // burst here cost 105-155 cycles of issue time per piece, profiles/dma_placement_phases.txt); descriptor, lens_in[b]
+    // and the per-lane offset are ready before the loop.  No next tile: n_in = 0 skips every piece.
+    __amdgpu_buffer_rsrc_t rx_n = ws_rsrc(p.x, 0, 0);
+    unsigned vo_in = 0;
+    int n_in = 0;
+    if (tile + 1 < tile_end) {
+      int nb, ncls, nt0;
+      decode(tile + 1, nb, ncls, nt0);
+      const int len_full = p.lens_in ? min(scalar_load_i32(p.lens_in + nb), p.Tin) : p.Tin;
+      const int len_in = max(0, (len_full - ncls + rs - 1) / rs);
+      rx_n = ws_rsrc(p.x, ((long long)nb * p.x_bs + (long long)ncls * p.ldx) * 2, (unsigned)len_in * pitch_x);
+      vo_in = voff_a0 + (unsigned)(nt0 - p.pad) * pitch_x;
+      n_in = ngroups;
+    }
+    unsigned char* const dst_in = smem + (size_t)(buf ^ 1) * buf_bytes + wave_s * 1024;
+    constexpr int WS_IN_SLOTS = 12, WS_IN_EVERY = 2;      // 12 pieces = 192 rows, more than the LDS budget of the plan allows
+    static_assert(WS_IN_SLOTS * WS_IN_EVERY <= NSTEP, "the pieces fit the tap loop");
+    WS_T(c2);
 
     f32x16 acc[MW];
 #pragma unroll
@@ -514,6 +586,12 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_pipe_kernel(ConvArgs p, const _
         constexpr int i = decltype(I)::value;
         if constexpr (q == 0) ws_first_use(acc[i]);
         ws_mfma(acc[i], wfrag[q / (KC / 16)][q % (KC / 16)], afr[q & 1][i], q / (KC / 16) < AGPR_TAPS);
+        if constexpr (i == 0 && q % WS_IN_EVERY == 0 && q / WS_IN_EVERY < WS_IN_SLOTS) {
+          constexpr int j = q / WS_IN_EVERY;
+          __builtin_amdgcn_sched_barrier(0);
+          if (wave_s + 4 * j < n_in) ws_dma16(rx_n, vo_in + (unsigned)(16 * j) * pitch_x, dst_in + j * 4096);
+          __builtin_amdgcn_sched_barrier(0);
+        }
         if constexpr (4 * q + i < PH_TILE) {
           __builtin_amdgcn_sched_barrier(0);
           epi(std::integral_constant<int, 4 * q + i>{});
@@ -523,16 +601,20 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_pipe_kernel(ConvArgs p, const _
     });
     static_for<(NGAP < PH_TILE ? NGAP : PH_TILE), PH_TILE>(epi);   // micro-steps that did not fit behind this tile's MFMAs
     ws_drain(acc);
+    WS_T(c5);
     vm_wait<0>();                                       // next tile has landed; older stores retired
+    WS_T(c6);
     // hand the tile over: y = bf16(acc + bias), packed
 #pragma unroll
     for (int i = 0; i < MW; ++i)
 #pragma unroll
       for (int e = 0; e < 16; e += 2) pc[i][e >> 1] = pack_bf16x2(acc[i][e] + bval[e], acc[i][e + 1] + bval[e + 1]);
     p_b = b; p_cls = cls; p_t0 = t0;
-    p_ru = ws_rsrc(p.y_act, ((long long)b * p.ya_bs + n0 + wave * 32) * 2, (unsigned)p.Ty * ((unsigned)p.ldya * 2u));
+    p_ru = ws_rsrc(p.y_act, ((long long)b * p.ya_bs + n0 + wave_s * 32) * 2, (unsigned)p.Ty * ((unsigned)p.ldya * 2u));
     p_Tc = (p.Tout - cls + rs - 1) / rs;
     p_len = p.lens_out ? scalar_load_i32(p.lens_out + b) : 0x7fffffff;
+    WS_T(c7);
+    WS_ACC(0, c0, c1); WS_ACC(1, c1, c2); WS_ACC(4, c2, c5); WS_ACC(5, c5, c6); WS_ACC(6, c6, c7); WS_ACC(7, c0, c0 + 1);
   }
   static_for<0, PH_TILE>(epi);                          // epilogue of the last tile
 }

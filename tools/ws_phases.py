@@ -1,6 +1,10 @@
 """Per-phase cycle sums of conv_ws2_kernel from the -DSMT_WS_STAMP=1 build (tools/ws_phases.sh): for waves 0-3 (multiply,
 then write out) and waves 4-7 (write out the previous tile, then multiply) of every workgroup, cycles per tile spent in:
-barrier wait | input-tile DMA issue | deferred epilogue | epilogue-operand DMA issue | MFMA loop | vmcnt(0) wait | epilogue."""
+barrier wait | input-tile DMA issue | deferred epilogue | epilogue-operand DMA issue | MFMA loop | vmcnt(0) wait | epilogue.
+The one-wave kernels (conv_ws_kernel, conv_ws_pipe_kernel: the k >= 5 lines) are stamped at the same places; where they
+issue their DMA pieces inside the MFMA loop, "dma in" / "dma epi" hold only the descriptor set-up and the pieces' issue
+time is part of "mfma".  In conv_ws_pipe_kernel "mfma" also holds the previous tile's epilogue micro-steps and "epi" is
+the hand-over of the accumulators."""
 import ctypes, os, sys
 import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,6 +1,7 @@
 #!/bin/bash
-# Diagnostic build of conv_ws.hip with -DSMT_WS_STAMP=1 (per-wave cycle sums of the phases of conv_ws2_kernel) into a library of
-# its own (the product build is never touched), then tools/ws_phases.py.  Run on the GPU box.
+# Diagnostic build of conv_ws.hip with -DSMT_WS_STAMP=1 (per-wave cycle sums of the phases of conv_ws2_kernel, conv_ws_kernel
+# and conv_ws_pipe_kernel) into a library of its own (the product build is never touched), then tools/ws_phases.py.  Run on
+# the GPU box.  (tools/wgrad_phases.sh does the same for conv_wgrad_shift_kernel.)
 set -e
 cd "$(dirname "$0")/../speech-masters-thesis_amd/csrc"
 make -s && mkdir -p build_abl && cp build/*.o build_abl/
