@@ -559,6 +559,42 @@ int smt_lm_ce_fwd(const float* logits, const int64_t* target, float* row_out, fl
 int smt_lm_ce_bwd(const float* logits, const int64_t* target, const float* lse, const float* coef, float* dlogits,
                   int64_t rows, int vocab, smt_stream_t stream);
 
+/* The other two training losses of the TransformerLM (loss_type focal | mmi, reference models/transformer_lm/losses.py), with
+ * the conventions of smt_lm_ce_*: logits [rows, vocab] fp32; target [rows] int64, < 0 = row not scored, a scored target is
+ * < vocab (the caller's guarantee); lse [rows]; coef a DEVICE scalar (upstream gradient / number of scored rows).  Nothing
+ * synchronises with the host and there are no float atomics: every cross-row sum is merged in a fixed order, so equal
+ * inputs give equal bits.  rows = 0 returns 0 and launches nothing; rows < 0, vocab < 1 and a gamma outside the built set
+ * are argument errors, returned before any HIP call.  On unscored rows dlogits is exactly 0.
+ *
+ * Focal, (1 - p_t)^gamma * CE (FocalLoss without class weights), per scored row r with s = logit[r, t_r] - lse[r] = log p_t,
+ * p_t = exp(s), q = -expm1(s) (not 1 - exp(s): no cancellation as p_t -> 1):
+ *   l_r = -q^gamma s,   c_r = dl_r/ds = gamma q^(gamma-1) p_t s - q^gamma   (gamma = 0: c_r = -1, the cross entropy)
+ *   fwd: row_out [rows, 2] = (l_r or 0, argmax == target as 0/1, lowest index on ties), lse, row_coef [rows] = c_r (0 on
+ *        unscored rows): the powers are taken once per row here, the backward has none
+ *   bwd: dlogits[r, v] = coef[0] * c_r * ([v = t_r] - p_v),  p_v = exp(logit[r, v] - lse[r])
+ * gamma = 0 or gamma >= 1, finite; 0 < gamma < 1 (an unbounded derivative at q = 0) is not built. */
+int smt_lm_focal_fwd(const float* logits, const int64_t* target, float* row_out, float* lse, float* row_coef, int64_t rows,
+                     int vocab, float gamma, smt_stream_t stream);
+int smt_lm_focal_bwd(const float* logits, const int64_t* target, const float* lse, const float* row_coef, const float* coef,
+                     float* dlogits, int64_t rows, int vocab, smt_stream_t stream);
+
+/* Maximum mutual information (MaximumMutualInformationLoss in its collapsed form), n = count[0] scored rows (a DEVICE float),
+ * p_rv = exp(logit[r, v] - lse[r]) on scored rows, m_v = (1/n) sum_r p_rv (two-stage column sums in a fixed order),
+ * logm_v = log m_v and 0 where m_v = 0 (every p_rv is 0 there, so the value is never weighed):
+ *   loss = log(e + vocab - 1) - (1/n) sum_r p_{r,t_r} + sum_v m_v logm_v
+ *   fwd: row_out [rows, 2] = (p_{r,t_r} or 0, correct 0/1), lse, logm [vocab] (kept for bwd), ent [1] = sum_v m_v logm_v;
+ *        the constant and the row mean are the caller's.  No scored row: ent is nan.
+ *   bwd: dlogits[r, v] = coef[0] * p_rv * (logm_v - [v = t_r] - E_r + p_{r,t_r}),  E_r = sum_v p_rv logm_v  (the exact
+ *        gradient: the +1 of d(m log m)/dm cancels against its own row mean)
+ * The marginal m is formed over the rows of THIS call: under data parallelism every rank uses the marginal of its own rows,
+ * as the reference does under DDP (its loss sees the local batch only).
+ * workspace: smt_lm_mmi_workspace_bytes (column-sum partials per block of 16 rows, and the merged sums). */
+size_t smt_lm_mmi_workspace_bytes(int64_t rows, int vocab);
+int smt_lm_mmi_fwd(const float* logits, const int64_t* target, const float* count, float* row_out, float* lse, float* logm,
+                   float* ent, int64_t rows, int vocab, void* workspace, size_t workspace_bytes, smt_stream_t stream);
+int smt_lm_mmi_bwd(const float* logits, const int64_t* target, const float* lse, const float* logm, const float* coef,
+                   float* dlogits, int64_t rows, int vocab, smt_stream_t stream);
+
 /* Incremental decoding (TransformerLM.sample(causal=True)): one new token per step against a key/value cache.  fp32, eval
  * mode (no dropout), head dim 32, batch 1..32.  What changes from step to step -- the position, the tokens, the uniforms --
  * lives in device memory, so a step is a fixed sequence of launches with fixed arguments.  Like the dropout keys above,

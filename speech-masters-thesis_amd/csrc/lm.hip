@@ -8,11 +8,13 @@
 //   lm_add_ln       LayerNorm(x + dropout(h))                                                   (TransformerEncoderLayer, post-norm)
 //   lm_bias_relu    dropout(relu(h + b))  in place                                              (linear1 -> activation -> dropout)
 //   lm_ce           masked mean cross-entropy + accuracy over the next-token logits              (transformer_lm.py:121-128)
+//   lm_focal/lm_mmi the other two losses of the config (loss_type focal | mmi), same conventions as lm_ce     (losses.py:8-103)
 //
 // Activations are [B, L, C] fp32 rows (the fp32 parity path; head dim 32, any L with L * 3 * heads * 32 < 2^31).  Dropout masks come from the
 // counter-based generator of include/smt_hip.h ("dropout"): keep(i) of the element's linear index under a per-site key,
 // so the backward kernels recompute them.
 #include <algorithm>
+#include <cmath>
 
 #include "conv_common.h"
 
@@ -522,6 +524,126 @@ __global__ __launch_bounds__(256) void lm_ce_bwd_kernel(const float* __restrict_
   }
 }
 
+// ------------------------------------------------------------------------------------------------ focal and MMI losses
+// The row pass of both (one wave per row, the reductions of lm_ce_fwd_kernel): lse, argmax (lowest index among equal
+// maxima) and s = logit[target] - lse = log p_t.  Lane 0 then writes, for a scored row (0 everywhere on an unscored one)
+//   FOCAL  out = (-q^gamma s, correct), row_coef = gamma q^(gamma-1) p_t s - q^gamma   with p_t = exp(s), q = -expm1(s):
+//          the two powers of the row, taken once here so that the backward kernel has none
+//   MMI    out = (p_t, correct)
+template <bool FOCAL>
+__global__ __launch_bounds__(256) void lm_loss_row_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                          float* __restrict__ out, float* __restrict__ lse,
+                                                          float* __restrict__ row_coef, long long rows, int V, float gamma) {
+  const int lane = threadIdx.x & 63;
+  const long long row = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  if (row >= rows) return;
+  const long long tg = target[row];
+  float m = -INFINITY;
+  int am = 0x7fffffff;
+  for (int c = lane; c < V; c += 64) {
+    const float v = logits[row * V + c];
+    if (v > m) { m = v; am = c; }                              // increasing c per lane: first maximum
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64);
+    const int oa = __shfl_xor(am, o, 64);
+    if (om > m || (om == m && oa < am)) { m = om; am = oa; }   // lowest index among equal maxima (torch.argmax)
+  }
+  float z = 0.f;
+  for (int c = lane; c < V; c += 64) z += __expf(logits[row * V + c] - m);
+  z = wave_sum(z);
+  const float l = m + __logf(z);
+  if (lane != 0) return;
+  lse[row] = l;
+  out[2 * row + 1] = (tg >= 0 && am == (int)tg) ? 1.f : 0.f;
+  if (tg < 0) {
+    out[2 * row] = 0.f;
+    if (FOCAL) row_coef[row] = 0.f;
+    return;
+  }
+  const float s = fminf(logits[row * V + tg] - l, 0.f);        // log p_t; rounding may leave it an ulp above 0
+  if (!FOCAL) { out[2 * row] = __expf(s); return; }
+  if (gamma == 0.f) {                                          // the cross entropy: q^0 = 1 also at q = 0, and no first term
+    out[2 * row] = -s;
+    row_coef[row] = -1.f;
+    return;
+  }
+  const float pt = expf(s), q = -expm1f(s);                    // not 1 - exp(s): keeps its digits as p_t -> 1
+  const float qg1 = powf(q, gamma - 1.f), qg = qg1 * q;        // gamma >= 1 (checked by the host): finite at q = 0
+  out[2 * row] = -qg * s;
+  row_coef[row] = gamma * qg1 * pt * s - qg;
+}
+// the cross-entropy backward with a factor per row: dlogits = coef * c_r * (onehot - softmax), 0 on unscored rows
+__global__ __launch_bounds__(256) void lm_focal_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                           const float* __restrict__ lse, const float* __restrict__ row_coef,
+                                                           const float* __restrict__ coef, float* __restrict__ dlogits,
+                                                           long long rows, int V) {
+  const float g = coef[0];                                     // upstream gradient / number of scored rows
+  const long long total = rows * V;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const long long row = e / V;
+    const int c = (int)(e % V);
+    const long long tg = target[row];
+    dlogits[e] = tg >= 0 ? g * row_coef[row] * ((c == tg ? 1.f : 0.f) - __expf(logits[e] - lse[row])) : 0.f;
+  }
+}
+// MMI column sums, first stage: part [nblk][V] = sum of p_rv = exp(logit - lse) over the scored rows of a block of
+// rows_per_blk rows, rows in increasing order (lm_colsum_kernel merges the blocks, in block order)
+__global__ __launch_bounds__(256) void lm_mmi_colpart_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                             const float* __restrict__ lse, float* __restrict__ part,
+                                                             long long rows, int V, int rows_per_blk) {
+  const long long r0 = (long long)blockIdx.x * rows_per_blk;
+  for (int c = blockIdx.y * 256 + threadIdx.x; c < V; c += 256 * gridDim.y) {
+    float s = 0.f;
+    for (long long r = r0; r < min(rows, r0 + rows_per_blk); ++r)
+      if (target[r] >= 0) s += __expf(logits[r * V + c] - lse[r]);
+    part[(size_t)blockIdx.x * V + c] = s;
+  }
+}
+// MMI finishing pass, one workgroup: m_v = colsum[v] / n, logm[v] = log m_v (0 where m_v is not positive: every p_rv is 0
+// there, and the value is never weighed), ent[0] = sum_v m_v logm[v] in a fixed order (column v goes to thread v % 256,
+// then the lanes, then the four waves).  n = 0: m is nan, and so is ent.
+__global__ __launch_bounds__(256) void lm_mmi_finish_kernel(const float* __restrict__ colsum, const float* __restrict__ count,
+                                                            float* __restrict__ logm, float* __restrict__ ent, int V) {
+  __shared__ float red[4];
+  const float n = count[0];
+  float a = 0.f;
+  for (int c = threadIdx.x; c < V; c += 256) {
+    const float mv = colsum[c] / n;
+    const float lg = mv > 0.f ? logf(mv) : 0.f;
+    logm[c] = lg;
+    a += mv * lg;
+  }
+  a = wave_sum(a);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) ent[0] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+// MMI backward, one wave per row: E_r = sum_v p_rv logm_v, then dlogits = coef p_rv (logm_v - [v = t] - E_r + p_t)
+__global__ __launch_bounds__(256) void lm_mmi_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                         const float* __restrict__ lse, const float* __restrict__ logm,
+                                                         const float* __restrict__ coef, float* __restrict__ dlogits,
+                                                         long long rows, int V) {
+  const int lane = threadIdx.x & 63;
+  const long long row = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  if (row >= rows) return;
+  const long long tg = target[row];
+  if (tg < 0) {
+    for (int c = lane; c < V; c += 64) dlogits[row * V + c] = 0.f;
+    return;
+  }
+  const float g = coef[0], l = lse[row];
+  float e = 0.f;
+  for (int c = lane; c < V; c += 64) e += __expf(logits[row * V + c] - l) * logm[c];
+  e = wave_sum(e);
+  const float base = __expf(fminf(logits[row * V + tg] - l, 0.f)) - e;      // p_t - E_r (p_t as the row pass wrote it)
+  for (int c = lane; c < V; c += 64) {
+    const float p = __expf(logits[row * V + c] - l);
+    dlogits[row * V + c] = g * p * (logm[c] - (c == tg ? 1.f : 0.f) + base);
+  }
+}
+
 // keys[s] = fmix32(seed * 0x9E3779B1 + s * 0x7F4A7C15 + 1): the per-site dropout keys (smt_amd.convops.dropout_key) of the step
 // whose seed sits in device memory -- what a captured graph replays with a new seed every time
 __global__ void lm_make_keys_kernel(const unsigned* __restrict__ seed, unsigned* __restrict__ keys, int n) {
@@ -692,5 +814,81 @@ extern "C" int smt_lm_ce_bwd(const float* logits, const int64_t* target, const f
   SMT_CHECK_ARG(logits && target && lse && coef && dlogits, "smt_lm_ce_bwd: null pointer");
   lm_ce_bwd_kernel<<<lm_grid(rows * vocab), 256, 0, stream>>>(logits, (const long long*)target, lse, coef, dlogits, rows, vocab);
   SMT_CHECK_LAUNCH("lm_ce_bwd");
+  return 0;
+}
+
+// one wave per row, four rows per workgroup, at most 2^31 - 1 workgroups
+static const long long LM_LOSS_MAX_ROWS = 4LL * 0x7fffffffLL;
+
+extern "C" int smt_lm_focal_fwd(const float* logits, const int64_t* target, float* row_out, float* lse, float* row_coef,
+                                int64_t rows, int vocab, float gamma, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(rows >= 0 && rows <= LM_LOSS_MAX_ROWS, "smt_lm_focal_fwd: rows must be in 0..2^33 - 4 (got %lld)", (long long)rows);
+  SMT_CHECK_ARG(vocab >= 1, "smt_lm_focal_fwd: vocab must be >= 1 (got %d)", vocab);
+  SMT_CHECK_ARG(std::isfinite(gamma) && (gamma == 0.f || gamma >= 1.f),
+                "smt_lm_focal_fwd: gamma must be 0 or a finite value >= 1 (got %g; 0 < gamma < 1 is not built)", (double)gamma);
+  if (rows == 0) return 0;
+  SMT_CHECK_ARG(logits && target && row_out && lse && row_coef, "smt_lm_focal_fwd: null pointer");
+  lm_loss_row_kernel<true><<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(logits, (const long long*)target, row_out, lse, row_coef,
+                                                                         rows, vocab, gamma);
+  SMT_CHECK_LAUNCH("lm_focal_fwd");
+  return 0;
+}
+
+extern "C" int smt_lm_focal_bwd(const float* logits, const int64_t* target, const float* lse, const float* row_coef,
+                                const float* coef, float* dlogits, int64_t rows, int vocab, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(rows >= 0 && rows <= LM_LOSS_MAX_ROWS, "smt_lm_focal_bwd: rows must be in 0..2^33 - 4 (got %lld)", (long long)rows);
+  SMT_CHECK_ARG(vocab >= 1, "smt_lm_focal_bwd: vocab must be >= 1 (got %d)", vocab);
+  if (rows == 0) return 0;
+  SMT_CHECK_ARG(logits && target && lse && row_coef && coef && dlogits, "smt_lm_focal_bwd: null pointer");
+  lm_focal_bwd_kernel<<<lm_grid(rows * vocab), 256, 0, stream>>>(logits, (const long long*)target, lse, row_coef, coef, dlogits, rows,
+                                                                vocab);
+  SMT_CHECK_LAUNCH("lm_focal_bwd");
+  return 0;
+}
+
+// MMI workspace: the column-sum partials [ceil(rows / 16)][vocab] and, behind them, the merged sums [vocab]
+extern "C" size_t smt_lm_mmi_workspace_bytes(int64_t rows, int vocab) {
+  if (rows <= 0 || vocab < 1) return 0;
+  return ((size_t)((rows + 15) / 16) + 1) * (size_t)vocab * sizeof(float);
+}
+
+extern "C" int smt_lm_mmi_fwd(const float* logits, const int64_t* target, const float* count, float* row_out, float* lse,
+                              float* logm, float* ent, int64_t rows, int vocab, void* workspace, size_t workspace_bytes,
+                              smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(rows >= 0 && rows <= LM_LOSS_MAX_ROWS, "smt_lm_mmi_fwd: rows must be in 0..2^33 - 4 (got %lld)", (long long)rows);
+  SMT_CHECK_ARG(vocab >= 1, "smt_lm_mmi_fwd: vocab must be >= 1 (got %d)", vocab);
+  if (rows == 0) return 0;
+  SMT_CHECK_ARG(workspace_bytes >= smt_lm_mmi_workspace_bytes(rows, vocab), "smt_lm_mmi_fwd: workspace too small (%zu bytes, needs %zu)",
+                workspace_bytes, smt_lm_mmi_workspace_bytes(rows, vocab));
+  SMT_CHECK_ARG(logits && target && count && row_out && lse && logm && ent && workspace, "smt_lm_mmi_fwd: null pointer");
+  const int nblk = (int)((rows + 15) / 16);
+  float* part = (float*)workspace;                           // [nblk][vocab]
+  float* colsum = part + (size_t)nblk * vocab;               // [vocab]
+  lm_loss_row_kernel<false><<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(logits, (const long long*)target, row_out, lse, nullptr,
+                                                                          rows, vocab, 0.f);
+  SMT_CHECK_LAUNCH("lm_mmi_rows");
+  lm_mmi_colpart_kernel<<<dim3(nblk, std::min(65535, (vocab + 255) / 256)), 256, 0, stream>>>(logits, (const long long*)target, lse, part,
+                                                                                              rows, vocab, 16);
+  SMT_CHECK_LAUNCH("lm_mmi_colpart");
+  lm_colsum_kernel<<<(vocab + 63) / 64, 256, 0, stream>>>(part, colsum, nblk, vocab);
+  SMT_CHECK_LAUNCH("lm_colsum");
+  lm_mmi_finish_kernel<<<1, 256, 0, stream>>>(colsum, count, logm, ent, vocab);
+  SMT_CHECK_LAUNCH("lm_mmi_finish");
+  return 0;
+}
+
+extern "C" int smt_lm_mmi_bwd(const float* logits, const int64_t* target, const float* lse, const float* logm, const float* coef,
+                              float* dlogits, int64_t rows, int vocab, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(rows >= 0 && rows <= LM_LOSS_MAX_ROWS, "smt_lm_mmi_bwd: rows must be in 0..2^33 - 4 (got %lld)", (long long)rows);
+  SMT_CHECK_ARG(vocab >= 1, "smt_lm_mmi_bwd: vocab must be >= 1 (got %d)", vocab);
+  if (rows == 0) return 0;
+  SMT_CHECK_ARG(logits && target && lse && logm && coef && dlogits, "smt_lm_mmi_bwd: null pointer");
+  lm_mmi_bwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(logits, (const long long*)target, lse, logm, coef, dlogits, rows,
+                                                                    vocab);
+  SMT_CHECK_LAUNCH("lm_mmi_bwd");
   return 0;
 }

@@ -1,6 +1,9 @@
-"""Alternative training losses of the TransformerLM (reference models/transformer_lm/losses.py): selected by
-``config.model.loss_type`` in {"mmi", "focal"}; the default "ce" runs in the native cross-entropy kernel instead
-(smt_amd.lm.cross_entropy).  These two are a handful of row-wise torch ops on the [rows, vocab] logits."""
+"""Alternative training losses of the TransformerLM (reference models/transformer_lm/losses.py), selected by
+``config.model.loss_type`` in {"mmi", "focal"}, in their torch form: a handful of row-wise torch ops on the [rows, vocab]
+logits of the scored rows.  The model's train step does not call them: like the default "ce" (smt_amd.lm.cross_entropy) the
+two run in the native loss kernels, smt_amd.lm.mmi_loss and smt_amd.lm.focal_loss (csrc/lm.hip), which
+take all rows with target = -1 on the unscored ones and never synchronise with the host.  These classes are the definition
+the kernels are tested against (in float64) and stay available as ``TransformerLM.loss``."""
 import math
 
 import torch

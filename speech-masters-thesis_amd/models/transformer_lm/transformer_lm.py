@@ -3,7 +3,7 @@
 Same constructor keys, parameter names (a reference state_dict loads as is), ``forward`` / ``sample`` /
 ``reconstruct`` / ``load_vqvae`` surface and loss definition as the reference, which builds the stack from
 ``torch.nn.TransformerEncoder``.  Here a layer is five library GEMMs with everything between them in the HIP kernels
-of csrc/lm.hip (attention core, add + dropout + LayerNorm, bias + ReLU + dropout, embedding, cross entropy); activations
+of csrc/lm.hip (attention core, add + dropout + LayerNorm, bias + ReLU + dropout, embedding, the three losses); activations
 are batch-major [B, L, d] instead of the reference's [L, B, d].  Dropout uses the counter-based generator keyed by
 (step counter, site): site 0 = positional-encoding dropout, 1 + 4 i + {0, 1, 2, 3} = layer i's attention-weight,
 attention-output, feed-forward-inner and feed-forward-output dropouts.
@@ -123,14 +123,17 @@ class TransformerLM(TokenToWaveformModel):
         self.classifier = nn.Linear(m.d_model, m.vocab_size)
         self.vqvae = TransformerLM.load_vqvae(m.vqvae.log_dir, m.vqvae.ckpt_num)
         self.loss_type = m.loss_type
+        # all three losses run in the native loss kernels (smt_amd.lm.cross_entropy / mmi_loss / focal_loss); `self.loss`
+        # holds the torch form of the other two for callers that want it, `forward` does not call it
+        self.focal_gamma = float(m.get("focal_gamma", 10.0))    # the reference hard-codes 10
         if m.loss_type == "ce":
-            self.loss = None                                    # native kernel (smt_lm_ce_fwd / _bwd)
+            self.loss = None
         elif m.loss_type == "mmi":
             from models.transformer_lm.losses import MaximumMutualInformationLoss
             self.loss = MaximumMutualInformationLoss(num_classes=m.vocab_size)
         elif m.loss_type == "focal":
             from models.transformer_lm.losses import FocalLoss
-            self.loss = FocalLoss(gamma=10.0, reduction="mean")
+            self.loss = FocalLoss(gamma=self.focal_gamma, reduction="mean")
         else:
             raise ValueError(f"Loss function {m.loss_type} not supported")
         self._drop_seed = 0
@@ -186,7 +189,7 @@ class TransformerLM(TokenToWaveformModel):
         return F.linear(h, self.classifier.weight, self.classifier.bias)
 
     def forward(self, x, x_lengths, y, y_lengths, speaker=None):
-        b, l = x.shape
+        l = x.shape[1]
         lens = x_lengths.to(device=x.device, dtype=torch.int32)
         if self.training:
             self._drop_seed += 1                                # one fresh set of dropout masks per training step
@@ -198,13 +201,12 @@ class TransformerLM(TokenToWaveformModel):
         nxt = x[:, 1:]
         target = torch.full_like(x, -1)
         target[:, :-1] = torch.where(nxt >= TransformerLM.OFFSET, nxt - TransformerLM.OFFSET, -1)
-        if self.loss is None:
+        if self.loss_type == "ce":
             loss, accuracy, _ = K.cross_entropy(xh, target)
+        elif self.loss_type == "mmi":
+            loss, accuracy, _ = K.mmi_loss(xh, target)
         else:
-            rows = target.reshape(-1) >= 0
-            scored, tgt = xh.reshape(b * l, -1)[rows], target.reshape(-1)[rows]
-            loss = self.loss(scored, tgt)
-            accuracy = (scored.argmax(1) == tgt).sum().float() / rows.sum()
+            loss, accuracy, _ = K.focal_loss(xh, target, self.focal_gamma)
         if not self.training:
             keep = torch.arange(l - 1, device=x.device)[None, :] < lens[:, None]
             yh = self.reconstruct(xh[:, :-1, :].argmax(-1), keep[:, None, :])

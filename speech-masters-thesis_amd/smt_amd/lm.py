@@ -240,6 +240,92 @@ def cross_entropy(logits, target):
     return _CrossEntropy.apply(logits, target)
 
 
+class _FocalLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, gamma):
+        v = logits.shape[-1]
+        rows = logits.numel() // v
+        logits = _f32(logits)
+        target = target.contiguous()
+        row_out = torch.empty(rows, 2, device=logits.device, dtype=torch.float32)
+        lse = torch.empty(rows, device=logits.device, dtype=torch.float32)
+        row_coef = torch.empty(rows, device=logits.device, dtype=torch.float32)
+        N.check(N.lib().smt_lm_focal_fwd(N.ptr(logits), N.ptr(target), N.ptr(row_out), N.ptr(lse), N.ptr(row_coef), rows, v, gamma,
+                                         N.stream_ptr()), "smt_lm_focal_fwd")
+        count = (target >= 0).sum().to(torch.float32)
+        sums = row_out.sum(0)
+        ctx.save_for_backward(logits, target, lse, row_coef, count)
+        # no scored row: 0 like FocalLoss (the row sums are 0 then), where the mean of the cross entropy is nan
+        loss, acc = sums[0] / count.clamp_min(1.0), sums[1] / count
+        ctx.mark_non_differentiable(acc, count)                   # one call: a second one would replace the first
+        return loss, acc, count
+
+    @staticmethod
+    def backward(ctx, dloss, _dacc, _dcount):
+        logits, target, lse, row_coef, count = ctx.saved_tensors
+        v = logits.shape[-1]
+        rows = logits.numel() // v
+        coef = (dloss.to(torch.float32) / count.clamp_min(1.0)).reshape(1).contiguous()
+        dlogits = torch.empty_like(logits)
+        N.check(N.lib().smt_lm_focal_bwd(N.ptr(logits), N.ptr(target), N.ptr(lse), N.ptr(row_coef), N.ptr(coef), N.ptr(dlogits), rows, v,
+                                         N.stream_ptr()), "smt_lm_focal_bwd")
+        return dlogits, None, None
+
+
+def focal_loss(logits, target, gamma):
+    """(mean of (1 - p_t)^gamma * CE over rows with target >= 0, accuracy over the same rows, their number): FocalLoss of
+    models/transformer_lm/losses.py without class weights, on the device (smt_lm_focal_fwd / _bwd) and with the convention of
+    `cross_entropy`: target = -1 on the rows that are not scored.  gamma = 0 or >= 1 (else RuntimeError).  No scored row: loss 0
+    (as FocalLoss), accuracy nan."""
+    assert target.dtype == torch.int64
+    return _FocalLoss.apply(logits, target, float(gamma))
+
+
+class _MMILoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target):
+        v = logits.shape[-1]
+        rows = logits.numel() // v
+        logits = _f32(logits)
+        target = target.contiguous()
+        lib = N.lib()
+        dev = logits.device
+        row_out = torch.empty(rows, 2, device=dev, dtype=torch.float32)
+        lse = torch.empty(rows, device=dev, dtype=torch.float32)
+        logm = torch.empty(v, device=dev, dtype=torch.float32)
+        ent = torch.full((1,), float("nan"), device=dev, dtype=torch.float32)     # rows = 0 launches nothing
+        count = (target >= 0).sum().to(torch.float32)
+        ws_bytes = lib.smt_lm_mmi_workspace_bytes(rows, v)
+        ws = N.workspace.get(max(int(ws_bytes), 16), dev)          # consumed inside this call: nothing of it is kept for backward
+        N.check(lib.smt_lm_mmi_fwd(N.ptr(logits), N.ptr(target), N.ptr(count.reshape(1)), N.ptr(row_out), N.ptr(lse), N.ptr(logm),
+                                   N.ptr(ent), rows, v, N.ptr(ws), ws.numel(), N.stream_ptr()), "smt_lm_mmi_fwd")
+        sums = row_out.sum(0)
+        ctx.save_for_backward(logits, target, lse, logm, count)
+        # the constant is formed in double and rounded once, when it meets the fp32 tensor
+        loss, acc = math.log(math.e + v - 1) - sums[0] / count + ent[0], sums[1] / count
+        ctx.mark_non_differentiable(acc, count)
+        return loss, acc, count
+
+    @staticmethod
+    def backward(ctx, dloss, _dacc, _dcount):
+        logits, target, lse, logm, count = ctx.saved_tensors
+        v = logits.shape[-1]
+        rows = logits.numel() // v
+        coef = (dloss.to(torch.float32) / count).reshape(1).contiguous()
+        dlogits = torch.empty_like(logits)
+        N.check(N.lib().smt_lm_mmi_bwd(N.ptr(logits), N.ptr(target), N.ptr(lse), N.ptr(logm), N.ptr(coef), N.ptr(dlogits), rows, v,
+                                       N.stream_ptr()), "smt_lm_mmi_bwd")
+        return dlogits, None
+
+
+def mmi_loss(logits, target):
+    """(MaximumMutualInformationLoss over the rows with target >= 0, accuracy over the same rows, their number) on the device
+    (smt_lm_mmi_fwd / _bwd), target = -1 on the rows that are not scored.  The marginal is that of the rows of this call (one
+    rank's own rows under data parallelism, as in the reference).  No scored row: loss and accuracy nan."""
+    assert target.dtype == torch.int64
+    return _MMILoss.apply(logits, target)
+
+
 # ------------------------------------------------------------------------------------------------ incremental decoding
 # csrc/lm_decode.hip, include/smt_hip.h "Incremental decoding": eval mode, fp32, no autograd.  Every op writes into a buffer the
 # caller owns (DecodeState) and takes the position by value (`pos`) or from device memory (`pos_dev`, which overrides it).
