@@ -862,7 +862,20 @@ static void wave_launch(K kernel, int slots, int frames, int batch, hipStream_t 
       return 1;                                                             \
   }
 
-static int stft_frames(int T, int n_fft, int hop) { return (T + 2 * ((n_fft - hop) / 2) - n_fft) / hop + 1; }
+// floor((T + 2 pad - n_fft) / hop) + 1, as spectral.num_frames (Python's //): a signal that is shorter than one frame after the
+// padding has a NEGATIVE numerator and no frame at all -- C's truncating division gave 1 for -hop < numerator < 0
+static int stft_frames(int T, int n_fft, int hop) {
+  const int num = T + 2 * ((n_fft - hop) / 2) - n_fft;
+  return (num >= 0 ? num / hop : -((hop - 1 - num) / hop)) + 1;
+}
+// the reference raises on such a signal (its DFT conv kernel is longer than the padded input); t > pad alone lets it through
+// once hop > ~n_fft / 3
+#define SMT_CHECK_STFT_LENGTH(name, t, pad, n_fft, hop)                                                              \
+  do {                                                                                                               \
+    SMT_CHECK_ARG((t) > (pad), name ": signal shorter than the reflect padding");                                    \
+    SMT_CHECK_ARG((t) + 2 * (pad) >= (n_fft), name ": signal shorter than one frame (t=%d + 2 * pad=%d < n_fft=%d, hop=%d)", \
+                  (t), (pad), (n_fft), (hop));                                                                       \
+  } while (0)
 
 extern "C" int smt_stft_num_frames(int t, int n_fft, int hop) { return stft_frames(t, n_fft, hop); }
 
@@ -871,7 +884,7 @@ extern "C" int smt_stft_magnitude(const float* x, const float* window, const flo
   hipStream_t stream = (hipStream_t)stream_;
   SMT_CHECK_ARG(x && window && twiddle && mag, "smt_stft_magnitude: null pointer");
   const int pad = (n_fft - hop) / 2;
-  SMT_CHECK_ARG(t > pad, "smt_stft_magnitude: signal shorter than the reflect padding");
+  SMT_CHECK_STFT_LENGTH("smt_stft_magnitude", t, pad, n_fft, hop);
   const int frames = stft_frames(t, n_fft, hop);
   if (batch == 0 || frames <= 0) return 0;
   SMT_FFT_DISPATCH(n_fft, (frame_launch(stft_mag_kernel<N, NT>, frame_slots<N, NT>(0), NT, frames, batch, stream, x, window, (const cplx*)twiddle, mag, t, hop,
@@ -886,7 +899,7 @@ extern "C" int smt_stft_loss_fwd(const float* y, const float* yh, const int* len
   hipStream_t stream = (hipStream_t)stream_;
   SMT_CHECK_ARG(y && yh && window && twiddle && partial, "smt_stft_loss_fwd: null pointer");
   const int pad = (n_fft - hop) / 2;
-  SMT_CHECK_ARG(t > pad, "smt_stft_loss_fwd: signal shorter than the reflect padding");
+  SMT_CHECK_STFT_LENGTH("smt_stft_loss_fwd", t, pad, n_fft, hop);
   const int frames = stft_frames(t, n_fft, hop);
   if (batch == 0 || frames <= 0) return 0;
   if (fft_nt() == 64) {
@@ -911,10 +924,9 @@ extern "C" int smt_stft_loss_bwd(const float* y, const float* yh, const int* len
   hipStream_t stream = (hipStream_t)stream_;
   SMT_CHECK_ARG(y && yh && window && twiddle && coef && dyh, "smt_stft_loss_bwd: null pointer");
   const int pad = (n_fft - hop) / 2;
-  const int frames = stft_frames(t, n_fft, hop);
-  if (batch == 0 || t <= 0) return 0;
-  if (frames <= 0) { (void)hipMemsetAsync(dyh, 0, (size_t)batch * t * sizeof(float), stream); return 0; }
-  SMT_CHECK_ARG(t > pad, "smt_stft_loss_bwd: signal shorter than the reflect padding");
+  SMT_CHECK_STFT_LENGTH("smt_stft_loss_bwd", t, pad, n_fft, hop);
+  const int frames = stft_frames(t, n_fft, hop);        // >= 1 after the check
+  if (batch == 0) return 0;
   SMT_CHECK_ARG(workspace && workspace_bytes >= smt_stft_loss_bwd_workspace_bytes(batch, t, n_fft, hop),
                 "smt_stft_loss_bwd: workspace too small");
   float* rows = (float*)workspace;
@@ -937,7 +949,7 @@ extern "C" int smt_melspec(const float* x, const float* window, const float* twi
   hipStream_t stream = (hipStream_t)stream_;
   SMT_CHECK_ARG(x && window && twiddle && mel_basis && band && mel, "smt_melspec: null pointer");
   const int pad = (n_fft - hop) / 2;
-  SMT_CHECK_ARG(t > pad, "smt_melspec: signal shorter than the reflect padding");
+  SMT_CHECK_STFT_LENGTH("smt_melspec", t, pad, n_fft, hop);
   const int frames = stft_frames(t, n_fft, hop);
   if (batch == 0 || frames <= 0) return 0;
   if (fft_nt() == 64) {

@@ -45,11 +45,23 @@ def num_frames(t, n_fft, hop):
     return (t + 2 * ((n_fft - hop) // 2) - n_fft) // hop + 1
 
 
+def _check_length(what, t, n_fft, hop):
+    """The library's own argument check (SMT_CHECK_STFT_LENGTH, csrc/spectral.hip), made before the outputs are sized:
+    num_frames() is 0 or negative for such a signal, and a negative size would fail in torch.empty with another message."""
+    pad = (n_fft - hop) // 2
+    if t <= pad:
+        raise RuntimeError(f"{what} failed (status 1): {what}: signal shorter than the reflect padding")
+    if t + 2 * pad < n_fft:
+        raise RuntimeError(f"{what} failed (status 1): {what}: signal shorter than one frame "
+                           f"(t={t} + 2 * pad={pad} < n_fft={n_fft}, hop={hop})")
+
+
 @torch.no_grad()
 def stft_magnitude(x, n_fft, hop, win_length):
     """x [B, T] fp32 -> |STFT| [B, n_fft/2+1, frames] (STFT.forward, transforms.py:108-123)."""
     x = x.contiguous().float()
     b, t = x.shape
+    _check_length("smt_stft_magnitude", t, n_fft, hop)
     window, tw = _get_tables(n_fft, win_length, x.device)
     frames = num_frames(t, n_fft, hop)
     mag = torch.empty(b, n_fft // 2 + 1, frames, dtype=torch.float32, device=x.device)
@@ -79,6 +91,7 @@ def log_mel(x, mel_basis, band, n_fft, hop, win_length):
     """x [B, T] -> log-mel [B, n_mels, frames] in one kernel (5.25 B/sample algorithmic)."""
     x = x.contiguous().float()
     b, t = x.shape
+    _check_length("smt_melspec", t, n_fft, hop)
     window, tw = _get_tables(n_fft, win_length, x.device)
     frames = num_frames(t, n_fft, hop)
     n_mels = mel_basis.shape[0]
@@ -96,6 +109,7 @@ class _StftLoss(torch.autograd.Function):
     def forward(ctx, y, yh, lens, n_fft, hop, win_length, use_log):
         y, yh = y.contiguous().float(), yh.contiguous().float()
         b, t = y.shape
+        _check_length("smt_stft_loss_fwd", t, n_fft, hop)
         window, tw = _get_tables(n_fft, win_length, y.device)
         frames = num_frames(t, n_fft, hop)
         part = torch.empty(b, frames, 2, dtype=torch.float32, device=y.device)
