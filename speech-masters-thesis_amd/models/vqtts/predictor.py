@@ -13,7 +13,7 @@ Deviation: the reference's ``F.cross_entropy`` averages over every frame, padded
 import torch
 import torch.nn as nn
 
-from smt_amd import convops, glow, vqtts
+from smt_amd import convops, glow, packing, vqtts
 from smt_amd.lm import Drop
 
 from ..vqvae.resnet import ConvParams, _numbered
@@ -54,7 +54,7 @@ class CodePredictor(nn.Module):
         valid = torch.arange(x.shape[1], device=x.device)[None, :] < q_lens[:, None]
         return x * valid[..., None].to(x.dtype), valid
 
-    @convops.forward_scope
+    @packing.forward_scope
     def forward(self, x_enc, align_idx, q_lens, target=None, drop_seed=0, sample=None):
         """With ``target`` (q_rel [B, Tq] of the bottleneck): (loss_ce, q_acc, pred); frames without a token or at or past
         q_lens are not scored.  Without: pred [B, Tq] int32, the argmax of the code head or, with

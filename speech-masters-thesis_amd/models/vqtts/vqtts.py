@@ -24,7 +24,7 @@ from models.vqtts.bottleneck import Bottleneck
 from models.vqtts.predictor import CodePredictor
 from models.vqvae.encdec import Decoder, Encoder
 from models.vqvae.losses import MultiNormReconstructionLoss, MultiResolutionSpectralLoss
-from smt_amd import convops, glow, profiler, vqtts
+from smt_amd import glow, packing, profiler, vqtts
 
 PARTS = ("x_enc", "logw_enc", "x_lens", "y_enc", "q_lens", "align_idx", "durations", "q_rel", "y_d", "pred")
 PREDICTOR_SEED_BIT = 1 << 31        # the predictor's dropout seed is the step counter with this bit set
@@ -100,7 +100,7 @@ class VQTTS(TokenToWaveformModel):
         state_dict = {k: v for k, v in state_dict.items() if not k.endswith("_basis")}
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
-    @convops.forward_scope
+    @packing.forward_scope
     def forward(self, x, x_lengths, y, y_lengths, speaker=None, *, return_parts=False):
         """x [B, Tx] int64 token ids, y [B, 1, T] fp32 in [-1, 1] with T a multiple of the total stride ->
         ({loss, loss_recon, loss_stft, loss_commit, loss_dur, loss_align, loss_ce, yh [B, T]}, {q_acc, + the quantiser's

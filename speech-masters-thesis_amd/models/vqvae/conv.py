@@ -11,7 +11,7 @@ L -> ceil(L/s) (``mask[:, :, ::s]``, conv.py:9) and a transposed conv L -> L*s
 import torch
 import torch.nn as nn
 
-from smt_amd import convops
+from smt_amd import convops, packing
 from models.vqvae.resnet import ConvParams, GatedHiFiBlock
 
 
@@ -38,7 +38,7 @@ class EncoderConvBlock(nn.Module):
         self.n_sites = down_t * 2 * depth
         self.act_dtype = torch.float32
 
-    @convops.forward_scope
+    @packing.forward_scope
     def forward(self, x, lens, drop_seed=0):
         s = self.stride_t
         for i in range(self.down_t):
@@ -72,7 +72,7 @@ class DecoderConvBlock(nn.Module):
         self.blocks = nn.ModuleList(blocks)
         self.n_sites = down_t * 2 * depth
 
-    @convops.forward_scope
+    @packing.forward_scope
     def forward(self, x, lens, drop_seed=0):
         s = self.stride_t
         if self.down_t > 0:

@@ -2,7 +2,7 @@
 activations.  The decoder's final 1x1 projection acts on masked rows (encdec.py:82)."""
 import torch.nn as nn
 
-from smt_amd import convops
+from smt_amd import convops, packing
 from models.vqvae.conv import DecoderConvBlock, EncoderConvBlock
 from models.vqvae.resnet import ConvParams
 
@@ -23,7 +23,7 @@ class Encoder(nn.Module):
         self.level_blocks = nn.ModuleList(stages)
         self.n_sites = base - site_base
 
-    @convops.forward_scope
+    @packing.forward_scope
     def forward(self, x, lens, drop_seed=0):
         """x: [B, T] fp32 waveform when input_emb_width == 1, else [B, T, C]."""
         b, t = x.shape[0], x.shape[1]
@@ -52,7 +52,7 @@ class Decoder(nn.Module):
         self.out = ConvParams(output_emb_width, input_emb_width, 1)
         self.n_sites = base - site_base
 
-    @convops.forward_scope
+    @packing.forward_scope
     def forward(self, x, lens, drop_seed=0):
         b, t, c = x.shape
         assert c == self.output_emb_width

@@ -9,7 +9,7 @@ tools read the mutated config.  Internally activations are channels-last [B, T, 
 import torch
 import torch.nn as nn
 
-from smt_amd import convops
+from smt_amd import convops, packing
 from models.base import WaveformReconstructionModel
 from models.vqvae.bottleneck import Bottleneck
 from models.vqvae.encdec import Decoder, Encoder
@@ -79,7 +79,7 @@ class VQVAE(WaveformReconstructionModel):
         state_dict = {k: v for k, v in state_dict.items() if not k.endswith("_basis")}
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
-    @convops.forward_scope
+    @packing.forward_scope
     def forward(self, x, x_lengths, speaker=None, **vq_kwargs):
         """x [B, 1, T] float in [-1, 1]; x_lengths [B] -> (loss_dict, vq metrics)."""
         b, c, t = x.shape

@@ -7,12 +7,12 @@ queue from empty.  One captured graph of forward + backward takes the host out o
 
 What capture needs from a model: static input buffers; no host synchronisation inside forward / backward; and dropout keys
 that live in DEVICE memory (``model.enable_device_keys()``): a graph freezes by-value kernel arguments, so by-value keys
-would replay the same masks for ever.  Packed-weight copies (smt_amd.convops._PackCache) are refreshed by the first conv of
+would replay the same masks for ever.  Packed-weight copies (smt_amd.packing) are refreshed by the first conv of
 every training forward (one batched launch); that launch is captured with the rest and simply runs every replay.  Optimizer, scheduler, NaN guard, gradient clipping and the parameter EMA stay eager.
 """
 import torch
 
-from . import convops
+from . import packing
 
 
 def stale_autograd_graphs(params):
@@ -47,16 +47,18 @@ class GraphedStep:
     hipStreamEndCapture.  The constructor checks (``stale_autograd_graphs``) and raises ``RuntimeError`` instead; it also
     turns torch's own warning about it, should it fire during the eager warm-up, into the same error.
 
-    The graph holds raw pointers into the packed conv-weight copies of ``smt_amd.convops``: the entries captured are kept
-    alive by this object, and ``replay`` refuses to run once they have been thrown away (``EMA.swap`` around validation,
-    ``load_checkpoint``: ``convops.invalidate_packed_weights``) -- build a new GraphedStep afterwards."""
+    The graph holds raw pointers into the packed conv-weight copies of ``smt_amd.packing`` and into their device table:
+    this object pins them (``packing.pin``), and ``replay`` refuses to run once any copy has been thrown away -- the copies
+    of a model that no longer exists were pruned (the captured repack launch reads a table that still lists them), or the
+    cache overflowed -- build a new GraphedStep afterwards.  Invalidation (``EMA.swap`` around validation,
+    ``load_checkpoint``, an optimizer step) only refreshes the copies in place and leaves the graph valid."""
 
     def __init__(self, model, fn, inputs, zero_grad, warmup=3):
         assert model.training and all(t is None or t.is_cuda for t in inputs)
         import gc
         import warnings
         gc.collect()                           # drop unreachable autograd graphs of earlier iterations (see above)
-        convops._pack_cache.prune()            # ... and the packed copies of models that no longer exist
+        packing.prune()                        # ... and the packed copies of models that no longer exist
         stale = stale_autograd_graphs(list(model.parameters()))
         if stale:
             raise RuntimeError(
@@ -76,8 +78,8 @@ class GraphedStep:
                 loss_dict, _ = fn(*self.static)
                 loss_dict["loss"].backward()
                 del loss_dict, _               # no autograd graph of a warm-up pass may outlive it (see the class docstring)
-            if convops._pack_cache.entries:
-                convops._pack_cache.repack_all()   # builds the device-side pack table the captured launch will reuse
+            if packing.entry_count():
+                packing.repack_all()           # builds the device-side pack table the captured launch will reuse
         main.wait_stream(side)
         mismatch = [w for w in caught if "AccumulateGrad node's stream does not match" in str(w.message)]
         for w in caught:
@@ -87,24 +89,23 @@ class GraphedStep:
             raise RuntimeError("GraphedStep: " + str(mismatch[0].message))
         zero_grad()                            # set_to_none: backward inside the capture allocates .grad from the graph's pool
         self.graph = torch.cuda.CUDAGraph()
-        repacks = convops._pack_cache.repacks
+        repacks = packing.repacks()
         with torch.cuda.graph(self.graph):
-            # a training forward of the VQ-VAE repacks the conv weights at its first conv (convops.training_forward): that
+            # a training forward of the VQ-VAE repacks the conv weights at its first conv (packing.training_forward): that
             # launch is captured here and runs on every replay; models without packed weights capture nothing for it
             self.loss_dict, self.metrics = fn(*self.static)
             self.loss_dict["loss"].backward()
-        assert convops._pack_cache.repacks - repacks <= 1, "one batched repack per captured step"
+        assert packing.repacks() - repacks <= 1, "one batched repack per captured step"
         # everything the captured launches point at must outlive the graph: the packed copies and their device-side table
-        self._pack_refs = (list(convops._pack_cache.entries.values()), convops._pack_cache.table)
-        self._pack_epoch = convops.pack_epoch()
+        self._packs = packing.pin()
         model._drop_seed -= 1                  # capture ran the Python side of forward once without executing the device increment
         self.loss_dict = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in self.loss_dict.items()}
 
     def replay(self, *inputs):
-        if convops.pack_epoch() != self._pack_epoch:
-            raise RuntimeError("GraphedStep.replay: the packed conv-weight copies this graph was captured with have been "
-                               "invalidated since (EMA.swap / load_checkpoint / invalidate_packed_weights); capture a new "
-                               "GraphedStep")
+        if not self._packs.valid():
+            raise RuntimeError("GraphedStep.replay: packed conv-weight copies that this graph's repack launch reads have been "
+                               "thrown away since (the copies of a dead model were pruned, or the pack cache overflowed); "
+                               "capture a new GraphedStep")
         for dst, src in zip(self.static, inputs):
             if dst is not None:
                 dst.copy_(src, non_blocking=True)

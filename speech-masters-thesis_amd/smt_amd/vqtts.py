@@ -12,7 +12,7 @@ import math
 
 import torch
 
-from . import convops
+from . import packing
 from . import native as N
 from . import profiler
 
@@ -108,7 +108,7 @@ def align_loss(x_enc, y_enc, idx, denom):
 class WeightSplit:
     """The bf16-pair split of one projection weight (smt_vqtts_code_head_prepare), kept by whoever owns the weight and
     redone when the weight has or may have changed.  The key is the weight's (data_ptr, _version) -- the rule of
-    ``Bottleneck._search_prep`` -- and the generation of ``convops.mark_packed_weights_dirty``: a fused optimizer step
+    ``Bottleneck._search_prep`` -- and the generation of ``packing.mark_dirty``: a fused optimizer step
     writes the parameters without moving ``_version``, and every optimizer step, every training forward of a module of this
     build, ``EMA.swap`` and ``load_checkpoint`` announce themselves there (the packed conv operands obey the same signal)."""
 
@@ -116,7 +116,7 @@ class WeightSplit:
         self.key, self.buf = None, None
 
     def get(self, weight):
-        key = (weight.data_ptr(), weight._version, convops.packed_weights_generation(), tuple(weight.shape), weight.device)
+        key = (weight.data_ptr(), weight._version, packing.generation(), tuple(weight.shape), weight.device)
         if self.key != key:
             v, c = weight.shape
             lib = N.lib()

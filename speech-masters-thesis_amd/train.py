@@ -150,8 +150,8 @@ def load_checkpoint(path, model, optimizer, scheduler, ema, device):
     ckpt = torch.load(path, map_location=device, weights_only=True)
     model.load_state_dict(ckpt["model"])
     restore_extra_train_state(model, ckpt.get("extra"))     # codebook accumulators, dropout counter (or restore_k)
-    from smt_amd import convops
-    convops.invalidate_packed_weights()
+    from smt_amd import packing
+    packing.invalidate()
     optimizer.load_state_dict(ckpt["optim"])
     scheduler.load_state_dict(ckpt["sched"])
     ema.load_state_dict(ckpt["ema"])

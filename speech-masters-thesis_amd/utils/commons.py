@@ -81,7 +81,7 @@ def get_optimizer(config, model):
                                     weight_decay=float(opt.weight_decay))
     else:
         raise ValueError(f"Didn't recognize optimizer name {opt.name}")
-    # (the packed operand copies of the conv weights follow every update by themselves: smt_amd.convops.training_forward)
+    # (the packed operand copies of the conv weights follow every update by themselves: smt_amd.packing.training_forward)
     sched = config.get("scheduler", None)
     from utils import lr_scheduler as S
     if not sched:

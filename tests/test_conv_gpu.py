@@ -534,7 +534,7 @@ def test_fused_k1_backward_matches_separate_kernels(b, t):
 def test_pack_cache_follows_in_place_weight_updates():
     """Packed operand copies are cached per (weight storage, layout) and repacked in one table-driven launch when a
     weight's version changes: outputs must follow an in-place (optimizer-style) update, forward and backward."""
-    from smt_amd import convops as C
+    from smt_amd import convops as C, packing
     g = torch.Generator(device="cuda").manual_seed(5)
     x = torch.randn(2, 300, 32, device="cuda", generator=g, requires_grad=True)
     ws = [torch.nn.Parameter(torch.randn(64, 32, 3, device="cuda", generator=g) * 0.1) for _ in range(3)]
@@ -553,16 +553,16 @@ def test_pack_cache_follows_in_place_weight_updates():
     first = run()
     import gc
     gc.collect()
-    C._pack_cache.prune()                                 # entries of dead parameters (earlier tests) go at the next repack anyway
-    n_entries = len(C._pack_cache.entries)
+    packing.prune()                                       # entries of dead parameters (earlier tests) go at the next repack anyway
+    n_entries = packing.entry_count()
     again = run()                                         # nothing changed: cache hits, no new entries
-    assert len(C._pack_cache.entries) == n_entries
+    assert packing.entry_count() == n_entries
     assert all(torch.equal(a[0], b_[0]) and torch.equal(a[1], b_[1]) for a, b_ in zip(first, again))
     with torch.no_grad():
         for w in ws:
             w.mul_(-0.5)                                  # in-place update bumps the version -> batched repack
     changed = run()                                       # run() re-checks against torch with the NEW weights
-    assert len(C._pack_cache.entries) == n_entries
+    assert packing.entry_count() == n_entries
     assert not torch.equal(first[0][0], changed[0][0]) and not torch.equal(first[0][1], changed[0][1])
 
 

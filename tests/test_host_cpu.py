@@ -170,40 +170,39 @@ def test_optimizer_scheduler_ema_and_checkpoint_layout(tmp_path):
 
 
 def test_training_forward_scope_marks_packed_weights_stale_once_per_pass():
-    """smt_amd.convops.training_forward: the outermost scope of a TRAINING forward marks the packed operand copies stale
+    """smt_amd.packing.training_forward: the outermost scope of a TRAINING forward marks the packed operand copies stale
     (one repack per pass), nested scopes and eval-mode scopes do not; every torch optimizer's step does, whoever built it."""
     import torch
-    from smt_amd import convops
-    c = convops._pack_cache
-    g0 = c.generation
-    with convops.training_forward(True):
-        with convops.training_forward(True):
+    from smt_amd import packing
+    g0 = packing.generation()
+    with packing.training_forward(True):
+        with packing.training_forward(True):
             pass
-        with convops.training_forward(True):
+        with packing.training_forward(True):
             pass
-    assert c.generation == g0 + 1 and c.dirty
-    with convops.training_forward(False):
-        with convops.training_forward(True):      # a training sub-module inside an eval-mode parent still refreshes
+    assert packing.generation() == g0 + 1 and packing._is_dirty()
+    with packing.training_forward(False):
+        with packing.training_forward(True):      # a training sub-module inside an eval-mode parent still refreshes
             pass
-    assert c.generation == g0 + 2
-    with convops.training_forward(False):
+    assert packing.generation() == g0 + 2
+    with packing.training_forward(False):
         pass
-    assert c.generation == g0 + 2
+    assert packing.generation() == g0 + 2
     p = torch.nn.Parameter(torch.zeros(3))
     p.grad = torch.ones(3)
     torch.optim.SGD([p], lr=0.1).step()           # an optimizer nobody registered anything on
-    assert c.generation == g0 + 3
+    assert packing.generation() == g0 + 3
 
     class M(torch.nn.Module):
-        @convops.forward_scope
+        @packing.forward_scope
         def forward(self, x):
             return x + 1
     m = M()
     m(torch.zeros(1))
-    assert c.generation == g0 + 4
+    assert packing.generation() == g0 + 4
     m.eval()
     m(torch.zeros(1))
-    assert c.generation == g0 + 4
+    assert packing.generation() == g0 + 4
 
 
 def test_stale_autograd_graph_probe():

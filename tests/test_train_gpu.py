@@ -218,7 +218,7 @@ def test_packed_conv_weights_follow_the_optimizer(tmp_path):
     away before every forward, bit for bit (the step is reproducible), and the loss must actually move."""
     import train as trainlib
     from oracle import vqvae_oracle as orc
-    from smt_amd import convops
+    from smt_amd import packing
     from utils import config as C
     from utils.commons import get_model, get_optimizer
     cfg = C.merge(C.load(os.path.join(PKG, "configs/models/vqvae.yaml")),
@@ -240,7 +240,7 @@ def test_packed_conv_weights_follow_the_optimizer(tmp_path):
         losses = []
         for step in range(3):
             if invalidate:
-                convops.invalidate_packed_weights()
+                packing.invalidate()
             loss_dict, _ = trainlib.train_step(global_step=step, batch=batch, config=cfg, model=model, ema=ema, optimizer=opt,
                                                scheduler=sched, device=dev)
             losses.append(float(loss_dict["loss"].detach()))
@@ -258,7 +258,7 @@ def test_an_optimizer_built_by_the_caller_trains_the_same_weights(tmp_path):
     build's get_optimizer bit for bit, and so do three steps whose parameters are moved by a raw ``p.data`` write that no
     hook and no version counter can see."""
     from oracle import vqvae_oracle as orc
-    from smt_amd import convops
+    from smt_amd import packing
     from utils import config as C
     from utils.commons import get_model, get_optimizer
     cfg = C.merge(C.load(os.path.join(PKG, "configs/models/vqvae.yaml")),
@@ -293,10 +293,10 @@ def test_an_optimizer_built_by_the_caller_trains_the_same_weights(tmp_path):
                 new = [p.detach().clone() for p in model.parameters()]
                 for p, old in zip(model.parameters(), shadow):
                     p.data.copy_(old)
-                convops._pack_cache.dirty = False       # pretend nobody told the cache anything
+                packing._is_dirty(clear=True)           # pretend nobody told the cache anything
                 for p, n in zip(model.parameters(), new):
                     p.data.copy_(n)
-                convops._pack_cache.dirty = False
+                packing._is_dirty(clear=True)
             else:
                 opt.step()
             losses.append(float(loss_dict["loss"].detach()))

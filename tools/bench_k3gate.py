@@ -12,7 +12,7 @@ w1 = [torch.randn(128, 64, 1, device="cuda", generator=g) / 8 for _ in range(4)]
 b3 = [torch.randn(128, device="cuda", generator=g) for _ in range(4)]
 b1 = [torch.randn(128, device="cuda", generator=g) for _ in range(4)]
 z = torch.empty_like(u2); gg = torch.empty_like(x)
-w3p, w1p = C._pack_cat_fwd_swz(w3, torch.bfloat16), C._pack_cat_fwd(w1, torch.bfloat16)
+w3p, w1p = C._pack_cat_fwd(w3, torch.bfloat16, swizzle=True), C._pack_cat_fwd(w1, torch.bfloat16)
 b3c, b1c = C._cat_bias(b3), C._cat_bias(b1)
 fn = lambda: C._conv_k3gate(u2, x, w3p, w1p, b3c, b1c, z, gg, None)
 for _ in range(3): fn()
