@@ -133,3 +133,28 @@ class SyntheticTTSAudio(Dataset):
         return token, tx, None, None, audio, length, None
 
     collate = staticmethod(LJSpeech.collate)
+
+
+class SyntheticTTSSpeakers(SyntheticTTS):
+    """``SyntheticTTS`` for ``n_speakers`` voices: the same seeded items plus a seeded speaker id in slot 7, and frames that
+    depend on the speaker as well -- every speaker shifts the token basis by its own offset vector, so that a speaker
+    embedding has something to learn.  item = (token, Tx, spect [n_mels, Ty], Ty, None, None, speaker id); ``collate`` stacks
+    the ids to int64 [B]."""
+
+    def __init__(self, config, split):
+        super().__init__(config, split)
+        self.n_speakers = int(config.dataset.get("n_speakers", 8))
+        assert self.n_speakers >= 1
+
+    def __getitem__(self, index):
+        token, tx, spect, ty, _, _, _ = super().__getitem__(index)
+        g = torch.Generator().manual_seed(90_000 + self.offset + index)
+        speaker = int(torch.randint(0, self.n_speakers, (1,), generator=g))
+        offsets = torch.randn(self.n_speakers, self.n_mels, generator=torch.Generator().manual_seed(11))
+        return token, tx, spect + 1.5 * offsets[speaker][:, None], ty, None, None, speaker
+
+    @staticmethod
+    def collate(batch):
+        out = list(LJSpeech.collate(batch))
+        out[6] = torch.tensor([item[6] for item in batch], dtype=torch.long)
+        return tuple(out)
