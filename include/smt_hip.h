@@ -348,6 +348,11 @@ int smt_conv1d_ntc(const smt_conv_desc* desc, smt_stream_t stream);
 /* Name of the kernel smt_conv1d_ntc dispatches this descriptor to ("conv_gemm", "conv_gemm_dma", "conv_ws",
  * "conv_ws_pipe", "conv1x1_dma", "conv1x1_fold", "conv_k1act"): for profilers and tests; no device work. */
 const char* smt_conv1d_kernel_name(const smt_conv_desc* desc);
+/* The plan behind the name "conv_gemm_dma", which covers two tile sizes with and without dilation classes: *tile_rows =
+ * output rows per workgroup (128 or 256), *row_classes = number of row classes the launch is split into (the dilation
+ * where the class decomposition is on, else 1).  Both are 0 for a descriptor that any other kernel runs (the
+ * weight-stationary kernels plan their own tiles).  Answered by the launch's own plan; no device work.  Returns 0. */
+int smt_conv1d_dma_plan(const smt_conv_desc* desc, int* tile_rows, int* row_classes);
 
 /* Weight (+ bias) gradient of the same convolution:
  *   dw[j][co][ci] = sum_{b,t} dy[b, t*out_stride + out_offset, co] * x[b, t*stride + j*dil - pad, ci]

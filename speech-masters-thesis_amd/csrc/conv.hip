@@ -1293,3 +1293,19 @@ extern "C" const char* smt_conv1d_kernel_name(const smt_conv_desc* d) {
     default: return "conv_gemm";
   }
 }
+
+// What plan_conv_dma decided for a descriptor that pick_kernel sends to conv_gemm_dma_kernel: the tile's rows and the
+// number of dilation classes.  Zeros for every other kernel.
+extern "C" int smt_conv1d_dma_plan(const smt_conv_desc* d, int* tile_rows, int* row_classes) {
+  if (tile_rows) *tile_rows = 0;
+  if (row_classes) *row_classes = 0;
+  if (!d) return 0;
+  ConvArgs p;
+  conv_args_from_desc(d, p);
+  if (pick_kernel(d, p) != K_DMA) return 0;
+  DmaPlan pl;
+  plan_conv_dma(p, pl);                      // sets p.rs and pl.big, as in launch_conv_dma
+  if (tile_rows) *tile_rows = pl.big ? 256 : 128;
+  if (row_classes) *row_classes = p.rs;
+  return 0;
+}

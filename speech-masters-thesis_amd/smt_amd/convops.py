@@ -209,6 +209,13 @@ def _kernel_of(desc):
     return N.lib().smt_conv1d_kernel_name(ctypes.byref(desc)).decode()
 
 
+def _dma_plan_of(desc):
+    """(tile rows, row classes) of the conv_gemm_dma launch of this descriptor, (0, 0) for any other kernel."""
+    rows, classes = ctypes.c_int(0), ctypes.c_int(0)
+    N.check(N.lib().smt_conv1d_dma_plan(ctypes.byref(desc), ctypes.byref(rows), ctypes.byref(classes)), "smt_conv1d_dma_plan")
+    return rows.value, classes.value
+
+
 def _launch(desc, name, flops=0.0, nbytes=0.0):
     dtype = "bf16" if desc.dtype == SMT_BF16 else "f32"
     name = _kernel_of(desc) + ":" + name.replace("conv_", "")      # e.g. conv_gemm_dma:fwd

@@ -47,6 +47,7 @@ _SIGNATURES = {
     "smt_pack_weights_batched": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr]),
     "smt_conv1d_ntc": (c_int, [c_ptr, c_ptr]),
     "smt_conv1d_kernel_name": (ctypes.c_char_p, [c_ptr]),
+    "smt_conv1d_dma_plan": (c_int, [c_ptr, c_ptr, c_ptr]),
     "smt_conv1d_wgrad_workspace_bytes": (c_size, [c_ptr]),
     "smt_conv1d_wgrad_kernel_name": (ctypes.c_char_p, [c_ptr]),
     "smt_conv1d_wgrad": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
