@@ -680,6 +680,33 @@ int smt_glow_gate_fwd(const float* a, float* acts, int64_t rows, int hidden, uin
                       uint32_t drop_thresh16, float drop_scale, smt_stream_t stream);
 int smt_glow_gate_bwd(const float* a, const float* dacts, float* da, int64_t rows, int hidden, uint32_t drop_key,
                       const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream);
+/* WN gate with a speaker condition (WN.forward with g, submodules.py:212-224): a [batch, t, 2 hidden], one vector per item
+ * cond[b * cond_stride + 0 .. 2 hidden) added AFTER the dropout of a:
+ *   acts[b, t, c] = tanh(d(a[b, t, c]) + cond[b, c]) sigmoid(d(a[b, t, hidden + c]) + cond[b, hidden + c]),
+ * d and its counter as in smt_glow_gate_fwd; cond = 0 gives that function's result bit for bit.
+ * bwd: one pass writes da (every row) and per-item partial sums, a second launch adds them in a fixed order (no float
+ * atomics, bitwise reproducible): dcond[b * dcond_stride + 0 .. 2 hidden) = the sum over the rows t < lens[b] (NULL: all) of
+ * the gate's derivative by its argument, without the dropout factor.  cond and dcond are two tensors with two layouts: each
+ * pointer has its own item stride, in floats, and both strides must be >= 2 hidden.
+ * workspace >= smt_glow_gate_cond_workspace_bytes(batch, t, 2 hidden) = batch * ceil(t / 64) * cols floats. */
+size_t smt_glow_gate_cond_workspace_bytes(int batch, int t, int cols);
+int smt_glow_gate_cond_fwd(const float* a, const float* cond, int64_t cond_stride, float* acts, int batch, int t, int hidden,
+                           uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale,
+                           smt_stream_t stream);
+int smt_glow_gate_cond_bwd(const float* a, const float* dacts, const float* cond, int64_t cond_stride, const int* lens, float* da,
+                           float* dcond, int64_t dcond_stride, int batch, int t, int hidden, uint32_t drop_key,
+                           const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, void* workspace,
+                           size_t workspace_bytes, smt_stream_t stream);
+/* The duration predictor's input with a speaker (TextEncoder.forward, modules.py:117-129): out [batch, t, width],
+ * out[b, t, :] = (x[b, t, 0 .. hidden) | g[b * g_stride + 0 .. gin) | zeros) on the rows t < lens[b] (NULL: all), zero rows
+ * after; width >= hidden + gin (the next channel count the convolution takes), g_stride >= gin.
+ * item_colsum, its gradient by g (x enters detached): dg[b * dg_stride + j] = sum over t < lens[b] of
+ * dout[b, t, col0 + j], j < ncol, rows of width floats, two-stage in a fixed order;
+ * workspace >= smt_glow_gate_cond_workspace_bytes(batch, t, ncol). */
+int smt_glow_bcast_concat(const float* x, const float* g, int64_t g_stride, const int* lens, float* out, int batch, int t, int hidden,
+                          int gin, int width, smt_stream_t stream);
+int smt_glow_item_colsum(const float* dout, const int* lens, float* dg, int64_t dg_stride, int batch, int t, int width, int col0,
+                         int ncol, void* workspace, size_t workspace_bytes, smt_stream_t stream);
 /* Plain dropout over the linear element index: y[i] = x[i] keep(i) (DurationPredictor, submodules.py:629-633). */
 int smt_glow_dropout(const float* x, float* y, int64_t n, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16,
                      float drop_scale, smt_stream_t stream);

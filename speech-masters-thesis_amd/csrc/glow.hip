@@ -188,6 +188,108 @@ __global__ __launch_bounds__(GL_NT) void gl_gate_bwd_kernel(const float* __restr
   }
 }
 
+// ------------------------------------------------------------------------------------------------ WN gate with a speaker condition
+// x + c, with c == 0 leaving x as it is (x + 0 would turn -0 into +0): cond = 0 reproduces the unconditioned gate bit for bit
+__device__ __forceinline__ float gl_add_cond(float x, float c) { return c == 0.f ? x : x + c; }
+// a [B, T, 2H], cond[b * cond_stride + 0 .. 2H) (one vector per item, added AFTER the dropout of a) -> acts [B, T, H]
+__global__ __launch_bounds__(GL_NT) void gl_gate_cond_fwd_kernel(const float* __restrict__ a, const float* __restrict__ cond,
+                                                                 long long cond_stride, float* __restrict__ acts, int B, int T, int H,
+                                                                 unsigned key, const unsigned* __restrict__ key_dev, unsigned thr,
+                                                                 float dscale) {
+  if (key_dev) key = *key_dev;
+  const long long total = (long long)B * T * H;
+  for (long long e = (long long)blockIdx.x * GL_NT + threadIdx.x; e < total; e += (long long)gridDim.x * GL_NT) {
+    const long long r = e / H;
+    const int c = (int)(e % H);
+    const float* cb = cond + (r / T) * cond_stride;
+    const unsigned long long it = (unsigned long long)r * 2 * H + c, is = it + H;
+    const float tv = gl_add_cond(a[it] * gl_keep(it, key, thr, dscale), cb[c]);
+    const float sv = gl_add_cond(a[is] * gl_keep(is, key, thr, dscale), cb[H + c]);
+    acts[e] = tanhf(tv) * gl_sigmoid(sv);
+  }
+}
+
+constexpr int GL_CT = 64;        // columns per workgroup of the per-item reductions: one wave across, GL_NT / 64 groups of rows down
+// Workgroup (item b, chunk ch of GL_ROWS rows, tile of GL_CT columns): wave w takes the rows t0 + w, t0 + w + 4, ...  One pass
+// writes da (every row) and part[b][ch][0 .. 2H) = the sums over the chunk's rows t < lens[b] of the gate's derivative by its
+// argument -- d cond, which enters after the dropout and so carries no dropout factor.  A workgroup never spans two items.
+__global__ __launch_bounds__(GL_NT) void gl_gate_cond_bwd_kernel(const float* __restrict__ a, const float* __restrict__ dacts,
+                                                                 const float* __restrict__ cond, long long cond_stride,
+                                                                 const int* __restrict__ lens, float* __restrict__ da,
+                                                                 float* __restrict__ part, int T, int H, int chunks, unsigned key,
+                                                                 const unsigned* __restrict__ key_dev, unsigned thr, float dscale) {
+  if (key_dev) key = *key_dev;
+  __shared__ float red[GL_NT / 64][2][GL_CT];
+  const int b = blockIdx.x / chunks, ch = blockIdx.x % chunks;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c = blockIdx.y * GL_CT + lane;
+  const int t0 = ch * GL_ROWS, t1 = min(T, t0 + GL_ROWS);
+  const int len = lens ? lens[b] : T;
+  float st = 0.f, ss = 0.f;
+  if (c < H) {
+    const float ct = cond[b * cond_stride + c], cs = cond[b * cond_stride + H + c];
+    for (int t = t0 + wv; t < t1; t += GL_NT / 64) {
+      const unsigned long long row = (unsigned long long)b * T + t, it = row * 2 * H + c, is = it + H;
+      const float kt = gl_keep(it, key, thr, dscale), ks = gl_keep(is, key, thr, dscale);
+      const float th = tanhf(gl_add_cond(a[it] * kt, ct)), sg = gl_sigmoid(gl_add_cond(a[is] * ks, cs)), g = dacts[row * H + c];
+      const float dt = g * sg * (1.f - th * th), ds = g * th * sg * (1.f - sg);
+      da[it] = dt * kt;
+      da[is] = ds * ks;
+      if (t < len) { st += dt; ss += ds; }
+    }
+  }
+  red[wv][0][lane] = st;
+  red[wv][1][lane] = ss;
+  __syncthreads();
+  if (wv < 2 && c < H)                         // wave 0: the tanh half, wave 1: the sigmoid half
+    part[(size_t)blockIdx.x * 2 * H + wv * H + c] = ((red[0][wv][lane] + red[1][wv][lane]) + red[2][wv][lane]) + red[3][wv][lane];
+}
+// the same tiling for a plain sum: part[b][ch][j] = sum over the chunk's rows t < lens[b] of src[b, t, col0 + j], j < ncol
+__global__ __launch_bounds__(GL_NT) void gl_item_colsum_part_kernel(const float* __restrict__ src, const int* __restrict__ lens,
+                                                                    float* __restrict__ part, int T, int W, int col0, int ncol,
+                                                                    int chunks) {
+  __shared__ float red[GL_NT / 64][GL_CT];
+  const int b = blockIdx.x / chunks, ch = blockIdx.x % chunks;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c = blockIdx.y * GL_CT + lane;
+  const int t0 = ch * GL_ROWS, t1 = min(min(T, t0 + GL_ROWS), lens ? lens[b] : T);
+  float s = 0.f;
+  if (c < ncol)
+    for (int t = t0 + wv; t < t1; t += GL_NT / 64) s += src[((size_t)b * T + t) * W + col0 + c];
+  red[wv][lane] = s;
+  __syncthreads();
+  if (wv == 0 && c < ncol) part[(size_t)blockIdx.x * ncol + c] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+}
+// part[item][chunk][ncol] -> out[item * out_stride + col] = sum over the item's chunks in index order
+__global__ __launch_bounds__(GL_NT) void gl_item_colsum_kernel(const float* __restrict__ part, int items, int chunks, int ncol,
+                                                               float* __restrict__ out, long long out_stride) {
+  const long long total = (long long)items * ncol;
+  for (long long e = (long long)blockIdx.x * GL_NT + threadIdx.x; e < total; e += (long long)gridDim.x * GL_NT) {
+    const int b = (int)(e / ncol), col = (int)(e % ncol);
+    float s = 0.f;
+    for (int k = 0; k < chunks; ++k) s += part[((size_t)b * chunks + k) * ncol + col];
+    out[b * out_stride + col] = s;
+  }
+}
+
+// out [B, T, W] = (x[b, t, 0 .. H) | g[b * g_stride + 0 .. gin) | 0 ...) on the rows t < lens[b], zero rows after
+__global__ __launch_bounds__(GL_NT) void gl_bcast_concat_kernel(const float* __restrict__ x, const float* __restrict__ g,
+                                                                long long g_stride, const int* __restrict__ lens,
+                                                                float* __restrict__ out, int B, int T, int H, int gin, int W) {
+  const long long total = (long long)B * T * W;
+  for (long long e = (long long)blockIdx.x * GL_NT + threadIdx.x; e < total; e += (long long)gridDim.x * GL_NT) {
+    const int col = (int)(e % W);
+    const long long row = e / W;
+    const int t = (int)(row % T), b = (int)(row / T);
+    float v = 0.f;
+    if (!lens || t < lens[b]) {
+      if (col < H) v = x[row * H + col];
+      else if (col < H + gin) v = g[b * g_stride + (col - H)];
+    }
+    out[e] = v;
+  }
+}
+
 __global__ __launch_bounds__(GL_NT) void gl_dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long long n, unsigned key,
                                                            const unsigned* __restrict__ key_dev, unsigned thr, float dscale) {
   if (key_dev) key = *key_dev;
@@ -725,6 +827,88 @@ extern "C" int smt_glow_gate_bwd(const float* a, const float* dacts, float* da, 
   SMT_CHECK_ARG(a && dacts && da, "smt_glow_gate_bwd: null pointer");
   gl_gate_bwd_kernel<<<gl_grid(rows * hidden), GL_NT, 0, stream>>>(a, dacts, da, rows, hidden, drop_key, drop_key_dev, drop_thresh16, drop_scale);
   SMT_CHECK_LAUNCH("glow_gate_bwd");
+  return 0;
+}
+
+extern "C" size_t smt_glow_gate_cond_workspace_bytes(int batch, int t, int cols) {
+  if (batch <= 0 || t <= 0 || cols <= 0) return 0;
+  return (size_t)batch * (size_t)((t + GL_ROWS - 1) / GL_ROWS) * (size_t)cols * sizeof(float);
+}
+
+extern "C" int smt_glow_gate_cond_fwd(const float* a, const float* cond, int64_t cond_stride, float* acts, int batch, int t, int hidden,
+                                      uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale,
+                                      smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(batch >= 0 && t >= 0 && hidden >= 1, "smt_glow_gate_cond_fwd: bad sizes");
+  SMT_CHECK_ARG(cond_stride >= 2 * (int64_t)hidden, "smt_glow_gate_cond_fwd: cond_stride %lld < 2 hidden = %d", (long long)cond_stride,
+                2 * hidden);
+  if ((long long)batch * t == 0) return 0;
+  SMT_CHECK_ARG(a && cond && acts, "smt_glow_gate_cond_fwd: null pointer");
+  gl_gate_cond_fwd_kernel<<<gl_grid((long long)batch * t * hidden), GL_NT, 0, stream>>>(a, cond, cond_stride, acts, batch, t, hidden, drop_key,
+                                                                                      drop_key_dev, drop_thresh16, drop_scale);
+  SMT_CHECK_LAUNCH("glow_gate_cond_fwd");
+  return 0;
+}
+
+extern "C" int smt_glow_gate_cond_bwd(const float* a, const float* dacts, const float* cond, int64_t cond_stride, const int* lens, float* da,
+                                      float* dcond, int64_t dcond_stride, int batch, int t, int hidden, uint32_t drop_key,
+                                      const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, void* workspace,
+                                      size_t workspace_bytes, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(batch >= 0 && t >= 0 && hidden >= 1 && (hidden + GL_CT - 1) / GL_CT <= 65535, "smt_glow_gate_cond_bwd: bad sizes");
+  SMT_CHECK_ARG(cond_stride >= 2 * (int64_t)hidden, "smt_glow_gate_cond_bwd: cond_stride %lld < 2 hidden = %d", (long long)cond_stride,
+                2 * hidden);
+  SMT_CHECK_ARG(dcond_stride >= 2 * (int64_t)hidden, "smt_glow_gate_cond_bwd: dcond_stride %lld < 2 hidden = %d", (long long)dcond_stride,
+                2 * hidden);
+  if (batch == 0) return 0;
+  SMT_CHECK_ARG(dcond, "smt_glow_gate_cond_bwd: null pointer");
+  const int chunks = (t + GL_ROWS - 1) / GL_ROWS;
+  if (chunks > 0) {
+    SMT_CHECK_ARG(a && dacts && cond && da && workspace, "smt_glow_gate_cond_bwd: null pointer");
+    SMT_CHECK_ARG((long long)batch * chunks <= 2147483647ll, "smt_glow_gate_cond_bwd: batch * ceil(t / 64) exceeds the grid");
+    SMT_CHECK_ARG(workspace_bytes >= smt_glow_gate_cond_workspace_bytes(batch, t, 2 * hidden), "smt_glow_gate_cond_bwd: workspace too small");
+    gl_gate_cond_bwd_kernel<<<dim3(batch * chunks, (hidden + GL_CT - 1) / GL_CT), GL_NT, 0, stream>>>(
+        a, dacts, cond, cond_stride, lens, da, (float*)workspace, t, hidden, chunks, drop_key, drop_key_dev, drop_thresh16, drop_scale);
+    SMT_CHECK_LAUNCH("glow_gate_cond_bwd");
+  }
+  gl_item_colsum_kernel<<<gl_grid((long long)batch * 2 * hidden), GL_NT, 0, stream>>>((const float*)workspace, batch, chunks, 2 * hidden, dcond,
+                                                                                    dcond_stride);
+  SMT_CHECK_LAUNCH("glow_item_colsum");
+  return 0;
+}
+
+extern "C" int smt_glow_bcast_concat(const float* x, const float* g, int64_t g_stride, const int* lens, float* out, int batch, int t,
+                                     int hidden, int gin, int width, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(batch >= 0 && t >= 0 && hidden >= 1 && gin >= 1, "smt_glow_bcast_concat: bad sizes");
+  SMT_CHECK_ARG(width >= hidden + gin, "smt_glow_bcast_concat: width %d < hidden + gin = %d", width, hidden + gin);
+  SMT_CHECK_ARG(g_stride >= gin, "smt_glow_bcast_concat: g_stride %lld < gin = %d", (long long)g_stride, gin);
+  if ((long long)batch * t == 0) return 0;
+  SMT_CHECK_ARG(x && g && out, "smt_glow_bcast_concat: null pointer");
+  gl_bcast_concat_kernel<<<gl_grid((long long)batch * t * width), GL_NT, 0, stream>>>(x, g, g_stride, lens, out, batch, t, hidden, gin, width);
+  SMT_CHECK_LAUNCH("glow_bcast_concat");
+  return 0;
+}
+
+extern "C" int smt_glow_item_colsum(const float* dout, const int* lens, float* dg, int64_t dg_stride, int batch, int t, int width, int col0,
+                                    int ncol, void* workspace, size_t workspace_bytes, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(batch >= 0 && t >= 0 && col0 >= 0 && ncol >= 1 && (ncol + GL_CT - 1) / GL_CT <= 65535, "smt_glow_item_colsum: bad sizes");
+  SMT_CHECK_ARG(width >= col0 + ncol, "smt_glow_item_colsum: width %d < col0 + ncol = %d", width, col0 + ncol);
+  SMT_CHECK_ARG(dg_stride >= ncol, "smt_glow_item_colsum: dg_stride %lld < ncol = %d", (long long)dg_stride, ncol);
+  if (batch == 0) return 0;
+  SMT_CHECK_ARG(dg, "smt_glow_item_colsum: null pointer");
+  const int chunks = (t + GL_ROWS - 1) / GL_ROWS;
+  if (chunks > 0) {
+    SMT_CHECK_ARG(dout && workspace, "smt_glow_item_colsum: null pointer");
+    SMT_CHECK_ARG((long long)batch * chunks <= 2147483647ll, "smt_glow_item_colsum: batch * ceil(t / 64) exceeds the grid");
+    SMT_CHECK_ARG(workspace_bytes >= smt_glow_gate_cond_workspace_bytes(batch, t, ncol), "smt_glow_item_colsum: workspace too small");
+    gl_item_colsum_part_kernel<<<dim3(batch * chunks, (ncol + GL_CT - 1) / GL_CT), GL_NT, 0, stream>>>(dout, lens, (float*)workspace, t, width, col0,
+                                                                                                     ncol, chunks);
+    SMT_CHECK_LAUNCH("glow_item_colsum_part");
+  }
+  gl_item_colsum_kernel<<<gl_grid((long long)batch * ncol), GL_NT, 0, stream>>>((const float*)workspace, batch, chunks, ncol, dg, dg_stride);
+  SMT_CHECK_LAUNCH("glow_item_colsum");
   return 0;
 }
 

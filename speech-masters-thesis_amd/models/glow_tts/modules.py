@@ -7,6 +7,7 @@ import torch.nn.functional as F
 
 import models.glow_tts.submodules as submodules
 from models.glow_tts.submodules import conv
+from smt_amd import glow
 from smt_amd import lm as K
 
 
@@ -17,9 +18,12 @@ class TextEncoder(nn.Module):
     def __init__(self, n_vocab, out_channels, hidden_channels, filter_channels, filter_channels_dp, n_heads, n_layers, kernel_size,
                  p_dropout, window_size, mean_only=False, prenet=False, gin_channels=0, sites=None):
         super().__init__()
-        assert gin_channels == 0, "speaker conditioning is not built (n_speakers = 1 in configs/models/glow_tts.yaml)"
         sites = sites if sites is not None else submodules._Sites()
         self.n_layers, self.hidden_channels, self.prenet, self.mean_only, self.p_dropout = n_layers, hidden_channels, prenet, mean_only, p_dropout
+        self.gin_channels = gin_channels
+        self.dp_width = hidden_channels + gin_channels        # the width proj_w's first convolution runs at (zero columns past H + gin)
+        while not submodules._cin_ok(self.dp_width):
+            self.dp_width += 8 - self.dp_width % 8
         self.emb = nn.Embedding(n_vocab, hidden_channels)
         nn.init.normal_(self.emb.weight, 0.0, hidden_channels ** -0.5)
         if prenet:
@@ -40,12 +44,15 @@ class TextEncoder(nn.Module):
         self.proj_m = submodules.ConvParams(hidden_channels, out_channels, 1)
         if not mean_only:
             self.proj_s = submodules.ConvParams(hidden_channels, out_channels, 1)
-        self.proj_w = submodules.DurationPredictor(hidden_channels, filter_channels_dp, kernel_size, p_dropout, sites=sites,
+        self.proj_w = submodules.DurationPredictor(hidden_channels + gin_channels, filter_channels_dp, kernel_size, p_dropout, sites=sites,
                                                    prefix="encoder.proj_w")
 
     def forward(self, text, text_lengths, seed=0, speaker_embeddings=None):
-        """text [B, Tx] int64 -> (x_m [B, Tx, D], x_logs [B, Tx, D] or None when mean_only, logw [B, Tx], lens int32)."""
-        assert speaker_embeddings is None
+        """text [B, Tx] int64 -> (x_m [B, Tx, D], x_logs [B, Tx, D] or None when mean_only, logw [B, Tx], lens int32).
+        speaker_embeddings [B, gin]: the duration predictor reads (detach(x) | g over the item's tokens) (modules.py:117-129)."""
+        if (speaker_embeddings is not None) != (self.gin_channels > 0):
+            raise ValueError(f"TextEncoder built with gin_channels = {self.gin_channels} was called "
+                             f"{'with' if speaker_embeddings is not None else 'without'} a speaker embedding")
         lens = text_lengths.to(torch.int32)
         x = F.embedding(text, self.emb.weight) * math.sqrt(self.hidden_channels)          # [B, Tx, H], channels-last as it comes
         if self.prenet:
@@ -58,7 +65,8 @@ class TextEncoder(nn.Module):
             x = self.norm_layers_2[i](x, y, K.Drop(self.p_dropout, self.training, seed, sf))
         x_m = conv(x, self.proj_m.weight, self.proj_m.bias, lens=lens)
         x_logs = None if self.mean_only else conv(x, self.proj_s.weight, self.proj_s.bias, lens=lens)
-        logw = self.proj_w(x.detach(), lens, seed)
+        x_dp = x.detach() if speaker_embeddings is None else glow.bcast_concat(x.detach(), speaker_embeddings, lens, self.dp_width)
+        logw = self.proj_w(x_dp, lens, seed)
         return x_m, x_logs, logw, lens
 
 
@@ -80,11 +88,12 @@ class FlowSpecDecoder(nn.Module):
                                                        prefix=f"decoder.flows.{3 * blk + 2}"))
 
     def forward(self, spect, lens, speaker_embeddings=None, reverse=False, seed=0):
-        """spect [B, T, n_mels] channels-last, lens [B] (a multiple of n_sqz each) -> (z [B, T, n_mels], logdet [B] or None)."""
+        """spect [B, T, n_mels] channels-last, lens [B] (a multiple of n_sqz each) -> (z [B, T, n_mels], logdet [B] or None);
+        speaker_embeddings [B, gin] condition every coupling block's WN, in both directions."""
         x, xl = self.squeeze(spect, lens, self.n_sqz) if self.n_sqz > 1 else (spect, lens)
         logdet_tot = None if reverse else 0
         for f in (reversed(self.flows) if reverse else self.flows):
-            x, logdet = f(x, xl, reverse=reverse, seed=seed)
+            x, logdet = f(x, xl, reverse=reverse, seed=seed, g=speaker_embeddings)
             if not reverse:
                 logdet_tot = logdet_tot + logdet
         if self.n_sqz > 1:

@@ -152,27 +152,40 @@ class ConvReluNorm(nn.Module):
 
 
 class WN(nn.Module):
-    """submodules.py:167-228 without speaker conditioning: n layers of [dilated conv H -> 2H, dropout, tanh * sigmoid gate,
-    1x1 conv to (residual | skip)].  The residual and skip halves of ``res_skip_layers`` run as two convolutions with the
-    running tensors as their residual operands, so `x + res` and `output + skip` cost no extra pass."""
+    """submodules.py:167-228: n layers of [dilated conv H -> 2H, dropout, tanh * sigmoid gate, 1x1 conv to (residual | skip)].
+    The residual and skip halves of ``res_skip_layers`` run as two convolutions with the running tensors as their residual
+    operands, so `x + res` and `output + skip` cost no extra pass.  With ``gin_channels`` > 0 (speaker conditioning) the
+    weight-normed 1x1 ``cond_layer`` maps the item's embedding g [B, gin] to every layer's condition at once, cond
+    [B, 2H n_layers], and layer i's gate adds its slice after the in-layer's dropout (``glow.wn_gate_cond``): no new dropout
+    site.  ``cond_layer`` is a [B, gin] x [gin, 2H n_layers] product of negligible size: one fp32 ``F.linear``."""
 
-    def __init__(self, hidden_channels, kernel_size, dilation_rate, n_layers, p_dropout, sites, prefix):
+    def __init__(self, hidden_channels, kernel_size, dilation_rate, n_layers, p_dropout, sites, prefix, gin_channels=0):
         super().__init__()
         assert kernel_size % 2 == 1 and hidden_channels % 2 == 0
         self.hidden_channels, self.kernel_size, self.dilation_rate, self.n_layers = hidden_channels, kernel_size, dilation_rate, n_layers
-        self.p_dropout = p_dropout
+        self.p_dropout, self.gin_channels = p_dropout, gin_channels
+        if gin_channels > 0:
+            self.cond_layer = WeightNormConvParams(gin_channels, 2 * hidden_channels * n_layers, 1)
         self.in_layers = nn.ModuleList(WeightNormConvParams(hidden_channels, 2 * hidden_channels, kernel_size) for _ in range(n_layers))
         self.res_skip_layers = nn.ModuleList(
             WeightNormConvParams(hidden_channels, 2 * hidden_channels if i < n_layers - 1 else hidden_channels, 1) for i in range(n_layers))
         self.sites = [sites.add(f"{prefix}.drop.{i}") for i in range(n_layers)]
 
-    def forward(self, x, lens, seed):
+    def forward(self, x, lens, seed, g=None):
         h, output = self.hidden_channels, None
+        if (g is not None) != (self.gin_channels > 0):
+            raise ValueError(f"WN built with gin_channels = {self.gin_channels} was called {'with' if g is not None else 'without'} "
+                             "a speaker embedding")
+        cond = None
+        if g is not None:
+            cl = self.cond_layer
+            cond = F.linear(g.float(), cl.weight[:, :, 0], cl.bias)              # [B, 2H n_layers], rows dense
         for i in range(self.n_layers):
             dil = self.dilation_rate ** i
             il, rs = self.in_layers[i], self.res_skip_layers[i]
             a = conv(x, il.weight, il.bias, padding=(self.kernel_size * dil - dil) // 2, dilation=dil, lens=lens)
-            acts = glow.wn_gate(a, K.Drop(self.p_dropout, self.training, seed, self.sites[i]))
+            drop = K.Drop(self.p_dropout, self.training, seed, self.sites[i])
+            acts = glow.wn_gate(a, drop) if cond is None else glow.wn_gate_cond(a, cond[:, 2 * h * i:2 * h * (i + 1)], lens, drop)
             w, b = rs.weight, rs.bias
             if i < self.n_layers - 1:
                 x = conv(acts, w[:h], b[:h], residual=x)                   # rows beyond the length are masked by every reader
@@ -246,16 +259,16 @@ class CouplingBlock(nn.Module):
     def __init__(self, in_channels, hidden_channels, kernel_size, dilation_rate, n_layers, gin_channels=0, p_dropout=0, sigmoid_scale=False,
                  sites=None, prefix=""):
         super().__init__()
-        assert gin_channels == 0, "speaker conditioning is not built (n_speakers = 1 in configs/models/glow_tts.yaml)"
         self.in_channels, self.hidden_channels, self.sigmoid_scale = in_channels, hidden_channels, sigmoid_scale
         self.start = WeightNormConvParams(in_channels // 2, hidden_channels, 1)
         self.end = ConvParams(hidden_channels, in_channels, 1, zero=True)    # zero: the coupling starts as the identity
-        self.wn = WN(hidden_channels, kernel_size, dilation_rate, n_layers, p_dropout, sites if sites is not None else _Sites(), prefix + ".wn")
+        self.wn = WN(hidden_channels, kernel_size, dilation_rate, n_layers, p_dropout, sites if sites is not None else _Sites(), prefix + ".wn",
+                     gin_channels=gin_channels)            # the reference (submodules.py:372) passes neither gin_channels nor p_dropout
 
-    def forward(self, x, lens, reverse=False, seed=0, **kwargs):
+    def forward(self, x, lens, reverse=False, seed=0, g=None, **kwargs):
         half = self.in_channels // 2
         h = conv(x, self.start.weight, self.start.bias, lens=lens, x_channels=half)       # reads x_0 = the first half of the row
-        h = self.wn(h, lens, seed)
+        h = self.wn(h, lens, seed, g)
         out = conv(h, self.end.weight, self.end.bias, lens=lens)
         if reverse:
             return glow.coupling_reverse(out, x, lens, self.sigmoid_scale), None
@@ -313,7 +326,8 @@ class FeedForwardNetwork(nn.Module):
 
 
 class DurationPredictor(nn.Module):
-    """submodules.py:612-637: 2 x [conv k, ReLU, LayerNorm, dropout], 1x1 projection to one channel."""
+    """submodules.py:612-637: 2 x [conv k, ReLU, LayerNorm, dropout], 1x1 projection to one channel.  ``x`` may be wider than
+    ``in_channels`` (the speaker-conditioned input is built at the width the convolution runs at, with zero columns)."""
 
     def __init__(self, in_channels, filter_channels, kernel_size, p_dropout, sites=None, prefix=""):
         super().__init__()
@@ -329,7 +343,7 @@ class DurationPredictor(nn.Module):
     def forward(self, x, lens, seed):
         pad = self.kernel_size // 2
         for i, (c, n) in enumerate(((self.conv_1, self.norm_1), (self.conv_2, self.norm_2))):
-            h = conv(x, c.weight, None, padding=pad, lens=lens)
+            h = conv(x, c.weight, None, padding=pad, lens=lens, x_channels=c.weight.shape[1])
             h = K.bias_relu_dropout_(h, c.bias)                                  # relu(conv + bias)
             x = glow.dropout(n(h), K.Drop(self.p_dropout, self.training, seed, self.sites[i]))
         return conv(x, self.proj.weight, self.proj.bias, lens=lens)[:, :, 0]     # [B, T]; rows beyond the length: masked by the loss

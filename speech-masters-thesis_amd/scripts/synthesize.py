@@ -2,7 +2,7 @@
 batched): mel spectrograms from a GlowTTS, waveforms from a VQTTS.
 
     python -m scripts.synthesize --log_dir ./logs/glow_tts --ckpt_num 5000 --tokens utterances.txt --dump_dir ./outputs \
-        [--batch_size 16] [--noise_scale 0.667] [--length_scale 1.0] [--seed 0] [--temperature 0] [--min_p 0]
+        [--batch_size 16] [--noise_scale 0.667] [--length_scale 1.0] [--seed 0] [--temperature 0] [--min_p 0] [--speaker N]
 
 ``--tokens`` holds one utterance per line as whitespace-separated integer ids (the ids of datasets/synthetic.py, and the ones
 the reference's CMUDict parser would emit; the text front end itself is not built).  Writes
@@ -13,7 +13,8 @@ A token-to-waveform model (VQTTS, `VQTTS.infer`) writes ``wav_<i>.wav`` (16-bit 
 the utterance's length) and the log-mel spectrograms of the waveforms as ``mel_spectrograms.png``; it has no prior noise,
 so ``--noise_scale`` other than 1 is refused for it.  ``--temperature`` > 0 draws its codes instead of taking the argmax
 (``--min_p`` truncates the draw); utterance i of the tokens file draws with seed ``--seed`` + i whatever ``--batch_size``.  GlowTTS
-has no codes and refuses both flags."""
+has no codes and refuses both flags.  ``--speaker N`` is the voice of every utterance: required by a multi-speaker GlowTTS
+checkpoint (``n_speakers`` > 1 in its config), an error for any other model."""
 import argparse
 import logging
 import math
@@ -42,6 +43,7 @@ def parse_args(argv=None):
     p.add_argument("--seed", type=int, default=0, help="Seed of the prior noise (GlowTTS) or of the code draws (VQTTS, --temperature > 0)")
     p.add_argument("--temperature", type=float, default=0.0, help="VQTTS: temperature of the code draw (0 = argmax)")
     p.add_argument("--min_p", type=float, default=0.0, help="VQTTS: draw among the codes with p >= min_p * p_max (0 = all)")
+    p.add_argument("--speaker", type=int, default=None, help="Multi-speaker GlowTTS: the speaker id of every utterance")
     return p.parse_args(argv)
 
 
@@ -120,6 +122,13 @@ def main(argv=None):
     os.makedirs(dump_dir, exist_ok=True)
 
     from models.base import TokenToWaveformModel
+    n_speakers = int(getattr(model, "n_speakers", 1))
+    if n_speakers > 1 and args.speaker is None:
+        raise ValueError(f"this checkpoint has {n_speakers} speakers: --speaker N (0 <= N < {n_speakers}) is required")
+    if n_speakers <= 1 and args.speaker is not None:
+        raise ValueError(f"--speaker applies to a multi-speaker GlowTTS checkpoint; this {type(model).__name__} is single-speaker")
+    if n_speakers > 1 and not 0 <= args.speaker < n_speakers:
+        raise ValueError(f"--speaker must lie in [0, {n_speakers}), got {args.speaker}")
     if isinstance(model, TokenToWaveformModel):
         return synthesize_waveforms(model, config, utterances, args, dump_dir, device)
     if args.temperature != 0.0 or args.min_p != 0.0:
@@ -127,7 +136,8 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     mels = []
     for x, x_lengths in batches(utterances, args.batch_size):
-        yh, y_lengths = model.infer(x, x_lengths, noise_scale=args.noise_scale, length_scale=args.length_scale)
+        voice = {} if args.speaker is None else {"speaker": args.speaker}
+        yh, y_lengths = model.infer(x, x_lengths, noise_scale=args.noise_scale, length_scale=args.length_scale, **voice)
         yh = yh.cpu().numpy()
         mels += [np.ascontiguousarray(yh[i, :, :n], dtype=np.float32) for i, n in enumerate(y_lengths.tolist())]
     for i, m in enumerate(mels):

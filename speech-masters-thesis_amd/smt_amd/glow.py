@@ -1,6 +1,7 @@
 """GlowTTS ops on the HIP library (include/smt_hip.h, "GlowTTS"): every function is a torch.autograd.Function whose forward
 and backward are libsmt_hip.so launches on torch's current stream.  fp32, channels-last rows [B, T, C], prefix row masks as
 int32 lengths.  Reference: models/glow_tts/{glow_tts,modules,submodules}.py (cited per function)."""
+import ctypes
 import math
 
 import torch
@@ -155,6 +156,125 @@ class _Gate(torch.autograd.Function):
 def wn_gate(a, drop=NO_DROP):
     """tanh(d(a)[..., :H]) * sigmoid(d(a)[..., H:]) with d = the in_layer's dropout (WN.forward, submodules.py:213-220)."""
     return _Gate.apply(a, drop)
+
+
+def check_extent(t, items, stride, width, what="tensor"):
+    """``items`` vectors of ``width`` elements, ``stride`` elements apart, starting at ``t``'s first element, must end inside
+    ``t``'s storage: (items - 1) stride + width <= the elements from there to the storage's end, and stride >= width when
+    there is more than one item.  ValueError otherwise.  Pure bookkeeping (CPU tensors too): the kernels that take a pointer and
+    an item stride (smt_glow_gate_cond_*, smt_glow_bcast_concat, smt_glow_item_colsum) are launched only after it."""
+    items, stride, width = int(items), int(stride), int(width)
+    if items <= 0:
+        return
+    avail = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+    if items > 1 and stride < width:
+        raise ValueError(f"{what}: item stride {stride} < width {width}: the items overlap")
+    need = (items - 1) * stride + width
+    if need > avail:
+        raise ValueError(f"{what}: {items} items of {width} elements at stride {stride} end at element {need}, "
+                         f"the storage holds {avail} from the tensor's first element")
+
+
+def _item_rows(t, width, what):
+    """(pointer, item stride) of a [B, width] fp32 device tensor whose rows are dense but may lie apart (a column slice of a
+    wider tensor).  The stride is THIS tensor's ``stride(0)`` -- never one computed from shapes, and never another tensor's:
+    the kernel writes or reads b * stride + j from this pointer.  (torch reports any stride for a dimension of size 1, where
+    the kernel never uses it; the library still wants it >= width.)"""
+    assert t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and t.shape[1] == width, f"{what}: fp32 device [B, {width}]"
+    assert t.stride(1) == 1 or width == 1, f"{what}: the rows must be dense (stride(1) == 1), got strides {t.stride()}"
+    stride = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), width)
+    check_extent(t, t.shape[0], stride, width, what)
+    return ctypes.c_void_p(t.data_ptr()), stride
+
+
+def gate_cond_backward(a, dacts, cond_i, lens, drop=NO_DROP, dcond=None):
+    """(da [B, T, 2H], d cond_i [B, 2H]) of ``wn_gate_cond``.  ``dcond``: the destination (rows dense, any item stride -- it is
+    passed with its OWN stride, whatever cond_i's is); default a new dense [B, 2H]."""
+    a, dacts = _f(a), _f(dacts)
+    b, t, h2 = a.shape
+    h = h2 // 2
+    if dcond is None:
+        dcond = torch.empty(b, h2, device=a.device)
+    cp, cs = _item_rows(cond_i, h2, "cond")
+    dp, ds = _item_rows(dcond, h2, "d cond")
+    da = torch.empty_like(a)
+    lib = N.lib()
+    ws = _ws(lib.smt_glow_gate_cond_workspace_bytes(b, t, h2), a.device)
+    with profiler.region("glow_gate_cond:bwd", nbytes=5 * b * t * h * 4, bound="hbm"):
+        N.check(lib.smt_glow_gate_cond_bwd(N.ptr(a), N.ptr(dacts), cp, cs, N.ptr(lens), N.ptr(da), dp, ds, b, t, h, drop.key,
+                                           N.ptr(drop.key_dev), drop.thresh, drop.scale, N.ptr(ws), ws.numel(), N.stream_ptr()),
+                "smt_glow_gate_cond_bwd")
+    return da, dcond
+
+
+class _GateCond(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, cond_i, lens, drop):
+        a = _f(a)
+        b, t, h2 = a.shape
+        h = h2 // 2
+        cp, cs = _item_rows(cond_i, h2, "cond")
+        acts = torch.empty(b, t, h, device=a.device)
+        with profiler.region("glow_gate_cond:fwd", nbytes=3 * b * t * h * 4, bound="hbm"):
+            N.check(N.lib().smt_glow_gate_cond_fwd(N.ptr(a), cp, cs, N.ptr(acts), b, t, h, drop.key, N.ptr(drop.key_dev), drop.thresh,
+                                                   drop.scale, N.stream_ptr()), "smt_glow_gate_cond_fwd")
+        ctx.save_for_backward(a, cond_i, lens if lens is not None else torch.empty(0))
+        ctx.meta = (drop, lens is not None)
+        return acts
+
+    @staticmethod
+    def backward(ctx, dacts):
+        a, cond_i, lens = ctx.saved_tensors
+        drop, has_lens = ctx.meta
+        da, dcond = gate_cond_backward(a, dacts, cond_i, lens if has_lens else None, drop)
+        return da, dcond, None, None         # d cond is dense [B, 2H]; autograd's slice backward places it in the wider tensor
+
+
+def wn_gate_cond(a, cond_i, lens, drop=NO_DROP):
+    """tanh(d(a)[..., :H] + cond_i[b, :H]) * sigmoid(d(a)[..., H:] + cond_i[b, H:]) for a [B, T, 2H] and one vector per item
+    cond_i [B, 2H] (WN.forward with g, submodules.py:212-224; the condition enters after the in_layer's dropout).  cond_i may
+    be the view ``cond[:, 2H i : 2H (i + 1)]`` of all layers' conditions.  ``lens``: d cond sums the rows t < lens[b] only."""
+    assert a.dim() == 3 and a.shape[-1] % 2 == 0 and cond_i.shape == (a.shape[0], a.shape[-1])
+    return _GateCond.apply(a, cond_i, _lens(lens), drop)
+
+
+class _BcastConcat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, g, lens, width):
+        x = _f(x)
+        b, t, h = x.shape
+        gin = g.shape[1]
+        gp, gs = _item_rows(g, gin, "g")
+        out = torch.empty(b, t, width, device=x.device)
+        with profiler.region("glow_bcast_concat", nbytes=b * t * (h + width) * 4, bound="hbm"):
+            N.check(N.lib().smt_glow_bcast_concat(N.ptr(x), gp, gs, N.ptr(lens), N.ptr(out), b, t, h, gin, width, N.stream_ptr()),
+                    "smt_glow_bcast_concat")
+        ctx.save_for_backward(lens if lens is not None else torch.empty(0))
+        ctx.meta = (h, gin, lens is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (lens,) = ctx.saved_tensors
+        h, gin, has_lens = ctx.meta
+        dout = _f(dout)
+        b, t, width = dout.shape
+        dg = torch.empty(b, gin, device=dout.device)
+        dp, ds = _item_rows(dg, gin, "d g")
+        lib = N.lib()
+        ws = _ws(lib.smt_glow_gate_cond_workspace_bytes(b, t, gin), dout.device)
+        with profiler.region("glow_item_colsum", nbytes=b * t * gin * 4, bound="hbm"):
+            N.check(lib.smt_glow_item_colsum(N.ptr(dout), N.ptr(lens if has_lens else None), dp, ds, b, t, width, h, gin, N.ptr(ws),
+                                             ws.numel(), N.stream_ptr()), "smt_glow_item_colsum")
+        return None, dg, None, None
+
+
+def bcast_concat(x, g, lens, width):
+    """out [B, T, width] = (x[b, t] | g[b] | zeros) on the rows t < lens[b], zero rows after: the duration predictor's input
+    ``cat[detach(x), g over T]`` (TextEncoder.forward, modules.py:117-129), ``width`` >= H + gin = the channel count the
+    convolution runs at.  x enters detached (no gradient); d g[b] = the column sums of d out over the item's valid rows."""
+    assert x.dim() == 3 and g.dim() == 2 and g.shape[0] == x.shape[0] and not x.requires_grad
+    return _BcastConcat.apply(x, g, _lens(lens), int(width))
 
 
 class _Coupling(torch.autograd.Function):

@@ -140,7 +140,13 @@ _SIGNATURES = {
     "smt_glow_invconv_wgrad": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_size, c_ptr]),
     "smt_glow_gate_fwd": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_u32, c_ptr, c_u32, c_f32, c_ptr]),
     "smt_glow_gate_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_u32, c_ptr, c_u32, c_f32, c_ptr]),
-    "smt_glow_dropout": (c_int, [c_ptr, c_ptr, c_i64, c_u32, c_ptr, c_u32, c_f32, c_ptr]),
+    "smt_glow_gate_cond_workspace_bytes": (c_size, [c_int, c_int, c_int]),
+    "smt_glow_gate_cond_fwd": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_int, c_int, c_int, c_u32, c_ptr, c_u32, c_f32, c_ptr]),
+    "smt_glow_gate_cond_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_u32, c_ptr, c_u32,
+                                       c_f32, c_ptr, c_size, c_ptr]),
+    "smt_glow_bcast_concat": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr]),
+    "smt_glow_item_colsum": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr, c_size, c_ptr]),
+    "smt_glow_dropout": (c_int,[c_ptr, c_ptr, c_i64, c_u32, c_ptr, c_u32, c_f32, c_ptr]),
     "smt_glow_coupling_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_size, c_ptr]),
     "smt_glow_coupling_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "smt_glow_attention_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int,

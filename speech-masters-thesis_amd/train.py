@@ -68,6 +68,8 @@ def train_step(*, global_step, batch, config, model, ema, optimizer, scheduler, 
     # NaN guard: the reference tests the loss before backward (train.py:124); testing after the
     # collectives are queued keeps the device->host sync off the critical path, same abort semantics.
     if torch.isnan(loss):
+        if callable(getattr(model, "check_speaker_ids", None)):
+            model.check_speaker_ids()          # a speaker id out of range poisons its item with NaN: name that cause
         print(dict(**{k: v for k, v in loss_dict.items() if k.startswith("loss")}, **metrics_dict,
                    STEP=global_step, RANK=rank))
         raise RuntimeError(f"Nan detected in loss at step {global_step}")
