@@ -472,6 +472,16 @@ int smt_stft_magnitude(const float* x, const float* window, const float* twiddle
  * log(max(mel_basis @ |STFT|, 1e-5)); band[2m], band[2m+1] = first / one-past-last non-zero bin of row m. */
 int smt_melspec(const float* x, const float* window, const float* twiddle, const float* mel_basis, const int* band,
                 float* mel, int batch, int t, int n_fft, int hop, int n_mels, smt_stream_t stream);
+/* Log-mel of a ragged batch in one launch.  Item b is the clip x[b, :L_b], L_b = clamp(lens[b], 0, t) (lens int32 [batch] on
+ * the device), transformed as smt_melspec transforms that clip alone: reflected about its own two ends, F_b =
+ * smt_stft_num_frames(L_b) frames, or none if L_b <= pad or L_b + 2 pad < n_fft (pad = (n_fft - hop) / 2).  mel [batch,
+ * n_mels, frames_out]: columns f < min(F_b, frames_out) hold the frames -- bit for bit what smt_melspec gives on the clip --
+ * and every other column holds `fill`; each element is written exactly once and no x[b, i >= L_b] is read.  Errors: null
+ * pointer, n_fft outside {256, 512, 1024, 2048}, hop outside [1, n_fft], n_mels < 1, t outside [1, 2^30], frames_out < 0,
+ * batch outside [0, 65535].  batch == 0 or frames_out == 0 launches nothing.  No workspace, no atomics. */
+int smt_melspec_ragged(const float* x, const int* lens, const float* window, const float* twiddle, const float* mel_basis,
+                       const int* band, float* mel, int batch, int t, int n_fft, int hop, int n_mels, int frames_out, float fill,
+                       smt_stream_t stream);
 /* One resolution of MultiResolutionSpectralLoss (models/vqvae/losses.py:39-55) without materialising
  * the spectra.  fwd: partial [batch, frames, 2] = per-frame sums of ((|Y|-|Yh|) m)^2 and
  * ((log|Y| - log|Yh|) m)^2 (clamp 1e-5), m = frame mask from lens (losses.py:33-37).

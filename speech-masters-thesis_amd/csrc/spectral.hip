@@ -730,6 +730,67 @@ __global__ __launch_bounds__(256, WAVE_LB) void melspec_wave_kernel(const float*
   }
 }
 
+// Ragged log-mel: item b is the clip x[b, :L], L = clamp(lens[b], 0, T), transformed as if it stood alone -- reflected about
+// ITS OWN two ends -- and its frames are followed by `fill` up to frames_out (what LJSpeech.collate does to per-clip mels with
+// log(1e-7)).  The frame body is melspec_wave_kernel's with L in the place of T: wave_load_frame judges "interior" against L, so
+// a frame that lies inside the buffer but crosses L takes the reflecting path and no sample at or past L is read (the padding
+// may hold anything).  One wave owns column f of item b and writes all n_mels elements of it, a frame or the fill: every
+// element of mel is written exactly once.  The choice between the two is wave-uniform and the kernel has no workgroup
+// barrier, so the four waves of a workgroup may take different sides.
+template <int N>
+__global__ __launch_bounds__(256, WAVE_LB) void melspec_ragged_wave_kernel(const float* __restrict__ x, const int* __restrict__ lens,
+                                                                  const float* __restrict__ window, const cplx* __restrict__ tw,
+                                                                  const float* __restrict__ basis, const int* __restrict__ band,
+                                                                  float* __restrict__ mel, int T, int hop, int pad,
+                                                                  int frames_out, int n_mels, float fill) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int wave = threadIdx.x >> 6, b = blockIdx.y;
+  int lane = threadIdx.x & 63;
+  constexpr int SLOTS = frame_padded<N>() + N / 2;    // N floats behind the frame for the magnitudes
+  cplx* Z = reinterpret_cast<cplx*>(smem_raw) + (size_t)wave * SLOTS;
+  float* magn = reinterpret_cast<float*>(Z + frame_padded<N>());
+  const int f = blockIdx.x * 4 + wave;
+  if (f >= frames_out) return;
+  const int L = min(max(lens[b], 0), T);
+  // frames of the clip alone (stft_frames; the numerator is >= 0 under the second condition); none for a clip the stand-alone
+  // entry refuses (SMT_CHECK_STFT_LENGTH)
+  const int item_frames = (L > pad && L + 2 * pad >= N) ? (L + 2 * pad - N) / hop + 1 : 0;
+  if (f >= item_frames) {
+    for (int m = lane; m < n_mels; m += 64) mel[((long long)b * n_mels + m) * frames_out + f] = fill;
+    return;
+  }
+  WaveFft<N> wc;
+  wc.load(tw, lane);
+  const float* xb = x + (long long)b * T;
+  wave_load_frame<N, false>(Z, wc, xb, xb, window, f * hop - pad, L, lane);
+  wave_fft<N, false>(Z, wc, lane);
+#pragma unroll 4
+  for (int i = 0; i < N / 128; ++i) {
+    const cplx z = Z[fidx<N, 64>(lane + 64 * i)];
+    magn[lane + 64 * i] = sqrtf(z.x * z.x + z.y * z.y);
+  }
+  if (lane == 0) { const cplx z = Z[fidx<N, 64>(N / 2)]; magn[N / 2] = sqrtf(z.x * z.x + z.y * z.y); }
+  __builtin_amdgcn_wave_barrier();
+  asm volatile("" ::: "memory");
+  for (int m = lane; m < n_mels; m += 64) {
+    float s = 0.f;
+    const float* row = basis + (long long)m * (N / 2 + 1);
+    const int lo = band[2 * m], hi = band[2 * m + 1];
+    for (int k = lo; k < hi; k += 8) {
+      float w[8], v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int kk = min(k + u, hi - 1);
+        w[u] = row[kk];
+        v[u] = magn[kk];
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s = fmaf(k + u < hi ? w[u] : 0.f, v[u], s);
+    }
+    mel[((long long)b * n_mels + m) * frames_out + f] = logf(fmaxf(s, 1e-5f));
+  }
+}
+
 // test hook: the one-wave transform alone on one complex frame (tests/test_spectral_gpu.py)
 template <int N>
 __global__ __launch_bounds__(64) void fft_selftest_kernel(const cplx* __restrict__ in, const cplx* __restrict__ tw,
@@ -960,6 +1021,28 @@ extern "C" int smt_melspec(const float* x, const float* window, const float* twi
                                           mel, t, hop, pad, frames, n_mels)));
   }
   SMT_CHECK_LAUNCH("melspec");
+  return 0;
+}
+
+// Always the one-wave form (there is no whole-workgroup ragged kernel; SMT_FFT_NT does not apply).  The device makes every
+// lens value safe (clamp to [0, t]; an item too short for a frame is all fill), so nothing about lens is checked here.
+extern "C" int smt_melspec_ragged(const float* x, const int* lens, const float* window, const float* twiddle,
+                                  const float* mel_basis, const int* band, float* mel, int batch, int t, int n_fft, int hop,
+                                  int n_mels, int frames_out, float fill, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(x && lens && window && twiddle && mel_basis && band && mel, "smt_melspec_ragged: null pointer");
+  SMT_CHECK_ARG(n_fft == 256 || n_fft == 512 || n_fft == 1024 || n_fft == 2048,
+                "smt_melspec_ragged: n_fft=%d unsupported (256, 512, 1024, 2048)", n_fft);
+  SMT_CHECK_ARG(hop >= 1 && hop <= n_fft, "smt_melspec_ragged: hop=%d outside [1, n_fft=%d]", hop, n_fft);
+  SMT_CHECK_ARG(n_mels >= 1, "smt_melspec_ragged: n_mels=%d, need >= 1", n_mels);
+  SMT_CHECK_ARG(t >= 1 && t <= (1 << 30), "smt_melspec_ragged: t=%d outside [1, 2^30]", t);
+  SMT_CHECK_ARG(frames_out >= 0, "smt_melspec_ragged: frames_out=%d, need >= 0", frames_out);
+  SMT_CHECK_ARG(batch >= 0 && batch <= 65535, "smt_melspec_ragged: batch=%d outside [0, 65535] (one grid row per item)", batch);
+  if (batch == 0 || frames_out == 0) return 0;
+  const int pad = (n_fft - hop) / 2;
+  SMT_WAVE_DISPATCH(n_fft, (wave_launch(melspec_ragged_wave_kernel<N>, frame_padded<N>() + N / 2, frames_out, batch, stream, x, lens,
+                                        window, (const cplx*)twiddle, mel_basis, band, mel, t, hop, pad, frames_out, n_mels, fill)));
+  SMT_CHECK_LAUNCH("melspec_ragged");
   return 0;
 }
 

@@ -85,3 +85,26 @@ class MelSpectrogram(nn.Module):
 
     def mel_len(self, audio_len):
         return audio_len // self.hop_length
+
+
+class BatchLogMel(MelSpectrogram):
+    """The log-mels of a collated, zero-padded audio batch as the reference's DataLoader workers make them (ljspeech.py:86-88,
+    :128-132): every clip transformed ALONE -- reflected about its own end -- and the shorter ones padded with log(1e-7).  One
+    launch for the batch (smt_melspec_ragged); the lengths are read from the collate's CPU tensor, so nothing here waits for
+    the device -- which is why the [-1, 1] assert of MelSpectrogram.forward is not repeated."""
+    FILL = float(np.float32(math.log(1e-7)))
+
+    def __init__(self, config=None, **kwargs):
+        if config is not None:
+            ds = config.dataset
+            kwargs = dict(sample_rate=ds.sample_rate, n_fft=ds.n_fft, win_length=ds.win_length, hop_length=ds.hop_length,
+                          n_mels=ds.n_mels, f_min=0.0, f_max=8000.0, **kwargs)
+        super().__init__(**kwargs)
+
+    def forward(self, audio, audio_len):
+        """audio [B, 1, T] or [B, T] on the device, audio_len int64 [B] on the CPU -> (spect [B, n_mels, F], spect_len int64 [B]
+        on the CPU), F = max spect_len; spect[b, :, spect_len[b]:] = log(1e-7)."""
+        b, t = audio.shape[0], audio.shape[-1]
+        stft = self.stft
+        return spectral.log_mel_ragged(audio.reshape(b, t), audio_len, self.mel_basis, self.band, stft.n_fft, stft.hop_length,
+                                       stft.win_length, self.FILL)

@@ -44,6 +44,28 @@ class SpectrogramReconstructionModel(_SlotModel):
     inputs, target = ("spect", "spect_len"), "spect"
 
 
+def text_frontend(config, n_vocab):
+    """(parser, intersperse_blanks) of a token model: the text front end ``dataset.text_frontend`` names (models/parser.py),
+    or None when the key is unset -- the model then takes token ids only.  ValueError when the parser's table is larger than
+    the model's embedding (``encoder.n_vocab``; the blank id sits right behind the table)."""
+    from models.parser import parser_from_config
+    ds = config.dataset
+    parser = parser_from_config(ds)
+    if parser is not None and len(parser.symbols) > n_vocab:
+        raise ValueError(f"dataset.text_frontend = {ds.text_frontend} has {len(parser.symbols)} symbols, more than "
+                         f"encoder.n_vocab = {n_vocab}")
+    return parser, bool(ds.get("intersperse_blanks", False))
+
+
+def sentence_to_ids(model, text):
+    """The token ids of one sentence for ``model.infer_step``, as the dataset makes them for training."""
+    if getattr(model, "text_parser", None) is None:
+        raise NotImplementedError("infer_step takes token ids: this model was configured without a text front end "
+                                  "(dataset.text_frontend: chars, or cmudict with the CMUDict file at dataset.cmudict_path)")
+    from models.parser import sentence_ids
+    return sentence_ids(model.text_parser, text, model.intersperse_blanks)
+
+
 def token_batch(x, x_lengths, n_vocab):
     """The checks of a synthesis call's token ids, shared by ``GlowTTS.infer`` and ``VQTTS.infer``: x [B, Tx] integer ids with
     B >= 1, x_lengths [B] integers in [1, Tx] (None = full width), every id inside its length in [0, n_vocab) -- ValueError

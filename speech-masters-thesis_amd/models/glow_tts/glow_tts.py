@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 import models.glow_tts.submodules as submodules
-from models.base import TokenToSpectrogramModel, token_batch
+from models.base import TokenToSpectrogramModel, sentence_to_ids, text_frontend, token_batch
 from models.glow_tts.modules import FlowSpecDecoder, TextEncoder
 from smt_amd import glow
 
@@ -42,6 +42,7 @@ class GlowTTS(TokenToSpectrogramModel):
                                        n_split=d.n_split, n_sqz=d.n_sqz, sigmoid_scale=d.sigmoid_scale, gin_channels=gin,
                                        sites=self.sites)
         self._drop_seed = 0
+        self.text_parser, self.intersperse_blanks = text_frontend(config, e.n_vocab)
 
     def dropout_sites(self):
         """Site name -> id of every dropout in forward order (the oracle replays the masks by name)."""
@@ -199,11 +200,12 @@ class GlowTTS(TokenToSpectrogramModel):
 
     @torch.no_grad()
     def infer_step(self, t, speaker=None):
-        """One utterance's token ids (a list or a 1-D tensor) -> yh [1, n_mels, T] (glow_tts.py:133-168).  The reference takes a
-        string and phonemizes it with CMUDictParser, which is not built here."""
+        """One utterance -> yh [1, n_mels, T] (glow_tts.py:133-168): its token ids (a list or a 1-D tensor), or, on a model
+        configured with ``dataset.text_frontend``, the sentence itself -- stripped, closed with a period, parsed and
+        interspersed with blanks as the dataset does for training (the reference's infer_step omits the blanks although it
+        trains with them: repaired).  ValueError for a text that leaves no symbol."""
         if isinstance(t, str):
-            raise NotImplementedError("infer_step takes token ids: the CMUDict text front end (models/parser.py) is not built "
-                                      "(DESIGN.md section 7)")
+            t = sentence_to_ids(self, t)
         x = torch.as_tensor(t)
         if x.dim() != 1:
             raise ValueError(f"infer_step takes one utterance's token ids (1-D), got shape {tuple(x.shape)}")

@@ -16,7 +16,7 @@ import math
 
 import torch
 
-from models.base import TokenToWaveformModel, token_batch
+from models.base import TokenToWaveformModel, sentence_to_ids, text_frontend, token_batch
 from models.glow_tts import submodules
 from models.glow_tts.modules import TextEncoder
 from models.vqtts.align import TextAudioAlignment
@@ -85,6 +85,7 @@ class VQTTS(TokenToWaveformModel):
         for stage in self.audio_encoder.level_blocks:
             stage.act_dtype = self.compute_dtype
         self._drop_seed = 0
+        self.text_parser, self.intersperse_blanks = text_frontend(config, e.n_vocab)
 
     def train(self, mode=True):
         self.predictor.train(mode)
@@ -213,11 +214,11 @@ class VQTTS(TokenToWaveformModel):
 
     @torch.no_grad()
     def infer_step(self, t, speaker=None):
-        """One utterance's token ids (a list or a 1-D tensor) -> wave [1, T].  The reference's text front end (CMUDictParser)
-        is not built, so a string is refused."""
+        """One utterance -> wave [1, T]: its token ids (a list or a 1-D tensor), or, on a model configured with
+        ``dataset.text_frontend``, the sentence itself, turned into ids as the dataset does for training (blanks included;
+        DESIGN.md section 18).  ValueError for a text that leaves no symbol."""
         if isinstance(t, str):
-            raise NotImplementedError("infer_step takes token ids: the CMUDict text front end (models/parser.py) is not built "
-                                      "(DESIGN.md section 7)")
+            t = sentence_to_ids(self, t)
         if speaker is not None:
             raise ValueError("speaker embeddings (n_speakers > 1) have no native path; configs/models/vqtts.yaml is single-speaker")
         x = torch.as_tensor(t)

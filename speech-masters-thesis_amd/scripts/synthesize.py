@@ -1,11 +1,13 @@
-"""Synthesis from token ids with a trained token-to-spectrogram or token-to-waveform model (the reference's `infer_step`,
+"""Synthesis from token ids or text with a trained token-to-spectrogram or token-to-waveform model (the reference's `infer_step`,
 batched): mel spectrograms from a GlowTTS, waveforms from a VQTTS.
 
-    python -m scripts.synthesize --log_dir ./logs/glow_tts --ckpt_num 5000 --tokens utterances.txt --dump_dir ./outputs \
+    python -m scripts.synthesize --log_dir ./logs/glow_tts --ckpt_num 5000 (--tokens utterances.txt | --text sentences.txt) --dump_dir ./outputs \
         [--batch_size 16] [--noise_scale 0.667] [--length_scale 1.0] [--seed 0] [--temperature 0] [--min_p 0] [--speaker N]
 
-``--tokens`` holds one utterance per line as whitespace-separated integer ids (the ids of datasets/synthetic.py, and the ones
-the reference's CMUDict parser would emit; the text front end itself is not built).  Writes
+``--tokens`` holds one utterance per line as whitespace-separated integer ids (the ids of datasets/synthetic.py, or the ones
+models/parser.py emits).  ``--text`` holds one sentence per line instead, for a checkpoint trained with
+``dataset.text_frontend``: the sentences go through that front end as the dataset's transcripts did.
+Exactly one of the two is given.  Writes
 ``<dump_dir>/<ModelClass>@<ckpt>/mel_<i>.npy`` (float32 [n_mels, frames], trimmed to the utterance's length) and one
 ``mel_spectrograms.png``.  Synthesis runs on MI355X through libsmt_hip.so (`GlowTTS.infer`); there is no vocoder.
 
@@ -35,7 +37,9 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--log_dir", type=str, required=True, help="Log directory of training")
     p.add_argument("--ckpt_num", type=int, required=True, help="Checkpoint number to load")
-    p.add_argument("--tokens", type=str, required=True, help="One utterance per line: whitespace-separated token ids")
+    p.add_argument("--tokens", type=str, default=None, help="One utterance per line: whitespace-separated token ids")
+    p.add_argument("--text", type=str, default=None,
+                   help="One sentence per line, for a checkpoint trained with dataset.text_frontend (instead of --tokens)")
     p.add_argument("--dump_dir", type=str, default="./outputs", help="Directory to dump the spectrograms")
     p.add_argument("--batch_size", type=int, default=16, help="Utterances per inference call")
     p.add_argument("--noise_scale", type=float, default=1.0, help="Scale of the prior noise (1 = the reference)")
@@ -55,6 +59,27 @@ def read_tokens(path):
         return [[int(v) for v in r] for r in rows if r]
     except ValueError as e:
         raise ValueError(f"{path}: every line must hold whitespace-separated integer token ids ({e})") from None
+
+
+def read_sentences(path):
+    """Non-empty lines, stripped."""
+    with open(path, encoding="utf-8") as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+def sentences_to_tokens(model, sentences, path):
+    """The ids the checkpoint's own text front end gives (as its dataset made them for training, blanks included)."""
+    from models.parser import sentence_ids
+    if getattr(model, "text_parser", None) is None:
+        raise ValueError("--text needs a checkpoint whose config sets dataset.text_frontend (chars or cmudict); this one was "
+                         "trained on token ids: use --tokens")
+    out = []
+    for i, sentence in enumerate(sentences):
+        try:
+            out.append(sentence_ids(model.text_parser, sentence, model.intersperse_blanks))
+        except ValueError as e:
+            raise ValueError(f"{path}, sentence {i}: {e}") from None
+    return out
 
 
 def batches(utterances, batch_size):
@@ -100,6 +125,9 @@ def synthesize_waveforms(model, config, utterances, args, dump_dir, device):
 
 def main(argv=None):
     args = parse_args(argv)
+    if (args.tokens is None) == (args.text is None):
+        raise ValueError("exactly one of --tokens (integer ids) and --text (sentences) must be given, got "
+                         + ("both" if args.tokens is not None else "neither"))
     if args.batch_size < 1:
         raise ValueError("--batch_size must be >= 1")
     if not (math.isfinite(args.temperature) and args.temperature >= 0):
@@ -108,9 +136,10 @@ def main(argv=None):
         raise ValueError(f"--min_p must lie in [0, 1] and applies to --temperature > 0 only, got {args.min_p}")
     if not torch.cuda.is_available():
         raise RuntimeError("synthesize runs the model on MI355X (libsmt_hip.so); no GPU is visible")
-    utterances = read_tokens(args.tokens)
+    source = args.tokens if args.tokens is not None else args.text
+    utterances = read_tokens(source) if args.tokens is not None else read_sentences(source)
     if not utterances:
-        raise ValueError(f"{args.tokens} holds no utterance")
+        raise ValueError(f"{source} holds no utterance")
     device = torch.device("cuda")
     config = cfglib.load(os.path.join(args.log_dir, "config.yaml"))
     config.train.n_gpus = 1
@@ -118,6 +147,8 @@ def main(argv=None):
     model, _ = get_model(config, device=device)
     model.load_state_dict(ckpt["model"])
     model.eval()
+    if args.text is not None:
+        utterances = sentences_to_tokens(model, utterances, source)
     dump_dir = os.path.join(args.dump_dir, f"{type(model).__name__}@{args.ckpt_num}")
     os.makedirs(dump_dir, exist_ok=True)
 

@@ -102,6 +102,51 @@ def log_mel(x, mel_basis, band, n_fft, hop, win_length):
     return mel
 
 
+def clip_frames(length, n_fft, hop):
+    """Frames of a clip of `length` samples transformed alone: num_frames(), or 0 for a clip `log_mel` refuses (not longer than
+    the reflect padding, or shorter than one frame after it).  The device computes the same in smt_melspec_ragged."""
+    pad = (n_fft - hop) // 2
+    return num_frames(length, n_fft, hop) if length > pad and length + 2 * pad >= n_fft else 0
+
+
+@torch.no_grad()
+def log_mel_ragged(x, lens, mel_basis, band, n_fft, hop, win_length, fill):
+    """x [B, T] on the device, lens int64 [B] ON THE CPU (what collate produced) -> (mel [B, n_mels, F], frames int64 [B] on the
+    CPU), F = max_b frames[b], in ONE launch.  Item b's first frames[b] = clip_frames(lens[b]) columns are log_mel(x[b:b+1,
+    :lens[b]]) bit for bit -- the clip is reflected about its own end, not the batch's -- and the rest hold `fill`; x at or
+    past lens[b] is never read.  Every check is made on the host copy of lens (ValueError), so the call does not wait for the
+    device; an item too short for one frame is not an error here: it is all `fill` and has frames[b] = 0."""
+    if not isinstance(lens, torch.Tensor) or lens.is_cuda or lens.is_floating_point() or lens.is_complex() \
+            or lens.dtype == torch.bool:
+        raise ValueError("log_mel_ragged: lens must be an integer tensor on the CPU (the lengths the collate produced)")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"log_mel_ragged: x must be [B, T] with B, T >= 1, got shape {tuple(x.shape)}")
+    b, t = x.shape
+    if lens.shape != (b,):
+        raise ValueError(f"log_mel_ragged: lens must hold {b} lengths, got shape {tuple(lens.shape)}")
+    host = [int(v) for v in lens.tolist()]
+    for i, n in enumerate(host):
+        if not 0 <= n <= t:
+            raise ValueError(f"log_mel_ragged: item {i} has length {n}, outside [0, T={t}]")
+    if n_fft not in (256, 512, 1024, 2048):
+        raise ValueError(f"log_mel_ragged: n_fft={n_fft} unsupported (256, 512, 1024, 2048)")
+    if not 1 <= hop <= n_fft:
+        raise ValueError(f"log_mel_ragged: hop={hop} outside [1, n_fft={n_fft}]")
+    x = x.contiguous().float()
+    frames = [clip_frames(n, n_fft, hop) for n in host]
+    frames_out = max(frames)
+    window, tw = _get_tables(n_fft, win_length, x.device)
+    n_mels = mel_basis.shape[0]
+    mel = torch.empty(b, n_mels, frames_out, dtype=torch.float32, device=x.device)
+    lens32 = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
+    if frames_out > 0:
+        with profiler.region("melspec_ragged", nbytes=sum(host) * 4 + mel.numel() * 4, bound="hbm"):
+            N.check(N.lib().smt_melspec_ragged(N.ptr(x), N.ptr(lens32), N.ptr(window), N.ptr(tw), N.ptr(mel_basis), N.ptr(band),
+                                               N.ptr(mel), b, t, n_fft, hop, n_mels, frames_out, float(fill), N.stream_ptr()),
+                    "smt_melspec_ragged")
+    return mel, torch.tensor(frames, dtype=torch.int64)
+
+
 class _StftLoss(torch.autograd.Function):
     """mean_b sqrt(sum ((|Y|-|Yh|) m)^2) [+ the same on clamped log magnitudes] for ONE resolution."""
 

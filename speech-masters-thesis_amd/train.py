@@ -50,10 +50,45 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
+_batch_mels = {}
+
+
+def batch_mel_for(config, device):
+    """The BatchLogMel of a run with dataset.device_spect (one per device and front-end geometry, built on first use); None
+    without the key."""
+    if not config.dataset.get("device_spect", False):
+        return None
+    ds = config.dataset
+    key = (str(device), ds.sample_rate, ds.n_fft, ds.win_length, ds.hop_length, ds.n_mels)
+    if key not in _batch_mels:
+        from datasets.transforms import BatchLogMel
+        _batch_mels[key] = BatchLogMel(config).to(device)
+    return _batch_mels[key]
+
+
+def prepare_batch(batch, config, device, batch_mel=None):
+    """The collated batch on the device.  With dataset.device_spect and use_spect, slots 2 and 3 (spect, spect_len) are made
+    there from the waveforms -- every clip transformed alone, padded with log(1e-7), as the reference's DataLoader workers
+    leave them; the lengths are read from the collate's CPU tensor, so nothing waits for the device -- and the audio slots are
+    emptied when the model does not take audio (use_audio off).  Without the key: to_device alone."""
+    audio_len = batch[5]
+    batch = to_device(batch, device)
+    if batch_mel is None or not config.dataset.get("device_spect", False):
+        return batch
+    if config.dataset.use_spect:
+        if batch[4] is None:
+            raise ValueError("dataset.device_spect needs the waveforms in the batch (slots 4 and 5)")
+        spect, spect_len = batch_mel(batch[4], audio_len)
+        batch[2], batch[3] = spect, spect_len.to(device, non_blocking=True)
+    if not config.dataset.use_audio:
+        batch[4] = batch[5] = None
+    return batch
+
+
 def train_step(*, global_step, batch, config, model, ema, optimizer, scheduler, device, rank=0, grad_sync=None):
     """zero_grad -> supervised_step -> NaN guard -> backward -> [grad all-reduce] -> [clip] -> optimiser
     -> scheduler -> parameter EMA (reference train.py:82-143, full-precision branch)."""
-    batch = to_device(batch, device)
+    batch = prepare_batch(batch, config, device, batch_mel_for(config, device))
     if grad_sync is not None:
         grad_sync.zero_grad()
     else:
@@ -107,7 +142,7 @@ def val_epoch(*, epoch, config, model, ema, val_dataloader, writer, device):
     ema.swap()
     ys, yhs = [], []
     for batch in val_dataloader:
-        loss_dict, metrics_dict = model.supervised_step(to_device(batch, device))
+        loss_dict, metrics_dict = model.supervised_step(prepare_batch(batch, config, device, batch_mel_for(config, device)))
         accumulate_stats(len(val_dataloader), loss_dict, metrics_dict, losses, metrics)
         if "y" in loss_dict and "yh" in loss_dict and len(ys) < 4:          # train.py:274-275
             ys += list(loss_dict["y"][:4 - len(ys)]); yhs += list(loss_dict["yh"][:4 - len(yhs)])
