@@ -502,6 +502,38 @@ int smt_stft_loss_bwd(const float* y, const float* yh, const int* lens, const fl
 int smt_stft_inverse(const float* magnitude, const float* phase, const float* window, const float* twiddle, float* out,
                      int batch, int n_fft, int hop, int frames, smt_stream_t stream);
 
+/* Mel magnitudes back to linear magnitudes (the inverse of smt_melspec's basis @ |STFT|): non-negative
+ * least squares by multiplicative updates.  Per frame m = exp(mel) if log_input else mel, c_j = sum_k B[j,k]:
+ *   num_k = sum_j B[j,k] m_j;  S_k = num_k / sum_j B[j,k] c_j where that is > 0, S_k = 0 for good on a bin no filter covers;
+ *   n_iter times: r = B S;  S_k <- S_k num_k / max(sum_j B[j,k] r_j, 1e-30).
+ * mel [batch, n_mels, frames] f32 -> mag [batch, n_fft/2+1, frames] f32; mel_basis / band as for smt_melspec; lens int32
+ * [batch] on the device (frames per item, clamped to [0, frames]) or NULL for `frames` everywhere.  Columns f >= lens[b] are
+ * written as exact zeros and mel is not read there.  One launch, no workspace, no atomics: equal inputs give equal bits.
+ * Errors: null pointer, n_fft outside {256, 512, 1024, 2048}, n_mels outside [1, 1024], n_iter < 0, batch outside [0, 65535],
+ * frames < 0.  batch == 0 or frames == 0 launches nothing. */
+int smt_mel_invert(const float* mel, const int* lens, const float* mel_basis, const int* band, float* mag, int batch, int n_fft,
+                   int n_mels, int frames, int n_iter, int log_input, smt_stream_t stream);
+
+/* Fast Griffin-Lim, every iteration queued by this one call.  With alpha = momentum / (1 + momentum),
+ * per item:  c = S e^{i phi0}, t = 0;  n_iter times: x = istft(c), R = stft(x), a = R - alpha t, t = R, c = S a / (|a| + 1e-16);
+ * wave = istft(c).  istft is smt_stft_inverse on the item's own F_b = lens[b] frames (lens int32 [batch] on the device,
+ * clamped to [0, frames], or NULL); stft is the complex spectrum of the item's own T_b = (F_b - 1) hop + n_fft - 2 pad samples,
+ * reflected about its own two ends, so an item's waveform does not depend on the batch around it.
+ *   mag [batch, n_fft/2+1, frames] f32;  exactly one of phase0 (same shape, radians) and seeds (int32 [batch] on the device):
+ *   with seeds, phi0 = 2 pi u in fp32, u = ((bits >> 9) + 0.5) 2^-23, bits = fmix32(fmix32(fmix32(seed_b) + f 0x9E3779B1) +
+ *   k 0x85EBCA77) -- a draw depends on (seed_b, f, k) only.  mag and phase0 are not read at f >= F_b.
+ *   wave [batch, t_max] f32, t_max = (frames - 1) hop + n_fft - 2 pad: exact zeros at or past T_b; an item with F_b = 0, or too
+ *   short to transform (T_b <= pad), is all zeros.
+ * workspace (smt_griffin_lim_workspace_bytes): t [batch, frames, K] complex, S transposed [batch, frames, K], the windowed rows
+ * [batch, frames, n_fft] and x [batch, t_max], all f32, each rounded up to 256 bytes.  Two launches per iteration, no
+ * floating-point atomics: bit-reproducible.  Errors: null pointer, both or neither of phase0 / seeds, n_fft outside {256, 512,
+ * 1024, 2048}, hop outside [1, n_fft], n_iter < 0, momentum outside [0, 1), batch outside [0, 65535], frames < 0, t_max above
+ * 2^30, workspace too small.  batch == 0 or frames == 0 launches nothing. */
+size_t smt_griffin_lim_workspace_bytes(int batch, int n_fft, int hop, int frames);
+int smt_griffin_lim(const float* mag, const int* lens, const float* phase0, const int* seeds, const float* window,
+                    const float* twiddle, float* wave, int batch, int n_fft, int hop, int frames, int n_iter, float momentum,
+                    void* workspace, size_t workspace_bytes, smt_stream_t stream);
+
 /* Test hook (no reference counterpart): the one-wave in-LDS transform of the spectral kernels alone on ONE complex frame.
  * in / out [n_fft][2] f32, twiddle as for smt_stft_magnitude; inverse != 0 uses the conjugate twiddles (no 1/N). */
 int smt_fft_selftest(const float* in, const float* twiddle, float* out, int n_fft, int inverse, smt_stream_t stream);

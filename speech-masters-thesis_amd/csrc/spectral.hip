@@ -14,6 +14,7 @@
 //     transform (a complex FFT with conjugate twiddles), windows it and overlap-adds into dyh.
 #include <algorithm>
 
+#include "conv_common.h"   // fmix32
 #include "smt_common.h"
 
 namespace smt {
@@ -805,6 +806,277 @@ __global__ __launch_bounds__(64) void fft_selftest_kernel(const cplx* __restrict
   for (int n = lane; n < N; n += 64) out[n] = Z[fidx<N, 64>(n)];
 }
 
+// ------------------------------------------------------------- mel inversion and Griffin-Lim ------
+// Mel magnitudes back to linear magnitudes: non-negative least squares of m = B S by multiplicative updates,
+//   num_k = sum_j B[j,k] m_j;  S_k = num_k / sum_j B[j,k] c_j (c_j = sum_k B[j,k]) where that is > 0, else 0 for good;
+//   n_iter times: r = B S;  S_k <- S_k num_k / max(sum_j B[j,k] r_j, 1e-30).
+// A workgroup owns MI_FR consecutive frames of one item, so the rows of mel [batch, n_mels, frames] and of mag [batch, K,
+// frames] are touched in runs of MI_FR floats.  S [K][MI_FR], m and r [n_mels][MI_FR] stay in LDS for all iterations; a thread
+// keeps num of its (bin, frame) elements in registers.  r walks each filter's band as melspec_wave_kernel does; the update
+// of bin k walks the filters jlo_k .. jhi_k - 1 whose band holds k (found once, two 16-bit halves of `cover`); the basis
+// between them is read as it is, because outside a filter's band it is zero by the definition of `band`.
+constexpr int MI_FR = 8;
+
+template <int N>
+__global__ __launch_bounds__(256) void mel_invert_kernel(const float* __restrict__ mel, const int* __restrict__ lens,
+                                                         const float* __restrict__ basis, const int* __restrict__ band,
+                                                         float* __restrict__ mag, int frames, int n_mels, int n_iter,
+                                                         int log_input) {
+  constexpr int K = N / 2 + 1, FR = MI_FR, NE = K * FR, PER = (NE + 255) / 256;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  float* S = reinterpret_cast<float*>(smem_raw);      // [K][FR]
+  float* mv = S + NE;                                 // [n_mels][FR]
+  float* r = mv + n_mels * FR;                        // [n_mels][FR]
+  float* csum = r + n_mels * FR;                      // [n_mels]
+  int* cover = reinterpret_cast<int*>(csum + n_mels); // [K]
+  const int tid = threadIdx.x, b = blockIdx.y, f0 = blockIdx.x * FR;
+  const int len = lens ? min(max(lens[b], 0), frames) : frames;
+  float* ob = mag + (size_t)b * K * frames;
+  auto live = [&](int f) { return f < len; };         // the one test of "column f belongs to item b", for the read and the write
+  if (f0 >= len) {                                    // a run of padding only (workgroup-uniform): exact zeros, mel not read
+    for (int e = tid; e < NE; e += 256) {
+      const int f = f0 + e % FR;
+      if (f < frames) ob[(size_t)(e / FR) * frames + f] = 0.f;
+    }
+    return;
+  }
+  for (int it = tid; it < n_mels * FR; it += 256) {
+    const int j = it / FR, f = f0 + it % FR;
+    float v = 0.f;                                    // a padded column of a live run: m = 0, never read
+    if (live(f)) {
+      v = mel[((size_t)b * n_mels + j) * frames + f];
+      if (log_input) v = expf(v);
+    }
+    mv[it] = v;
+  }
+  for (int j = tid; j < n_mels; j += 256) {
+    const float* row = basis + (size_t)j * K;
+    float s = 0.f;
+    for (int k = band[2 * j]; k < band[2 * j + 1]; ++k) s += row[k];
+    csum[j] = s;
+  }
+  for (int k = tid; k < K; k += 256) {
+    int jlo = n_mels, jhi = 0;
+    for (int j = 0; j < n_mels; ++j)
+      if (band[2 * j] <= k && k < band[2 * j + 1]) { jlo = min(jlo, j); jhi = j + 1; }
+    cover[k] = jlo | (jhi << 16);
+  }
+  __syncthreads();
+  float num[PER];
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int e = tid + 256 * i;
+    num[i] = 0.f;
+    if (e < NE) {
+      const int k = e / FR, fi = e % FR, cv = cover[k];
+      float n = 0.f, d = 0.f;
+      for (int j = cv & 0xFFFF; j < (cv >> 16); ++j) {
+        const float w = basis[(size_t)j * K + k];
+        n = fmaf(w, mv[j * FR + fi], n);
+        d = fmaf(w, csum[j], d);
+      }
+      const bool covered = d > 0.f;
+      num[i] = covered ? n : 0.f;
+      S[e] = covered ? n / d : 0.f;
+    }
+  }
+  for (int iter = 0; iter < n_iter; ++iter) {
+    __syncthreads();
+    for (int it = tid; it < n_mels * FR; it += 256) {
+      const int j = it / FR, fi = it % FR;
+      const float* row = basis + (size_t)j * K;
+      const int lo = band[2 * j], hi = band[2 * j + 1];
+      float s = 0.f;
+      for (int k = lo; k < hi; k += 8) {
+        float w[8], v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int kk = min(k + u, hi - 1);
+          w[u] = row[kk];
+          v[u] = S[kk * FR + fi];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s = fmaf(k + u < hi ? w[u] : 0.f, v[u], s);
+      }
+      r[it] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int e = tid + 256 * i;
+      if (e < NE) {
+        const int k = e / FR, fi = e % FR, cv = cover[k];
+        float d = 0.f;
+        for (int j = cv & 0xFFFF; j < (cv >> 16); ++j) d = fmaf(basis[(size_t)j * K + k], r[j * FR + fi], d);
+        S[e] = S[e] * num[i] / fmaxf(d, 1e-30f);      // an uncovered bin: S = num = 0 stays 0
+      }
+    }
+  }
+  // every thread writes the elements it owns (no barrier needed)
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int e = tid + 256 * i;
+    if (e < NE) {
+      const int f = f0 + e % FR;
+      if (f < frames) ob[(size_t)(e / FR) * frames + f] = live(f) ? S[e] : 0.f;
+    }
+  }
+}
+
+// Fast Griffin-Lim (Perraudin et al. 2013), alpha = momentum / (1 + momentum):
+//   c0 = S e^{i phi0};  i = 1 .. n_iter: x = istft(c), R = stft(x), a = R - alpha t, t = R, c = S a / (|a| + 1e-16);  wave = istft(c).
+// istft is STFT.inverse (stft_inverse_kernel above), stft the spectrum of the item's own T_b = (F_b - 1) hop + N - 2 pad
+// samples reflected about its own ends.  Per iteration two launches, modelled on the loss backward: gl_step_wave_kernel (one
+// wave per frame: windowed frame of x -> FFT -> projection in place -> inverse FFT -> windowed row) and gl_gather_kernel (every
+// sample adds its <= ceil(N / hop) rows in ascending frame order and divides by the window sum-square of ITS item's F_b
+// frames).  gl_init_wave_kernel makes the rows of c0 and leaves S transposed to [batch, frames, K] for the steps, which then
+// read it, like t, with consecutive bins on consecutive lanes.  No floating-point atomics anywhere.
+__device__ __forceinline__ int gl_item_frames(const int* __restrict__ lens, int b, int frames, int n_fft, int hop, int pad) {
+  const int F = lens ? min(max(lens[b], 0), frames) : frames;
+  // T_b <= pad: the reflection would reach past the item's other end.  (T_b + 2 pad = (F_b - 1) hop + n_fft >= n_fft always.)
+  return (F > 0 && (F - 1) * hop + n_fft - 2 * pad <= pad) ? 0 : F;
+}
+
+// window[n] * Re(Z[n]) of one frame as 16-byte pieces
+template <int N>
+__device__ __forceinline__ void gl_write_row(const cplx* Z, const float* __restrict__ window, float* __restrict__ row, int lane) {
+#pragma unroll
+  for (int i = 0; i < N / 256; ++i) {
+    const float4 w = *reinterpret_cast<const float4*>(window + 4 * lane + 256 * i);
+    float4 o;
+    o.x = w.x * Z[fidx<N, 64>(4 * lane + 256 * i)].x;
+    o.y = w.y * Z[fidx<N, 64>(4 * lane + 256 * i + 1)].x;
+    o.z = w.z * Z[fidx<N, 64>(4 * lane + 256 * i + 2)].x;
+    o.w = w.w * Z[fidx<N, 64>(4 * lane + 256 * i + 3)].x;
+    *reinterpret_cast<float4*>(row + 4 * lane + 256 * i) = o;
+  }
+}
+
+// Weighted one-sided spectrum of the inverse real FFT in place: Z[k] = wgt_k c_k (wgt = 1/N at bins 0 and N/2, whose imaginary
+// parts drop out, 2/N between), mirror half zero.
+template <int N>
+__device__ __forceinline__ void gl_put_bin(cplx* Z, int k, float re, float im) {
+  const bool edge = (k == 0) || (k == N / 2);
+  const float wgt = edge ? 1.f / (float)N : 2.f / (float)N;
+  const int km = (N - k) & (N - 1);
+  if (km != k) Z[fidx<N, 64>(km)] = {0.f, 0.f};
+  Z[fidx<N, 64>(k)] = {wgt * re, edge ? 0.f : wgt * im};
+}
+
+template <int N>
+__global__ __launch_bounds__(256, WAVE_LB) void gl_init_wave_kernel(const float* __restrict__ mag, const float* __restrict__ phase0,
+                                                           const int* __restrict__ seeds, const int* __restrict__ lens,
+                                                           const float* __restrict__ window, const cplx* __restrict__ tw,
+                                                           float* __restrict__ st, float* __restrict__ rows, int hop, int pad,
+                                                           int frames) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  constexpr int K = N / 2 + 1;
+  const int wave = threadIdx.x >> 6, b = blockIdx.y;
+  int lane = threadIdx.x & 63;
+  cplx* Z = reinterpret_cast<cplx*>(smem_raw) + (size_t)wave * frame_padded<N>();
+  const int f = blockIdx.x * 4 + wave;
+  if (f < gl_item_frames(lens, b, frames, N, hop, pad)) {       // wave-uniform; no workgroup barrier in this kernel
+    WaveFft<N> wc;
+    wc.load(tw, lane);
+    const float* mb = mag + (size_t)b * K * frames + f;
+    const float* pb = phase0 ? phase0 + (size_t)b * K * frames + f : nullptr;
+    float* sb = st + ((size_t)b * frames + f) * K;
+    // generated phases: the counter hash of the code sampler (vqtts_codes.hip), a draw depends on (seed_b, f, k) only
+    const unsigned key = seeds ? fmix32(fmix32((unsigned)seeds[b]) + (unsigned)f * 0x9E3779B1u) : 0u;
+    auto bin = [&](int k) {
+      const float m = mb[(size_t)k * frames];
+      float ph;
+      if (pb) ph = pb[(size_t)k * frames];
+      else {
+        const unsigned bits = fmix32(key + (unsigned)k * 0x85EBCA77u);
+        const float u = ((float)(bits >> 9) + 0.5f) * 1.1920928955078125e-07f;      // exact, strictly inside (0, 1)
+        ph = 6.28318530717958647692f * u;
+      }
+      float s, c;
+      sincosf(ph, &s, &c);
+      sb[k] = m;
+      gl_put_bin<N>(Z, k, m * c, m * s);
+    };
+#pragma unroll 2
+    for (int i = 0; i < N / 128; ++i) bin(lane + 64 * i);
+    if (lane == 0) bin(N / 2);
+    wave_fence();
+    wave_fft<N, true>(Z, wc, lane);
+    gl_write_row<N>(Z, window, rows + ((size_t)b * frames + f) * N, lane);
+  }
+}
+
+template <int N>
+__global__ __launch_bounds__(256, WAVE_LB) void gl_step_wave_kernel(const float* __restrict__ x, const float* __restrict__ st,
+                                                           const int* __restrict__ lens, const float* __restrict__ window,
+                                                           const cplx* __restrict__ tw, cplx* __restrict__ tprev,
+                                                           float* __restrict__ rows, int hop, int pad, int frames, int t_max,
+                                                           float alpha, int first) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  constexpr int K = N / 2 + 1;
+  const int wave = threadIdx.x >> 6, b = blockIdx.y;
+  int lane = threadIdx.x & 63;
+  cplx* Z = reinterpret_cast<cplx*>(smem_raw) + (size_t)wave * frame_padded<N>();
+  const int f = blockIdx.x * 4 + wave;      // one frame per wave, no frame loop (see stft_loss_fwd_wave_kernel)
+  const int Fb = gl_item_frames(lens, b, frames, N, hop, pad);
+  if (f < Fb) {
+    WaveFft<N> wc;
+    wc.load(tw, lane);
+    const int Tb = (Fb - 1) * hop + N - 2 * pad;          // the item's own length: reflection about ITS ends
+    const float* xb = x + (size_t)b * t_max;
+    wave_load_frame<N, false>(Z, wc, xb, xb, window, f * hop - pad, Tb, lane);
+    wave_fft<N, false>(Z, wc, lane);
+    const float* sb = st + ((size_t)b * frames + f) * K;
+    cplx* tb = tprev + ((size_t)b * frames + f) * K;
+    // projection IN PLACE: bin k and its mirror are rewritten by the lane that read bin k, and no lane reads a bin above N / 2
+    auto bin = [&](int k) {
+      const cplx R = Z[fidx<N, 64>(k)];
+      cplx a = R;
+      if (!first) {                                       // t = 0 before the first step: not read, so never initialised
+        const cplx t = tb[k];
+        a.x = R.x - alpha * t.x;
+        a.y = R.y - alpha * t.y;
+      }
+      tb[k] = R;
+      const float sc = sb[k] / (sqrtf(a.x * a.x + a.y * a.y) + 1e-16f);
+      gl_put_bin<N>(Z, k, sc * a.x, sc * a.y);
+    };
+#pragma unroll 2
+    for (int i = 0; i < N / 128; ++i) bin(lane + 64 * i);
+    if (lane == 0) bin(N / 2);
+    wave_fence();
+    wave_fft<N, true>(Z, wc, lane);
+    gl_write_row<N>(Z, window, rows + ((size_t)b * frames + f) * N, lane);
+  }
+}
+
+// dst[b, i] = (sum over the frames f < F_b that cover sample i of rows[b, f, i + pad - f hop], frames ascending) / (the window
+// sum-square of those frames, where it exceeds float tiny); exact zero at or past T_b.
+__global__ __launch_bounds__(256) void gl_gather_kernel(const float* __restrict__ rows, const int* __restrict__ lens,
+                                                        const float* __restrict__ window, float* __restrict__ dst, int N,
+                                                        int hop, int pad, int frames, int t_max) {
+  const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  if (i >= t_max) return;
+  const int Fb = gl_item_frames(lens, b, frames, N, hop, pad);
+  const int Tb = Fb > 0 ? (Fb - 1) * hop + N - 2 * pad : 0;
+  float v = 0.f;
+  if (i < Tb) {
+    const float* rb = rows + (size_t)b * frames * N;
+    const int q = i + pad;                                      // position in the untrimmed overlap-add
+    const int f_hi = min(Fb - 1, q / hop);
+    const int f_lo = q - N + 1 > 0 ? (q - N + hop) / hop : 0;   // ceil((q - N + 1) / hop)
+    float s = 0.f, wss = 0.f;
+    for (int f = f_lo; f <= f_hi; ++f) {
+      const int n = q - f * hop;
+      const float w = window[n];
+      s += rb[(size_t)f * N + n];
+      wss = fmaf(w, w, wss);
+    }
+    v = wss > 1.17549435e-38f ? s / wss : s;                    // librosa.util.tiny(float32)
+  }
+  dst[(size_t)b * t_max + i] = v;
+}
+
 }  // namespace smt
 
 using namespace smt;
@@ -1070,5 +1342,100 @@ extern "C" int smt_stft_inverse(const float* magnitude, const float* phase, cons
   stft_inverse_norm_kernel<<<(unsigned)std::min<long long>(2048, (total + 255) / 256), 256, 0, stream>>>(window, out, n_fft, hop,
                                                                                                    pad, frames, t_out, batch);
   SMT_CHECK_LAUNCH("stft_inverse_norm");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------- mel inversion and Griffin-Lim ------
+#define SMT_CHECK_NFFT_HOP(name, n_fft, hop)                                                                          \
+  do {                                                                                                                \
+    SMT_CHECK_ARG((n_fft) == 256 || (n_fft) == 512 || (n_fft) == 1024 || (n_fft) == 2048,                             \
+                  name ": n_fft=%d unsupported (256, 512, 1024, 2048)", (n_fft));                                     \
+    SMT_CHECK_ARG((hop) >= 1 && (hop) <= (n_fft), name ": hop=%d outside [1, n_fft=%d]", (hop), (n_fft));             \
+  } while (0)
+
+template <int N, typename... Args>
+static void mel_invert_launch(dim3 grid, size_t lds, hipStream_t stream, Args... args) {
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)mel_invert_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  mel_invert_kernel<N><<<grid, 256, lds, stream>>>(args...);
+}
+
+extern "C" int smt_mel_invert(const float* mel, const int* lens, const float* mel_basis, const int* band, float* mag, int batch,
+                              int n_fft, int n_mels, int frames, int n_iter, int log_input, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(mel && mel_basis && band && mag, "smt_mel_invert: null pointer");
+  SMT_CHECK_ARG(n_fft == 256 || n_fft == 512 || n_fft == 1024 || n_fft == 2048,
+                "smt_mel_invert: n_fft=%d unsupported (256, 512, 1024, 2048)", n_fft);
+  SMT_CHECK_ARG(n_mels >= 1 && n_mels <= 1024, "smt_mel_invert: n_mels=%d outside [1, 1024]", n_mels);
+  SMT_CHECK_ARG(n_iter >= 0, "smt_mel_invert: n_iter=%d, need >= 0", n_iter);
+  SMT_CHECK_ARG(batch >= 0 && batch <= 65535, "smt_mel_invert: batch=%d outside [0, 65535] (one grid row per item)", batch);
+  SMT_CHECK_ARG(frames >= 0, "smt_mel_invert: frames=%d, need >= 0", frames);
+  if (batch == 0 || frames == 0) return 0;
+  const int bins = n_fft / 2 + 1;
+  // S [K][MI_FR], m and r [n_mels][MI_FR], c [n_mels], cover [K]: 37 KB at 2048 / 80 mels, 107 KB at the n_mels limit
+  const size_t lds = sizeof(float) * ((size_t)bins * MI_FR + 2 * (size_t)n_mels * MI_FR + n_mels + bins);
+  const dim3 grid((frames + MI_FR - 1) / MI_FR, batch);
+  SMT_WAVE_DISPATCH(n_fft, (mel_invert_launch<N>(grid, lds, stream, mel, lens, mel_basis, band, mag, frames, n_mels, n_iter, log_input)));
+  SMT_CHECK_LAUNCH("mel_invert");
+  return 0;
+}
+
+// workspace of smt_griffin_lim, each part rounded up to 256 bytes (K = n_fft / 2 + 1, t_max = (frames - 1) hop + n_fft - 2 pad):
+//   t [batch, frames, K] complex f32 | S transposed [batch, frames, K] f32 | rows [batch, frames, n_fft] f32 | x [batch, t_max] f32
+struct GlWorkspace { size_t t, st, rows, x, total; long long t_max; };
+static GlWorkspace gl_workspace(int batch, int n_fft, int hop, int frames) {
+  GlWorkspace w{};
+  const size_t bf = (size_t)batch * frames, bins = n_fft / 2 + 1;
+  w.t_max = (long long)(frames - 1) * hop + n_fft - 2 * ((n_fft - hop) / 2);
+  w.t = 0;
+  w.st = w.t + align_up(bf * bins * sizeof(cplx), 256);
+  w.rows = w.st + align_up(bf * bins * sizeof(float), 256);
+  w.x = w.rows + align_up(bf * n_fft * sizeof(float), 256);
+  w.total = w.x + align_up((size_t)batch * (size_t)w.t_max * sizeof(float), 256);
+  return w;
+}
+
+extern "C" size_t smt_griffin_lim_workspace_bytes(int batch, int n_fft, int hop, int frames) {
+  if (batch <= 0 || frames <= 0 || n_fft <= 0 || hop < 1 || hop > n_fft) return 0;
+  return gl_workspace(batch, n_fft, hop, frames).total;
+}
+
+extern "C" int smt_griffin_lim(const float* mag, const int* lens, const float* phase0, const int* seeds, const float* window,
+                               const float* twiddle, float* wave, int batch, int n_fft, int hop, int frames, int n_iter,
+                               float momentum, void* workspace, size_t workspace_bytes, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(mag && window && twiddle && wave, "smt_griffin_lim: null pointer");
+  SMT_CHECK_ARG((phase0 != nullptr) != (seeds != nullptr), "smt_griffin_lim: exactly one of phase0 and seeds must be given, got %s",
+                phase0 ? "both" : "neither");
+  SMT_CHECK_NFFT_HOP("smt_griffin_lim", n_fft, hop);
+  SMT_CHECK_ARG(n_iter >= 0, "smt_griffin_lim: n_iter=%d, need >= 0", n_iter);
+  SMT_CHECK_ARG(momentum >= 0.f && momentum < 1.f, "smt_griffin_lim: momentum=%g outside [0, 1)", (double)momentum);
+  SMT_CHECK_ARG(batch >= 0 && batch <= 65535, "smt_griffin_lim: batch=%d outside [0, 65535] (one grid row per item)", batch);
+  SMT_CHECK_ARG(frames >= 0, "smt_griffin_lim: frames=%d, need >= 0", frames);
+  if (batch == 0 || frames == 0) return 0;
+  const GlWorkspace ws = gl_workspace(batch, n_fft, hop, frames);
+  SMT_CHECK_ARG(ws.t_max <= (1 << 30), "smt_griffin_lim: (frames - 1) * hop + n_fft - 2 * pad = %lld samples, above 2^30", ws.t_max);
+  SMT_CHECK_ARG(workspace && workspace_bytes >= ws.total, "smt_griffin_lim: workspace too small (%zu bytes, need %zu)",
+                workspace_bytes, ws.total);
+  const int pad = (n_fft - hop) / 2, t_max = (int)ws.t_max;
+  unsigned char* base = (unsigned char*)workspace;
+  cplx* tprev = (cplx*)(base + ws.t);
+  float* st = (float*)(base + ws.st);
+  float* rows = (float*)(base + ws.rows);
+  float* x = (float*)(base + ws.x);
+  const float alpha = momentum / (1.f + momentum);
+  const dim3 ggrid((t_max + 255) / 256, batch);
+  SMT_WAVE_DISPATCH(n_fft, (wave_launch(gl_init_wave_kernel<N>, frame_padded<N>(), frames, batch, stream, mag, phase0, seeds, lens, window,
+                                        (const cplx*)twiddle, st, rows, hop, pad, frames)));
+  SMT_CHECK_LAUNCH("gl_init");
+  for (int i = 1; i <= n_iter; ++i) {
+    gl_gather_kernel<<<ggrid, 256, 0, stream>>>(rows, lens, window, x, n_fft, hop, pad, frames, t_max);
+    SMT_CHECK_LAUNCH("gl_gather");
+    SMT_WAVE_DISPATCH(n_fft, (wave_launch(gl_step_wave_kernel<N>, frame_padded<N>(), frames, batch, stream, (const float*)x, (const float*)st,
+                                          lens, window, (const cplx*)twiddle, tprev, rows, hop, pad, frames, t_max, alpha,
+                                          i == 1 ? 1 : 0)));
+    SMT_CHECK_LAUNCH("gl_step");
+  }
+  gl_gather_kernel<<<ggrid, 256, 0, stream>>>(rows, lens, window, wave, n_fft, hop, pad, frames, t_max);
+  SMT_CHECK_LAUNCH("gl_gather");
   return 0;
 }

@@ -87,6 +87,31 @@ class MelSpectrogram(nn.Module):
         return audio_len // self.hop_length
 
 
+def _front_end_kwargs(config, kwargs):
+    ds = config.dataset
+    return dict(sample_rate=ds.sample_rate, n_fft=ds.n_fft, win_length=ds.win_length, hop_length=ds.hop_length,
+                n_mels=ds.n_mels, f_min=0.0, f_max=8000.0, **kwargs)
+
+
+class GriffinLim(MelSpectrogram):
+    """Log-mels back to waveforms on the device: the non-negative least-squares inverse of this front
+    end's own `mel_basis @ |STFT|` (spectral.mel_invert), then fast Griffin-Lim on the linear magnitudes
+    (spectral.griffin_lim).  Constructed like BatchLogMel, so it shares `mel_basis` / `band` with the forward transform.  The
+    reference does this on the host with librosa.feature.inverse.mel_to_audio (utils/train_utils.py:198-246), which treats the
+    magnitude-mels as powers; this inverts what MelSpectrogram.forward computes."""
+
+    def __init__(self, config=None, **kwargs):
+        super().__init__(**(_front_end_kwargs(config, kwargs) if config is not None else kwargs))
+
+    def forward(self, log_mel, frames, *, n_iter=32, nnls_iter=32, momentum=0.99, seed=0):
+        """log_mel [B, n_mels, F] on the device, frames integer [B] on the CPU -> (wave [B, T_max], wave_lengths int64 [B] on
+        the CPU); item b has frames[b] * hop samples when n_fft - hop is even."""
+        stft = self.stft
+        mag = spectral.mel_invert(log_mel, frames, self.mel_basis, self.band, n_iter=nnls_iter, log_input=True)
+        return spectral.griffin_lim(mag, frames, stft.n_fft, stft.hop_length, stft.win_length, n_iter=n_iter, momentum=momentum,
+                                    seed=seed)
+
+
 class BatchLogMel(MelSpectrogram):
     """The log-mels of a collated, zero-padded audio batch as the reference's DataLoader workers make them (ljspeech.py:86-88,
     :128-132): every clip transformed ALONE -- reflected about its own end -- and the shorter ones padded with log(1e-7).  One

@@ -2,18 +2,23 @@
 batched): mel spectrograms from a GlowTTS, waveforms from a VQTTS.
 
     python -m scripts.synthesize --log_dir ./logs/glow_tts --ckpt_num 5000 (--tokens utterances.txt | --text sentences.txt) --dump_dir ./outputs \
-        [--batch_size 16] [--noise_scale 0.667] [--length_scale 1.0] [--seed 0] [--temperature 0] [--min_p 0] [--speaker N]
+        [--batch_size 16] [--noise_scale 0.667] [--length_scale 1.0] [--seed 0] [--temperature 0] [--min_p 0] [--speaker N] \
+        [--vocoder griffin_lim [--gl_iters 32]]
 
 ``--tokens`` holds one utterance per line as whitespace-separated integer ids (the ids of datasets/synthetic.py, or the ones
 models/parser.py emits).  ``--text`` holds one sentence per line instead, for a checkpoint trained with
 ``dataset.text_frontend``: the sentences go through that front end as the dataset's transcripts did.
 Exactly one of the two is given.  Writes
 ``<dump_dir>/<ModelClass>@<ckpt>/mel_<i>.npy`` (float32 [n_mels, frames], trimmed to the utterance's length) and one
-``mel_spectrograms.png``.  Synthesis runs on MI355X through libsmt_hip.so (`GlowTTS.infer`); there is no vocoder.
+``mel_spectrograms.png``.  Synthesis runs on MI355X through libsmt_hip.so (`GlowTTS.infer`).  With ``--vocoder griffin_lim``
+every spectrogram is also inverted to ``wav_<i>.wav`` (16-bit mono, ``frames * hop_length`` samples, clamped to [-1, 1]) on the
+device: 32 non-negative least-squares updates back to linear magnitudes, then ``--gl_iters`` iterations of fast Griffin-Lim at
+momentum 0.99 (datasets.transforms.GriffinLim).  Utterance i starts from the phases of seed ``--seed`` + i
+whatever ``--batch_size``.  There is no neural vocoder; without the flag the outputs are the spectrograms alone.
 
 A token-to-waveform model (VQTTS, `VQTTS.infer`) writes ``wav_<i>.wav`` (16-bit mono at the dataset's sample rate, trimmed to
 the utterance's length) and the log-mel spectrograms of the waveforms as ``mel_spectrograms.png``; it has no prior noise,
-so ``--noise_scale`` other than 1 is refused for it.  ``--temperature`` > 0 draws its codes instead of taking the argmax
+so ``--noise_scale`` other than 1 is refused for it, and it makes waveforms itself, so ``--vocoder`` is refused too.  ``--temperature`` > 0 draws its codes instead of taking the argmax
 (``--min_p`` truncates the draw); utterance i of the tokens file draws with seed ``--seed`` + i whatever ``--batch_size``.  GlowTTS
 has no codes and refuses both flags.  ``--speaker N`` is the voice of every utterance: required by a multi-speaker GlowTTS
 checkpoint (``n_speakers`` > 1 in its config), an error for any other model."""
@@ -48,7 +53,14 @@ def parse_args(argv=None):
     p.add_argument("--temperature", type=float, default=0.0, help="VQTTS: temperature of the code draw (0 = argmax)")
     p.add_argument("--min_p", type=float, default=0.0, help="VQTTS: draw among the codes with p >= min_p * p_max (0 = all)")
     p.add_argument("--speaker", type=int, default=None, help="Multi-speaker GlowTTS: the speaker id of every utterance")
-    return p.parse_args(argv)
+    p.add_argument("--vocoder", type=str, default=None, choices=["griffin_lim"],
+                   help="GlowTTS: also invert every spectrogram to wav_<i>.wav on the device")
+    p.add_argument("--gl_iters", type=int, default=None, help="Iterations of fast Griffin-Lim with --vocoder griffin_lim (32)")
+    args = p.parse_args(argv)
+    args.gl_iters_given = args.gl_iters is not None
+    if args.gl_iters is None:
+        args.gl_iters = 32
+    return args
 
 
 def read_tokens(path):
@@ -100,6 +112,31 @@ def draw_mels(dump_dir, mels):
                        mel_grid([np.pad(m, ((0, 0), (0, width - m.shape[1])), constant_values=m.min()) for m in drawn]))
 
 
+def refuse_vocoder_for(model):
+    raise ValueError(f"--vocoder applies to a token-to-spectrogram model; {type(model).__name__} makes waveforms itself")
+
+
+def vocode(config, yh, y_lengths, first, args, dump_dir, device):
+    """wav_<first + i>.wav of one batch of spectrograms; utterance number j starts from the phases of seed --seed + j.  An
+    utterance too short to invert (fewer samples than the reflect padding) is written as silence of its length."""
+    from datasets.transforms import GriffinLim
+    from smt_amd.spectral import invertible
+    ds = config.dataset
+    lengths = [int(n) for n in y_lengths.tolist()]
+    ok = [invertible(n, ds.n_fft, ds.hop_length) for n in lengths]
+    frames = torch.tensor([n if k else 0 for n, k in zip(lengths, ok)])
+    wave, _ = GriffinLim(config).to(device)(yh.float(), frames, n_iter=args.gl_iters,
+                                            seed=[(args.seed + first + i) % (1 << 31) for i in range(len(lengths))])
+    wave = wave.clamp(-1, 1).cpu().numpy()
+    for i, n in enumerate(lengths):
+        samples = n * ds.hop_length
+        if not ok[i] and n > 0:
+            logger.info("utterance %d has %d frames: too short to invert, written as silence", first + i, n)
+        out = np.zeros(samples, dtype=np.float32)
+        out[:min(samples, wave.shape[1])] = wave[i, :samples]
+        write_wav(os.path.join(dump_dir, f"wav_{first + i}.wav"), out, ds.sample_rate)
+
+
 def synthesize_waveforms(model, config, utterances, args, dump_dir, device):
     """The token-to-waveform branch: wav files and the log-mel image of what was synthesized."""
     from datasets.transforms import MelSpectrogram
@@ -134,6 +171,10 @@ def main(argv=None):
         raise ValueError(f"--temperature must be a finite number >= 0, got {args.temperature}")
     if not 0.0 <= args.min_p <= 1.0 or (args.temperature == 0 and args.min_p != 0):
         raise ValueError(f"--min_p must lie in [0, 1] and applies to --temperature > 0 only, got {args.min_p}")
+    if args.gl_iters < 0:
+        raise ValueError(f"--gl_iters must be >= 0, got {args.gl_iters}")
+    if args.gl_iters_given and args.vocoder is None:
+        raise ValueError("--gl_iters applies to --vocoder griffin_lim")
     if not torch.cuda.is_available():
         raise RuntimeError("synthesize runs the model on MI355X (libsmt_hip.so); no GPU is visible")
     source = args.tokens if args.tokens is not None else args.text
@@ -160,6 +201,8 @@ def main(argv=None):
         raise ValueError(f"--speaker applies to a multi-speaker GlowTTS checkpoint; this {type(model).__name__} is single-speaker")
     if n_speakers > 1 and not 0 <= args.speaker < n_speakers:
         raise ValueError(f"--speaker must lie in [0, {n_speakers}), got {args.speaker}")
+    if isinstance(model, TokenToWaveformModel) and args.vocoder is not None:
+        refuse_vocoder_for(model)
     if isinstance(model, TokenToWaveformModel):
         return synthesize_waveforms(model, config, utterances, args, dump_dir, device)
     if args.temperature != 0.0 or args.min_p != 0.0:
@@ -169,6 +212,8 @@ def main(argv=None):
     for x, x_lengths in batches(utterances, args.batch_size):
         voice = {} if args.speaker is None else {"speaker": args.speaker}
         yh, y_lengths = model.infer(x, x_lengths, noise_scale=args.noise_scale, length_scale=args.length_scale, **voice)
+        if args.vocoder is not None:
+            vocode(config, yh, y_lengths, len(mels), args, dump_dir, device)
         yh = yh.cpu().numpy()
         mels += [np.ascontiguousarray(yh[i, :, :n], dtype=np.float32) for i, n in enumerate(y_lengths.tolist())]
     for i, m in enumerate(mels):

@@ -101,6 +101,10 @@ _SIGNATURES = {
     "smt_stft_loss_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int,
                                   c_ptr, c_size, c_ptr]),
     "smt_stft_inverse": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
+    "smt_mel_invert": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr]),
+    "smt_griffin_lim_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int]),
+    "smt_griffin_lim": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_f32,
+                                c_ptr, c_size, c_ptr]),
     "smt_fft_selftest": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr]),
     "smt_conv_out_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr,
                                  c_size, c_ptr]),

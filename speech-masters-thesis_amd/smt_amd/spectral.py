@@ -147,6 +147,110 @@ def log_mel_ragged(x, lens, mel_basis, band, n_fft, hop, win_length, fill):
     return mel, torch.tensor(frames, dtype=torch.int64)
 
 
+def _host_lens(what, lens, batch, frames):
+    """The per-item frame counts of a ragged spectrogram batch as Python ints, checked on the host copy (no device wait)."""
+    if not isinstance(lens, torch.Tensor) or lens.is_cuda or lens.is_floating_point() or lens.is_complex() \
+            or lens.dtype == torch.bool:
+        raise ValueError(f"{what}: lens must be an integer tensor on the CPU (frames per item)")
+    if lens.shape != (batch,):
+        raise ValueError(f"{what}: lens must hold {batch} lengths, got shape {tuple(lens.shape)}")
+    host = [int(v) for v in lens.tolist()]
+    for i, n in enumerate(host):
+        if not 0 <= n <= frames:
+            raise ValueError(f"{what}: item {i} has {n} frames, outside [0, frames={frames}]")
+    return host
+
+
+@torch.no_grad()
+def mel_invert(mel, lens, mel_basis, band, n_iter=32, log_input=True):
+    """mel [B, n_mels, F] (log-mel as MelSpectrogram makes it, or mel magnitudes with log_input=False), lens integer [B] ON THE
+    CPU -> linear magnitudes [B, K, F], K = mel_basis.shape[1]: the non-negative least-squares inverse of `mel_basis @ |STFT|`
+    by n_iter multiplicative updates in ONE launch (smt_mel_invert).  Columns at or past lens[b] are exact
+    zeros and mel is not read there."""
+    if mel.dim() != 3 or mel.shape[1] != mel_basis.shape[0]:
+        raise ValueError(f"mel_invert: mel must be [B, n_mels={mel_basis.shape[0]}, frames], got shape {tuple(mel.shape)}")
+    if n_iter < 0:
+        raise ValueError(f"mel_invert: n_iter={n_iter}, need >= 0")
+    b, n_mels, frames = mel.shape
+    host = _host_lens("mel_invert", lens, b, frames)
+    bins = mel_basis.shape[1]
+    mel = mel.contiguous().float()
+    mag = torch.empty(b, bins, frames, dtype=torch.float32, device=mel.device)
+    if b == 0 or frames == 0:
+        return mag
+    lens32 = torch.tensor(host, dtype=torch.int32).to(mel.device, non_blocking=True)
+    with profiler.region("mel_invert", nbytes=sum(host) * (n_mels + bins) * 4, bound="hbm"):
+        N.check(N.lib().smt_mel_invert(N.ptr(mel), N.ptr(lens32), N.ptr(mel_basis), N.ptr(band), N.ptr(mag), b, 2 * (bins - 1),
+                                       n_mels, frames, int(n_iter), int(bool(log_input)), N.stream_ptr()), "smt_mel_invert")
+    return mag
+
+
+def inverse_samples(frames, n_fft, hop):
+    """Samples STFT.inverse makes of `frames` frames: (frames - 1) hop + n_fft - 2 pad, so num_frames() of it is `frames`."""
+    return (frames - 1) * hop + n_fft - 2 * ((n_fft - hop) // 2) if frames > 0 else 0
+
+
+def invertible(frames, n_fft, hop):
+    """Whether an item of `frames` frames can be transformed back and forth: its samples must outnumber the reflect padding."""
+    return inverse_samples(frames, n_fft, hop) > (n_fft - hop) // 2
+
+
+@torch.no_grad()
+def griffin_lim(mag, lens, n_fft, hop, win_length, n_iter=32, momentum=0.99, seed=0, phase0=None):
+    """mag [B, n_fft/2+1, F] on the device, lens integer [B] ON THE CPU (frames per item) -> (wave [B, T_max] with T_max =
+    inverse_samples(F), wave_lengths int64 [B] on the CPU): fast Griffin-Lim, all n_iter iterations queued by one call
+    (smt_griffin_lim).  The start phases are phase0 [B, n_fft/2+1, F] or generated on the device from
+    `seed`: an int (item b uses (seed + b) mod 2^31) or one int per item.  Item b's samples depend on its own lens[b] frames
+    only -- not on its neighbours, its position or F -- and are exact zeros at or past wave_lengths[b]."""
+    what = "griffin_lim"
+    if n_fft not in (256, 512, 1024, 2048):
+        raise ValueError(f"{what}: n_fft={n_fft} unsupported (256, 512, 1024, 2048)")
+    if not 1 <= hop <= n_fft:
+        raise ValueError(f"{what}: hop={hop} outside [1, n_fft={n_fft}]")
+    if mag.dim() != 3 or mag.shape[1] != n_fft // 2 + 1:
+        raise ValueError(f"{what}: mag must be [B, n_fft/2+1={n_fft // 2 + 1}, frames], got shape {tuple(mag.shape)}")
+    if n_iter < 0:
+        raise ValueError(f"{what}: n_iter={n_iter}, need >= 0")
+    if not 0.0 <= momentum < 1.0:
+        raise ValueError(f"{what}: momentum={momentum} outside [0, 1)")
+    b, bins, frames = mag.shape
+    host = _host_lens(what, lens, b, frames)
+    for i, n in enumerate(host):
+        if n > 0 and not invertible(n, n_fft, hop):
+            raise ValueError(f"{what}: item {i} has {n} frames = {inverse_samples(n, n_fft, hop)} samples, not more than the "
+                             f"reflect padding {(n_fft - hop) // 2}: too short to transform")
+    seeds = None
+    if phase0 is not None:
+        if not (isinstance(seed, int) and seed == 0):
+            raise ValueError(f"{what}: give either seed or phase0, not both")
+        if phase0.shape != mag.shape:
+            raise ValueError(f"{what}: phase0 must have mag's shape {tuple(mag.shape)}, got {tuple(phase0.shape)}")
+        phase0 = phase0.contiguous().float()
+    else:
+        per_item = [(seed + i) % (1 << 31) for i in range(b)] if isinstance(seed, int) else [int(s) for s in seed]
+        if len(per_item) != b or any(not 0 <= s < (1 << 31) for s in per_item):
+            raise ValueError(f"{what}: seed must be an int or {b} ints in [0, 2^31)")
+        seeds = torch.tensor(per_item, dtype=torch.int32).to(mag.device, non_blocking=True)
+    mag = mag.contiguous().float()
+    t_max = inverse_samples(frames, n_fft, hop)
+    wave = torch.empty(b, t_max, dtype=torch.float32, device=mag.device)
+    lengths = torch.tensor([inverse_samples(n, n_fft, hop) for n in host], dtype=torch.int64)
+    if b == 0 or frames == 0:
+        return wave, lengths
+    window, tw = _get_tables(n_fft, win_length, mag.device)
+    lens32 = torch.tensor(host, dtype=torch.int32).to(mag.device, non_blocking=True)
+    ws_bytes = int(N.lib().smt_griffin_lim_workspace_bytes(b, n_fft, hop, frames))
+    ws = N.workspace.get(ws_bytes, mag.device)
+    # per iteration: x written and read as frames (n_fft / hop times, mostly from L2), t read and written, S read, rows written
+    # and read
+    per_iter = sum(host) * (bins * (8 + 8 + 4) + 2 * n_fft * 4) + 2 * int(lengths.sum()) * 4
+    with profiler.region("griffin_lim", nbytes=2 * mag.numel() * 4 + n_iter * per_iter + wave.numel() * 4, bound="hbm"):
+        N.check(N.lib().smt_griffin_lim(N.ptr(mag), N.ptr(lens32), N.ptr(phase0), N.ptr(seeds), N.ptr(window), N.ptr(tw),
+                                        N.ptr(wave), b, n_fft, hop, frames, int(n_iter), float(momentum), N.ptr(ws), ws.numel(),
+                                        N.stream_ptr()), "smt_griffin_lim")
+    return wave, lengths
+
+
 class _StftLoss(torch.autograd.Function):
     """mean_b sqrt(sum ((|Y|-|Yh|) m)^2) [+ the same on clamped log magnitudes] for ONE resolution."""
 

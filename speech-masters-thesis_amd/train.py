@@ -22,7 +22,7 @@ from utils import config as cfglib  # noqa: E402
 from utils.commons import get_dataloaders, get_model, get_optimizer, setup_logdir, to_device  # noqa: E402
 from utils.train_utils import (ScalarWriter, accumulate_stats, barrier, log_stats,  # noqa: E402
                                print_top_level_summary, restore_extra_train_state, save_audio_and_computed_spect,
-                               save_checkpoint, seed_all_rng)
+                               save_checkpoint, save_spect_and_inverted_audio, seed_all_rng)
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(levelname)s: %(message)s")
 logger = logging.getLogger("train")
@@ -140,15 +140,23 @@ def val_epoch(*, epoch, config, model, ema, val_dataloader, writer, device):
     losses, metrics = defaultdict(float), defaultdict(float)
     model.eval()
     ema.swap()
-    ys, yhs = [], []
+    ys, yhs, spect_lens = [], [], []
+    from models.base import (SpectrogramReconstructionModel, TokenToSpectrogramModel, TokenToWaveformModel,
+                             WaveformReconstructionModel)
+    spect_model = isinstance(model, (TokenToSpectrogramModel, SpectrogramReconstructionModel))
     for batch in val_dataloader:
-        loss_dict, metrics_dict = model.supervised_step(prepare_batch(batch, config, device, batch_mel_for(config, device)))
+        batch = prepare_batch(batch, config, device, batch_mel_for(config, device))
+        loss_dict, metrics_dict = model.supervised_step(batch)
         accumulate_stats(len(val_dataloader), loss_dict, metrics_dict, losses, metrics)
         if "y" in loss_dict and "yh" in loss_dict and len(ys) < 4:          # train.py:274-275
-            ys += list(loss_dict["y"][:4 - len(ys)]); yhs += list(loss_dict["yh"][:4 - len(yhs)])
+            k = 4 - len(ys)
+            if spect_model:             # frames per item: the batch's spect_len slot (the waveform models trim to the shortest)
+                spect_lens += batch[3][:k].tolist() if batch[3] is not None else [loss_dict["y"].shape[-1]] * len(loss_dict["y"][:k])
+            ys += list(loss_dict["y"][:k]); yhs += list(loss_dict["yh"][:k])
     ema.swap()
     log_stats(epoch, writer, losses, metrics, prefix="val")
-    from models.base import TokenToWaveformModel, WaveformReconstructionModel
+    if spect_model and ys:                                                                # train.py:300-304
+        save_spect_and_inverted_audio(config, epoch, writer, ys, yhs, spect_lens, n=4)
     if isinstance(model, (TokenToWaveformModel, WaveformReconstructionModel)) and ys:     # train.py:296-299
         n = min(len(ys), len(yhs))
         t = min(min(v.shape[-1] for v in ys[:n]), min(v.shape[-1] for v in yhs[:n]))

@@ -1,6 +1,7 @@
 """Helpers of the train loop (reference utils/train_utils.py): barrier, seeding, running
-averages, scalar logging, checkpoints.  The val-time spectrogram / audio dumps of the
-reference need librosa + soundfile + matplotlib and are outside the hot path."""
+averages, scalar logging, checkpoints, and the val-time spectrogram / audio dumps.  The reference makes
+those with librosa + soundfile + matplotlib; here the mel front end, the mel inversion and Griffin-Lim
+run on the device (datasets.transforms) and the files are written with the stdlib."""
 import json
 import logging
 import os
@@ -199,6 +200,51 @@ def save_audio_and_computed_spect(config, global_step, writer, audio, audio_pred
         tb.add_image("mel/val", grid, global_step, dataformats="HW")
         tb.add_audio("audio/val_gt", audio[0].cpu(), global_step=global_step, sample_rate=ds.sample_rate)
         tb.add_audio("audio/val_pred", audio_pred[0].cpu(), global_step=global_step, sample_rate=ds.sample_rate)
+    return path
+
+
+@torch.no_grad()
+def save_spect_and_inverted_audio(config, global_step, writer, spect, spect_pred, lens, n=4):
+    """Validation artefacts of a spectrogram model (reference train_utils.py:198-246): a grid of the first `n` pairs of
+    log-mels, each trimmed to its lens[i] frames, as spect/val_spect_<step>.png, and the first pair inverted to audio --
+    audio/val_audio_<step>_gt.wav and _syn.wav -- by datasets.transforms.GriffinLim on the device (32 NNLS updates, 32
+    iterations of fast Griffin-Lim at momentum 0.99; the reference calls librosa.feature.inverse.mel_to_audio).  spect,
+    spect_pred: sequences of [n_mels, frames_i] tensors.  A pair too short to invert is skipped with a log line."""
+    from datasets.transforms import GriffinLim
+    from smt_amd.spectral import invertible
+    ds, log_dir = config.dataset, config.train.log_dir
+    for sub in ("audio", "spect"):
+        os.makedirs(os.path.join(log_dir, sub), exist_ok=True)
+    k = min(n, len(spect), len(spect_pred))
+    lens = [int(v) for v in lens[:k]]
+    lens_pred = [min(lens[i], spect_pred[i].shape[-1]) for i in range(k)]
+    gts = [spect[i][:, :lens[i]].detach().float().cpu().numpy() for i in range(k)]
+    preds = [spect_pred[i][:, :lens_pred[i]].detach().float().cpu().numpy() for i in range(k)]
+    drawn = [i for i in range(k) if lens[i] > 0 and lens_pred[i] > 0]
+    path = os.path.join(log_dir, "spect", f"val_spect_{global_step}.png")
+    grid = None
+    if drawn:
+        grid = spects_to_grid([gts[i] for i in drawn], [preds[i] for i in drawn], n=len(drawn))
+        write_png_gray(path, grid)
+    tb = getattr(writer, "_tb", None)
+    if tb is not None and grid is not None:
+        tb.add_image("mel/val", grid, global_step, dataformats="HW")
+    if k == 0 or not (invertible(lens[0], ds.n_fft, ds.hop_length) and invertible(lens_pred[0], ds.n_fft, ds.hop_length)):
+        logger.info("validation audio of step %s skipped: the first spectrogram pair is too short to invert (%s frames)",
+                    global_step, (lens[0], lens_pred[0]) if k else 0)
+        return path
+    device = spect[0].device if spect[0].is_cuda else torch.device("cuda")
+    frames = max(lens[0], lens_pred[0])
+    pair = torch.zeros(2, gts[0].shape[0], frames, device=device)
+    pair[0, :, :lens[0]] = spect[0][:, :lens[0]].detach().float().to(device)
+    pair[1, :, :lens_pred[0]] = spect_pred[0][:, :lens_pred[0]].detach().float().to(device)
+    wave, wave_lens = GriffinLim(config).to(device)(pair, torch.tensor([lens[0], lens_pred[0]]))
+    wave = wave.clamp(-1, 1).cpu()
+    for i, name in enumerate(("gt", "syn")):
+        audio = wave[i, :int(wave_lens[i])]
+        write_wav(os.path.join(log_dir, "audio", f"val_audio_{global_step}_{name}.wav"), audio.numpy(), ds.sample_rate)
+        if tb is not None:
+            tb.add_audio("audio/val_gt" if i == 0 else "audio/val_pred", audio, global_step=global_step, sample_rate=ds.sample_rate)
     return path
 
 
