@@ -459,6 +459,35 @@ int smt_conv_out_bwd(const void* x, const float* weight, const int* lens, const 
                      float* dbias, int dtype, int batch, int t, int c_in, void* workspace, size_t workspace_bytes,
                      smt_stream_t stream);
 
+/* -------------------------------------------------------- WaveNet block ---- */
+/* The gate and the layer tail of WaveNetBlock (models/vqvae/resnet.py:170-181; additions under ABI 10).  z is [B, t, 2 hidden]:
+ * the first `hidden` channels of a row are the tanh half, the last `hidden` the sigmoid half.  Every tensor has an explicit batch
+ * stride bs_* and row pitch ld_*, both in elements; lens[b] is the valid length of item b (NULL: every row is valid).  A row at
+ * or past lens[b] is WRITTEN as zero and NOT READ in any input.  One launch each, no atomics, no workspace, no host
+ * synchronisation; equal inputs give equal bits; batch * t == 0 returns 0 without a launch (pointers may then be NULL).
+ * Argument errors, all decided on the host before a launch and named by smt_last_error: hidden (a positive multiple of 8; 64
+ * or 128 for the tail), dtype, null pointers, pointers not 16-byte aligned, a pitch smaller than the row width, a pitch or
+ * batch stride that is not a multiple of 8 elements, batch * t >= 2^31, an output that overlaps an input.
+ *
+ *   smt_wavenet_gate_fwd:  a[b,t,c] = tanh(z[b,t,c]) * sigmoid(z[b,t,hidden + c])                         (resnet.py:176-177)
+ *   smt_wavenet_gate_bwd:  dz[b,t,c]          = da * sigmoid(s) * (1 - tanh(t)^2)
+ *                          dz[b,t,hidden + c] = da * tanh(t) * sigmoid(s) * (1 - sigmoid(s))
+ * dtype SMT_F32 or SMT_BF16 (all tensors); arithmetic in fp32, a bf16 result is rounded once. */
+int smt_wavenet_gate_fwd(const void* z, int64_t bs_z, int ld_z, void* a, int64_t bs_a, int ld_a, const int* lens, int batch,
+                         int t, int hidden, int dtype, smt_stream_t stream);
+int smt_wavenet_gate_bwd(const void* z, int64_t bs_z, int ld_z, const void* da, int64_t bs_da, int ld_da, void* dz,
+                         int64_t bs_dz, int ld_dz, const int* lens, int batch, int t, int hidden, int dtype,
+                         smt_stream_t stream);
+/* One layer's tail in one pass (bf16, hidden 64 or 128; resnet.py:176-179):
+ *   y[b,t,:] = keep(t) * ( x[b,t,:] + bias + W_g . (tanh(z_t) * sigmoid(z_s)) ),   keep = t < lens[b]
+ * z [B,t,2 hidden], x / y [B,t,hidden]; w_packed = smt_pack_weight layout [1][c_out][c_in] of the 1x1 gate convolution with
+ * swizzle = 0 (the kernel pads the rows itself when it stages them); bias fp32 [hidden] or NULL.  The gated value is formed in
+ * fp32, rounded to bf16 once and fed to the matrix cores from registers: it is never stored.  fp32 accumulation, y rounded
+ * once.  4 hidden elements of traffic per row, against 6 hidden for smt_wavenet_gate_fwd + smt_conv1d_ntc with a residual. */
+int smt_wavenet_tail_fwd(const void* z, int64_t bs_z, int ld_z, const void* x, int64_t bs_x, int ld_x, const void* w_packed,
+                         const float* bias, void* y, int64_t bs_y, int ld_y, const int* lens, int batch, int t, int hidden,
+                         smt_stream_t stream);
+
 /* ------------------------------------------------------------- spectral ---- */
 /* Windowed STFT magnitude (STFT.forward, datasets/transforms.py:108-123): reflect padding
  * (n_fft - hop)/2, frame every `hop`, window[n_fft] (Hann centre-padded), bins 0..n_fft/2.

@@ -2,8 +2,9 @@
 
 Each stage owns a ``blocks`` ModuleList with the reference's element order so the
 state-dict keys ``...level_blocks.N.blocks.I.*`` line up:
-  encoder:  [strided conv k=2s, GatedHiFi] * down_t, conv k3        (conv.py:38-84)
-  decoder:  conv k3, [GatedHiFi, transposed conv k=2s] * down_t     (conv.py:87-143)
+  encoder:  [strided conv k=2s, Block] * down_t, conv k3        (conv.py:38-84)
+  decoder:  conv k3, [Block, transposed conv k=2s] * down_t     (conv.py:87-143)
+Block = get_block(block_type): GatedHiFiBlock or WaveNetBlock.
 Row masks are prefix masks, carried as per-item lengths: a stride-s conv maps
 L -> ceil(L/s) (``mask[:, :, ::s]``, conv.py:9) and a transposed conv L -> L*s
 (``repeat_interleave``, conv.py:17).
@@ -12,14 +13,16 @@ import torch
 import torch.nn as nn
 
 from smt_amd import convops, packing
-from models.vqvae.resnet import ConvParams, GatedHiFiBlock
+from models.vqvae.resnet import ConvParams, GatedHiFiBlock, WaveNetBlock
 
 
 def get_block(block_type):
     if block_type == "gated_hifi":
         return GatedHiFiBlock
-    raise ValueError(f"block_type={block_type!r}: only 'gated_hifi' has a native implementation "
-                     "(the one configs/models/vqvae.yaml uses)")
+    if block_type == "wavenet":
+        return WaveNetBlock
+    raise ValueError(f"block_type={block_type!r}: 'gated_hifi' and 'wavenet' have native implementations; 'base' and 'hifi' "
+                     "(the reference's ResLayer blocks) are not built")
 
 
 class EncoderConvBlock(nn.Module):
@@ -31,7 +34,7 @@ class EncoderConvBlock(nn.Module):
         blocks = []
         for i in range(down_t):
             blocks.append(ConvParams(input_emb_width if i == 0 else width, width, 2 * stride_t))
-            blocks.append(Block(width, depth, site_base=site_base + i * 2 * depth, **block_kwargs))
+            blocks.append(Block(width, depth, m_conv=m_conv, site_base=site_base + i * 2 * depth, **block_kwargs))
         if down_t > 0:
             blocks.append(ConvParams(width, output_emb_width, 3))
         self.blocks = nn.ModuleList(blocks)
@@ -66,7 +69,7 @@ class DecoderConvBlock(nn.Module):
         if down_t > 0:
             blocks.append(ConvParams(output_emb_width, width, 3))
             for i in range(down_t):
-                blocks.append(Block(width, depth, site_base=site_base + i * 2 * depth, **block_kwargs))
+                blocks.append(Block(width, depth, m_conv=m_conv, site_base=site_base + i * 2 * depth, **block_kwargs))
                 blocks.append(ConvParams(width, input_emb_width if i == down_t - 1 else width, 2 * stride_t,
                                          transposed=True))
         self.blocks = nn.ModuleList(blocks)

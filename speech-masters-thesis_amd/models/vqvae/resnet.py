@@ -1,10 +1,10 @@
-"""Gated multi-receptive-field residual block of the VQ-VAE encoder / decoder.
+"""Residual blocks of the VQ-VAE encoder / decoder: the gated multi-receptive-field block and the WaveNet stack.
 
-Mirrors the parameter tree of the reference ``GatedHiFiBlock`` (models/vqvae/
-resnet.py:184-241; per branch ``Sequential(Conv1d 1x1, ResLayer)``, resnet.py:16-36)
-so checkpoints interchange, but activations are channels-last and the arithmetic goes
-through ``smt_amd.convops``.  Only ``block_type: gated_hifi`` is implemented natively --
-it is the only one configs/models/vqvae.yaml exercises.
+They mirror the parameter trees of the reference ``GatedHiFiBlock`` (models/vqvae/
+resnet.py:184-241; per branch ``Sequential(Conv1d 1x1, ResLayer)``, resnet.py:16-36) and
+``WaveNetBlock`` (resnet.py:123-181) so checkpoints interchange, but activations are
+channels-last and the arithmetic goes through ``smt_amd.convops``.  ``block_type: gated_hifi``
+and ``wavenet`` are implemented natively; ``base`` and ``hifi`` are not (models/vqvae/conv.py).
 """
 import math
 
@@ -45,6 +45,37 @@ def _numbered(**children):
 
 def mod_cycle(depth, cycle):
     return depth if cycle is None else depth % cycle
+
+
+class WaveNetBlock(nn.Module):
+    """Stack of WaveNet residual layers (reference ``WaveNetBlock``, models/vqvae/resnet.py:123-181), with its parameter tree:
+    ``conv_in`` (1x1, n_in -> H), per layer ``convs.d`` (k = 3, dilated, H -> 2H) and ``gates.d`` (1x1, H -> H), ``conv_out``
+    (1x1, H -> n_in), H = int(m_conv * n_in).  No ReLU and no dropout: the block uses no dropout site, ``drop_seed`` is
+    accepted for the common block interface; ``reverse_dilation``, ``kernel_size_*`` and ``dropout`` are ignored as the
+    reference's ``**kwargs`` ignores them."""
+
+    def __init__(self, n_in, n_depth, m_conv=1.0, dilation_growth_rate=1, dilation_cycle=None, zero_out=True,
+                 res_scale=False, site_base=0, **unused):
+        super().__init__()
+        self.n_in, self.n_depth, self.n_hid = n_in, n_depth, int(m_conv * n_in)
+        self.res_scale = 1.0 if not res_scale else 1.0 / math.sqrt(n_depth)
+        self.dilations = [dilation_growth_rate ** mod_cycle(d, dilation_cycle) for d in range(n_depth)]
+        h = self.n_hid
+        self.conv_in = ConvParams(n_in, h, 1)
+        self.conv_out = ConvParams(h, n_in, 1)
+        self.convs = nn.ModuleList([ConvParams(h, 2 * h, 3) for _ in range(n_depth)])
+        self.gates = nn.ModuleList([ConvParams(h, h, 1, zero=zero_out) for _ in range(n_depth)])
+
+    @packing.forward_scope
+    def forward(self, x, lens, drop_seed=0):
+        """x [B, T, n_in]; lens [B] valid lengths (the block's row mask)."""
+        if self.res_scale != 1.0:
+            raise NotImplementedError("res_scale=True is not used by the reference configs (conv.py:55)")
+        x = convops.conv1d(x, self.conv_in.weight, self.conv_in.bias, lens=lens)
+        for dil, conv, gate in zip(self.dilations, self.convs, self.gates):
+            z = convops.conv1d(x, conv.weight, conv.bias, padding=dil, dilation=dil, lens=lens)
+            x = convops.wavenet_tail(z, x, gate.weight, gate.bias, lens)
+        return convops.conv1d(x, self.conv_out.weight, self.conv_out.bias, lens=lens)
 
 
 class GatedHiFiBlock(nn.Module):

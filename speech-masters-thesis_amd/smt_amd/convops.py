@@ -8,6 +8,8 @@ and backward are libsmt_hip.so launches on torch's current stream.
     conv_transpose1d  the same kernel, one launch per output phase
     conv_in / conv_out  the C_in = 1 and C_out = 1 ends of the network (HBM-bound kernels)
     gate_mix          sum_d tanh(t_d) * softmax_d(s_d)
+    wavenet_gate      tanh(t) * sigmoid(s), the WaveNet gate
+    wavenet_tail      x + bias + W_g . wavenet_gate(z): one WaveNet layer's gate, 1x1 and residual (fused in bf16)
 
 Data gradients are the same GEMM kernel on repacked weights; weight / bias gradients use the
 transposed-fragment kernel (conv_wgrad.hip) with a fixed-order reduction.  The operand-layout copies of the
@@ -125,6 +127,8 @@ def _phases(kernel, stride, padding):
 
 _K3GATE = not bool(int(os.environ.get("SMT_NO_K3GATE", "0")))       # A/B switches for tests and profiles
 _RESAMPLE = not bool(int(os.environ.get("SMT_NO_RESAMPLE", "0")))
+_WN_TAIL = not bool(int(os.environ.get("SMT_NO_WN_TAIL", "0")))     # the fused WaveNet layer tail (smt_wavenet_tail_fwd)
+_WN_TAIL_WIDTHS = (64, 128)     # widths at which the fused tail is the default: where it measured faster
 
 
 # ---- operand layouts: which element of a torch-layout weight goes where (packed and kept current by smt_amd.packing) ----
@@ -541,6 +545,103 @@ class _GateMix(torch.autograd.Function):
 def gate_mix(z, depth: int):
     """sum_d tanh(t_d) * softmax_d(s_d); z = [.., d*2w + (0..w-1)] = t_d, [.., d*2w + (w..2w-1)] = s_d."""
     return _GateMix.apply(z, depth)
+
+
+def _wavenet_gate_fwd(z, a, lens32):
+    (pz, bsz, ldz), (pa, bsa, lda) = _geom(z), _geom(a)
+    b, t, h = a.shape
+    with profiler.region("wavenet_gate_fwd", nbytes=float(b) * t * 3 * h * z.element_size(), bound="hbm"):
+        N.check(N.lib().smt_wavenet_gate_fwd(pz, bsz, ldz, pa, bsa, lda, _p(lens32), b, t, h, _DT[z.dtype], N.stream_ptr()),
+                "smt_wavenet_gate_fwd")
+
+
+def _wavenet_gate_bwd(z, da, dz, lens32):
+    (pz, bsz, ldz), (pda, bsda, ldda), (pdz, bsdz, lddz) = _geom(z), _geom(da), _geom(dz)
+    b, t, h = da.shape
+    with profiler.region("wavenet_gate_bwd", nbytes=float(b) * t * 5 * h * z.element_size(), bound="hbm"):
+        N.check(N.lib().smt_wavenet_gate_bwd(pz, bsz, ldz, pda, bsda, ldda, pdz, bsdz, lddz, _p(lens32), b, t, h, _DT[z.dtype],
+                                             N.stream_ptr()), "smt_wavenet_gate_bwd")
+
+
+class _WaveNetGate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, lens):
+        b, t, c = z.shape
+        lens32 = _i32(lens)
+        a = torch.empty(b, t, c // 2, dtype=z.dtype, device=z.device)
+        _wavenet_gate_fwd(z, a, lens32)
+        ctx.save_for_backward(z, lens32 if lens32 is not None else torch.empty(0))
+        ctx.has_lens = lens is not None
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        z, lens32 = ctx.saved_tensors
+        dz = torch.empty_like(z)
+        _wavenet_gate_bwd(z, da.contiguous(), dz, lens32 if ctx.has_lens else None)
+        return dz, None
+
+
+def wavenet_gate(z, lens=None):
+    """tanh(z[..., :H]) * sigmoid(z[..., H:]) on rows t < lens[b], zero on the others (which are not read); z is [B, T, 2H]."""
+    return _WaveNetGate.apply(z, lens)
+
+
+def _wn_tail_ok(dtype, hidden):
+    return _WN_TAIL and dtype == torch.bfloat16 and hidden in _WN_TAIL_WIDTHS
+
+
+class _WaveNetTail(torch.autograd.Function):
+    """The fused tail: z is the only activation kept (the gated a is recomputed in backward)."""
+
+    @staticmethod
+    def forward(ctx, z, x, weight, bias, lens):
+        b, t, h = x.shape
+        lens32 = _i32(lens)
+        y = torch.empty(b, t, h, dtype=x.dtype, device=x.device)
+        (pz, bsz, ldz), (px, bsx, ldx_), (py, bsy, ldy) = _geom(z), _geom(x), _geom(y)
+        rows = float(b) * t
+        with profiler.region("wavenet_tail", flops=2.0 * rows * h * h, nbytes=rows * 4 * h * 2 + h * h * 2, bound="hbm",
+                             dtype="bf16"):
+            N.check(N.lib().smt_wavenet_tail_fwd(pz, bsz, ldz, px, bsx, ldx_, _p(_pack_fwd(weight, x.dtype)), _p(bias), py, bsy,
+                                                 ldy, _p(lens32), b, t, h, N.stream_ptr()), "smt_wavenet_tail_fwd")
+        ctx.save_for_backward(z, weight, lens32 if lens32 is not None else torch.empty(0))
+        ctx.cfg = (lens is not None, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, weight, lens32 = ctx.saved_tensors
+        has_lens, has_bias = ctx.cfg
+        lens32 = lens32 if has_lens else None
+        b, t, c = z.shape
+        h = c // 2
+        dy = dy.contiguous()
+        a = torch.empty(b, t, h, dtype=z.dtype, device=z.device)          # scratch: recomputed, not kept by forward
+        _wavenet_gate_fwd(z, a, lens32)
+        da = torch.empty_like(a)
+        dw = torch.empty_like(weight)
+        db = torch.empty(h, dtype=torch.float32, device=z.device)
+        if h == 64:       # data, weight and bias gradient of the 64 -> 64 1x1 in one pass over dy
+            _conv_gate_bwd(dy, a, _pack_bwd(weight, z.dtype), da, lens32, dw, db)
+        else:
+            d = _dgrad_stride1(dy, _pack_bwd(weight, z.dtype), da, 1, 1, 0)
+            d.lens_out = _p(lens32)
+            _launch(d, "conv_dgrad", _conv_flops(d), _conv_bytes(d, z.element_size()))
+            _wgrad(_base_desc(a, dy, lens32, h, h, 1, 1, 1, 0, t), dw, h, 1, 1, [0], db)
+        del a
+        dz = torch.empty_like(z)
+        _wavenet_gate_bwd(z, da, dz, lens32)
+        return dz, dy, dw, (db if has_bias else None), None
+
+
+def wavenet_tail(z, x, weight, bias, lens=None):
+    """One WaveNet layer after its dilated conv: x + bias + W_g . (tanh(z_t) * sigmoid(z_s)); z [B, T, 2H], x [B, T, H], ``weight``
+    the 1x1 gate conv in torch's layout [H, H, 1].  In bf16 at the widths of _WN_TAIL_WIDTHS this is one kernel that never
+    stores the gated tensor (rows >= lens[b] of its output are zero); otherwise the gate kernel followed by conv1d."""
+    if _wn_tail_ok(x.dtype, x.shape[2]):
+        return _WaveNetTail.apply(z, x, weight, bias, lens)
+    return conv1d(wavenet_gate(z, lens), weight, bias, lens=lens, residual=x)
 
 
 class _ConvIn(torch.autograd.Function):

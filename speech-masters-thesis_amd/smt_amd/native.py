@@ -66,6 +66,11 @@ _SIGNATURES = {
                                     c_ptr, c_i64, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr]),
     "smt_gate_mix_fwd": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_int, c_int, c_ptr]),
     "smt_gate_mix_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr]),
+    "smt_wavenet_gate_fwd": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
+    "smt_wavenet_gate_bwd": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_int, c_int, c_int,
+                                     c_int, c_ptr]),
+    "smt_wavenet_tail_fwd": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_int,
+                                     c_int, c_int, c_ptr]),
     "smt_conv_in_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                 c_int, c_ptr]),
     "smt_conv_in_wgrad_workspace_bytes": (c_size, [c_int, c_int, c_int]),
