@@ -491,9 +491,7 @@ __global__ __launch_bounds__(DMA_NT) void conv1x1_dma_kernel(ConvArgs p, const _
   bf16x8 wfrag[KC / 16];
   {
     const int co = n0 + wn * 32 + r;
-    const unsigned char* wrow = reinterpret_cast<const unsigned char*>(p.w) + (size_t)co * ROWB;
-#pragma unroll
-    for (int kk = 0; kk < KC / 16; ++kk) wfrag[kk] = *reinterpret_cast<const bf16x8*>(wrow + (((2 * kk + hh) ^ (co & 15)) << 4));
+    load_wfrags(wfrag, reinterpret_cast<const unsigned char*>(p.w) + (size_t)co * ROWB, hh, co & 15);
   }
   const float bval = p.bias ? p.bias[n0 + wn * 32 + r] : 0.f;
   const int cv0 = tid % CV, row0 = tid / CV;
@@ -634,12 +632,8 @@ __global__ __launch_bounds__(FO_NT) void conv1x1_fold_kernel(ConvArgs p, const _
   bf16x8 wfrag[8], w2frag[4];
   {
     const int co = n0 + wn * 32 + r;
-    const unsigned char* wrow = reinterpret_cast<const unsigned char*>(p.w) + (size_t)co * 256;
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) wfrag[kk] = *reinterpret_cast<const bf16x8*>(wrow + (((2 * kk + hh) ^ (co & 15)) << 4));
-    const unsigned char* w2row = reinterpret_cast<const unsigned char*>(p.w2) + (size_t)co * 128;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) w2frag[kk] = *reinterpret_cast<const bf16x8*>(w2row + ((2 * kk + hh) << 4));
+    load_wfrags(wfrag, reinterpret_cast<const unsigned char*>(p.w) + (size_t)co * 256, hh, co & 15);
+    load_wfrags(w2frag, reinterpret_cast<const unsigned char*>(p.w2) + (size_t)co * 128, hh);
   }
   // accumulator element 4g + k of a lane = output channel col0 + 8g + k
   const int col0 = n0 + wn * 32 + 4 * hh;
@@ -663,15 +657,14 @@ __global__ __launch_bounds__(FO_NT) void conv1x1_fold_kernel(ConvArgs p, const _
       const int g = wave + (FO_NT / 64) * q;
       const int row = 4 * g + (lane >> 4), pos = lane & 15;
       const int t = t0 + row;
-      lds_dma16(t < len_in ? ug + (long long)t * p.ldx + ((pos ^ (row & 15)) * 8) : zero_page + pos * 8, base + g * 1024);
+      lds_dma16(t < len_in ? ug + (long long)t * p.ldx + ((pos ^ swz256_row(row)) * 8) : zero_page + pos * 8, base + g * 1024);
     }
 #pragma unroll
     for (int q = 0; q < (FO_ROWS / 8) / (FO_NT / 64); ++q) {     // x2: 8 rows x 8 chunks per instruction
       const int g = wave + (FO_NT / 64) * q;
       const int row = 8 * g + (lane >> 3), pos = lane & 7;
       const int t = t0 + row;
-      // 128-byte rows: two rows share a 256-byte bank window, chunk c of row n sits at c ^ ((n >> 1) & 7)
-      lds_dma16(t < len_in2 ? xg + (long long)t * p.ldx2 + ((pos ^ ((row >> 1) & 7)) * 8) : zero_page + pos * 8,
+      lds_dma16(t < len_in2 ? xg + (long long)t * p.ldx2 + ((pos ^ swz128_row(row)) * 8) : zero_page + pos * 8,
                 base + FO_U + g * 1024);
     }
   };
@@ -697,7 +690,7 @@ __global__ __launch_bounds__(FO_NT) void conv1x1_fold_kernel(ConvArgs p, const _
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int row = wm * 64 + 32 * i + r;
-        bf16x8 bv = *reinterpret_cast<const bf16x8*>(ut + row * 256 + (((2 * kk + hh) ^ (row & 15)) << 4));
+        bf16x8 bv = lds_row_frag(ut, row, 256, kk, hh, swz256_row(row));
         acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[kk], bv, acc[i], 0, 0, 0);
       }
 #pragma unroll
@@ -705,7 +698,7 @@ __global__ __launch_bounds__(FO_NT) void conv1x1_fold_kernel(ConvArgs p, const _
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int row = wm * 64 + 32 * i + r;
-        bf16x8 bv = *reinterpret_cast<const bf16x8*>(xt + row * 128 + (((2 * kk + hh) ^ ((row >> 1) & 7)) << 4));
+        bf16x8 bv = lds_row_frag(xt, row, 128, kk, hh, swz128_row(row));
         acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2frag[kk], bv, acc[i], 0, 0, 0);
       }
 
@@ -737,13 +730,10 @@ __global__ __launch_bounds__(FO_NT) void conv1x1_fold_kernel(ConvArgs p, const _
 
 static int launch_conv1x1_fold(ConvArgs p, const void* zero_page, hipStream_t stream) {
   p.tiles_per_batch = (p.Tout + FO_ROWS - 1) / FO_ROWS;
-  const int ntiles = p.tiles_per_batch * p.B;
-  int nwg = std::min(256, std::max(8, (ntiles + 1) / 2));     // one workgroup per CU (96 KiB of LDS)
-  nwg = (nwg + 7) / 8 * 8;
-  const int tpw = (ntiles + nwg - 1) / nwg;
-  dim3 grid((unsigned)nwg, (unsigned)(p.Cout / 128));
+  const StreamGrid sg = plan_stream((long long)p.tiles_per_batch * p.B, 256, 2);     // one workgroup per CU (96 KiB of LDS)
+  dim3 grid((unsigned)sg.nwg, (unsigned)(p.Cout / 128));
   (void)hipFuncSetAttribute((const void*)conv1x1_fold_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  conv1x1_fold_kernel<<<grid, FO_NT, 2 * FO_STAGE, stream>>>(p, (const __bf16*)zero_page, tpw);
+  conv1x1_fold_kernel<<<grid, FO_NT, 2 * FO_STAGE, stream>>>(p, (const __bf16*)zero_page, sg.tiles_per_wg);
   SMT_CHECK_LAUNCH("conv1x1_fold");
   return 0;
 }
@@ -785,16 +775,12 @@ __global__ __launch_bounds__(K1_NT) void conv_k1act_kernel(ConvArgs p, const __b
     cs[c] = col0 - site * p.site_width;
   }
 
-  // Round 3: the tile loop owns its vector-memory waits (conv_common.h, conv_k3gate.hip): untracked x tiles through a V#,
-  // scalar lens loads, stores through a V# (always issued), and ONE counted wait per tile -- vmcnt(16 stores) -- so the
-  // 128 KiB a workgroup writes per tile drains under the next tile instead of in front of it.
-  auto decode = [&](int tile, int& b, int& t0) {
-    b = __builtin_amdgcn_readfirstlane(tile / p.tiles_per_batch);
-    t0 = __builtin_amdgcn_readfirstlane((tile - b * p.tiles_per_batch) * K1_ROWS);
-  };
+  // the tile loop of conv_stream.h; the counted wait is vmcnt(16 stores): the 128 KiB a workgroup writes per tile drain
+  // under the next tile instead of in front of it
+  auto decode = [&](int tile, int& b, int& t0) { tile_decode<K1_ROWS>(tile, p.tiles_per_batch, b, t0); };
   const unsigned pitch_x = (unsigned)p.ldx * 2u, pitch_u = (unsigned)p.ldya * 2u;
   const int xrow = 8 * wave + (lane >> 3);                        // group wave + 8 q: rows 8 wave + .. + 64 q, swizzle independent of q
-  const unsigned xoff0 = (unsigned)xrow * pitch_x + (unsigned)(((lane & 7) ^ ((xrow >> 1) & 7)) << 4);
+  const unsigned xoff0 = (unsigned)xrow * pitch_x + (unsigned)(((lane & 7) ^ swz128_row(xrow)) << 4);
   auto stage = [&](int tile, int buf) {
     int b, t0;
     decode(tile, b, t0);
@@ -803,7 +789,6 @@ __global__ __launch_bounds__(K1_NT) void conv_k1act_kernel(ConvArgs p, const __b
     unsigned vo = xoff0 + (unsigned)t0 * pitch_x;
 #pragma unroll
     for (int q = 0; q < (K1_ROWS / 8) / (K1_NT / 64); ++q) {     // 8 rows x 8 chunks per instruction; rows >= len_in read as zero
-      // 128-byte rows: two rows share a 256-byte bank window, chunk c of row n sits at c ^ ((n >> 1) & 7)
       untracked_dma16(rx, vo, smem + (size_t)buf * K1_X + (wave + (K1_NT / 64) * q) * 1024);
       vo += 64u * pitch_x;
     }
@@ -833,7 +818,7 @@ __global__ __launch_bounds__(K1_NT) void conv_k1act_kernel(ConvArgs p, const __b
         for (int e = 0; e < 16; ++e) acc[c][e] = 0.f;
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
-        bf16x8 bv = *reinterpret_cast<const bf16x8*>(xt + row * 128 + (((2 * kk + hh) ^ ((row >> 1) & 7)) << 4));
+        bf16x8 bv = lds_row_frag(xt, row, 128, kk, hh, swz128_row(row));
 #pragma unroll
         for (int c = 0; c < 2; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[c][kk], bv, acc[c], 0, 0, 0);
       }
@@ -879,11 +864,8 @@ static bool conv_k1act_eligible(const smt_conv_desc* d) {
 
 static int launch_conv_k1act(ConvArgs p, const void* zero_page, hipStream_t stream) {
   p.tiles_per_batch = (p.Tout + K1_ROWS - 1) / K1_ROWS;
-  const int ntiles = p.tiles_per_batch * p.B;
-  int nwg = std::min(512, std::max(8, (ntiles + 1) / 2));     // two workgroups per CU (32 KiB of LDS each)
-  nwg = (nwg + 7) / 8 * 8;
-  const int tpw = (ntiles + nwg - 1) / nwg;
-  conv_k1act_kernel<<<nwg, K1_NT, 2 * K1_X, stream>>>(p, (const __bf16*)zero_page, tpw);
+  const StreamGrid sg = plan_stream((long long)p.tiles_per_batch * p.B, 512, 2);     // two workgroups per CU (32 KiB of LDS each)
+  conv_k1act_kernel<<<sg.nwg, K1_NT, 2 * K1_X, stream>>>(p, (const __bf16*)zero_page, sg.tiles_per_wg);
   SMT_CHECK_LAUNCH("conv_k1act");
   return 0;
 }
@@ -906,32 +888,23 @@ __global__ __launch_bounds__(C64_NT) void conv1x1_c64_kernel(ConvArgs p, int til
   const int r = lane & 31, hh = lane >> 5;
   const int ct = wave & 1, rg = wave >> 1;
 
-  const int ntiles = p.tiles_per_batch * p.B;
-  const int nwg = gridDim.x;
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
-  const int tile_begin = wg * tiles_per_wg;
-  const int tile_end = min(ntiles, tile_begin + tiles_per_wg);
-  if (tile_begin >= tile_end) return;
+  int wg, tile_begin, tile_end;
+  if (!wg_tile_run(p.tiles_per_batch * p.B, tiles_per_wg, wg, tile_begin, tile_end)) return;
 
   bf16x8 wfrag[4];
   float bval[16];
   {
     const int co = 32 * ct + r;
-    const unsigned char* wrow = reinterpret_cast<const unsigned char*>(p.w) + (size_t)co * 128;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) wfrag[kk] = *reinterpret_cast<const bf16x8*>(wrow + ((2 * kk + hh) << 4));
+    load_wfrags(wfrag, reinterpret_cast<const unsigned char*>(p.w) + (size_t)co * 128, hh);
     // accumulator element 4g + k of a lane = output channel 32 ct + 4 hh + 8g + k
 #pragma unroll
     for (int e = 0; e < 16; ++e) bval[e] = p.bias ? p.bias[32 * ct + 4 * hh + 8 * (e >> 2) + (e & 3)] : 0.f;
   }
 
-  auto decode = [&](int tile, int& b, int& t0) {
-    b = __builtin_amdgcn_readfirstlane(tile / p.tiles_per_batch);
-    t0 = __builtin_amdgcn_readfirstlane((tile - b * p.tiles_per_batch) * C64_ROWS);
-  };
+  auto decode = [&](int tile, int& b, int& t0) { tile_decode<C64_ROWS>(tile, p.tiles_per_batch, b, t0); };
   const unsigned pitch_x = (unsigned)p.ldx * 2u, pitch_r = (unsigned)p.ldr * 2u, pitch_y = (unsigned)p.ldy * 2u;
   const int srow = 8 * wave + (lane >> 3);                         // group wave + 8 q: rows 8 wave + .. + 64 q
-  const unsigned schunk = (unsigned)(((lane & 7) ^ ((srow >> 1) & 7)) << 4);   // chunk c of row n sits at c ^ ((n >> 1) & 7)
+  const unsigned schunk = (unsigned)(((lane & 7) ^ swz128_row(srow)) << 4);
   auto stage = [&](int tile, int buf) {
     int b, t0;
     decode(tile, b, t0);
@@ -960,13 +933,13 @@ __global__ __launch_bounds__(C64_NT) void conv1x1_c64_kernel(ConvArgs p, int til
     const __amdgpu_buffer_rsrc_t ry = ws_rsrc(p.y, (long long)b * p.y_bs * 2, (unsigned)p.Tout * pitch_y);
     const int len_out = p.lens_out ? scalar_load_i32(p.lens_out + b) : 0x7fffffff;
     const int row = 32 * rg + r;
-    const int swz = (row >> 1) & 7;
+    const int swz = swz128_row(row);
     f32x16 acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-      const bf16x8 bv = *reinterpret_cast<const bf16x8*>(gt + row * 128 + (((2 * kk + hh) ^ swz) << 4));
+      const bf16x8 bv = lds_row_frag(gt, row, 128, kk, hh, swz);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[kk], bv, acc, 0, 0, 0);
     }
     const int t = t0 + row;
@@ -983,6 +956,7 @@ __global__ __launch_bounds__(C64_NT) void conv1x1_c64_kernel(ConvArgs p, int til
       yp[2 * g + 1] = pack_bf16x2(fmaf(__builtin_bit_cast(float, h23 << 16), keep_row, __builtin_bit_cast(float, rv.y << 16)),
                                   fmaf(__builtin_bit_cast(float, h23 & 0xffff0000u), keep_row, __builtin_bit_cast(float, rv.y & 0xffff0000u)));
     }
+    // lane pairing (written out: as a call to pair_up8 this kernel compiles to a different instruction order)
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
@@ -990,11 +964,7 @@ __global__ __launch_bounds__(C64_NT) void conv1x1_c64_kernel(ConvArgs p, int til
         auto sw = __builtin_amdgcn_permlane32_swap(yp[4 * h2 + d], yp[4 * h2 + 2 + d], false, false);
         yp[4 * h2 + d] = sw[0]; yp[4 * h2 + 2 + d] = sw[1];
       }
-    {                                                   // rows >= Tout: out of range, dropped -- but ISSUED
-      const unsigned vo = (unsigned)t * pitch_y + (unsigned)(32 * ct + 8 * hh) * 2u;
-      __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[0], (int)yp[1], (int)yp[2], (int)yp[3]}, ry, (int)vo, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[4], (int)yp[5], (int)yp[6], (int)yp[7]}, ry, (int)(vo + 32u), 0, 0);
-    }
+    store_paired(yp, ry, (unsigned)t * pitch_y + (unsigned)(32 * ct + 8 * hh) * 2u);   // rows >= Tout: dropped -- but ISSUED
     step_end_wait<C64_STORES>();                        // the next tile's DMA is older than this tile's stores
   }
 }
@@ -1008,27 +978,21 @@ static bool conv1x1_c64_eligible(const smt_conv_desc* d) {
 
 static int launch_conv1x1_c64(ConvArgs p, hipStream_t stream) {
   p.tiles_per_batch = (p.Tout + C64_ROWS - 1) / C64_ROWS;
-  const int ntiles = p.tiles_per_batch * p.B;
-  int nwg = std::min(1024, std::max(8, (ntiles + 1) / 2));    // four workgroups per CU (32 KiB of LDS, four waves each)
-  nwg = (nwg + 7) / 8 * 8;
-  const int tpw = (ntiles + nwg - 1) / nwg;
+  const StreamGrid sg = plan_stream((long long)p.tiles_per_batch * p.B, 1024, 2);    // four workgroups per CU (32 KiB of LDS, four waves each)
   (void)hipFuncSetAttribute((const void*)conv1x1_c64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * C64_TILE);
-  conv1x1_c64_kernel<<<nwg, C64_NT, 4 * C64_TILE, stream>>>(p, tpw);
+  conv1x1_c64_kernel<<<sg.nwg, C64_NT, 4 * C64_TILE, stream>>>(p, sg.tiles_per_wg);
   SMT_CHECK_LAUNCH("conv1x1_c64");
   return 0;
 }
 
 static int launch_conv1x1_dma(ConvArgs p, const void* zero_page, hipStream_t stream) {
   p.tiles_per_batch = (p.Tout + DMA_BM - 1) / DMA_BM;
-  const int ntiles = p.tiles_per_batch * p.B;
   // two workgroups per CU (70 KB of LDS each); at least 2 tiles per workgroup so that the pipeline pays
-  int nwg = std::min(512, std::max(8, (ntiles + 1) / 2));
-  nwg = (nwg + 7) / 8 * 8;
-  const int tpw = (ntiles + nwg - 1) / nwg;
-  dim3 grid((unsigned)nwg, (unsigned)(p.Cout / DMA_BN));
+  const StreamGrid sg = plan_stream((long long)p.tiles_per_batch * p.B, 512, 2);
+  dim3 grid((unsigned)sg.nwg, (unsigned)(p.Cout / DMA_BN));
   const size_t lds = 2 * P1_BUF;
   (void)hipFuncSetAttribute((const void*)conv1x1_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  conv1x1_dma_kernel<<<grid, DMA_NT, lds, stream>>>(p, (const __bf16*)zero_page, tpw);
+  conv1x1_dma_kernel<<<grid, DMA_NT, lds, stream>>>(p, (const __bf16*)zero_page, sg.tiles_per_wg);
   SMT_CHECK_LAUNCH("conv1x1_dma");
   return 0;
 }

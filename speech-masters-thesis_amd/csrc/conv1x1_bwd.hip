@@ -20,10 +20,7 @@
 // 4 consecutive rows are 64 B apart (transposed fragments, 4 rows x 32 B per 16-lane group).
 // Each workgroup leaves its partial dW / db in a slab; conv_wgrad_reduce_kernel sums the slabs in fixed order.
 //
-// Round 3: the tile loop owns its vector-memory waits (see conv_k3gate.hip): tiles and stores go through range-checked
-// V#s (always issued), lens[b] is a scalar load, and ONE counted wait per tile -- vmcnt(4 stores) -- leaves the dx stores
-// draining under the next tile while the prefetched tile is known to have landed.  Before, the vector load of lens[b]
-// made the compiler wait vmcnt(0) right after the prefetch was issued: every tile waited for its own prefetch.
+// The tile loop follows conv_stream.h; the counted wait at the end of a tile is vmcnt(4 dx stores).
 #include <algorithm>
 
 #include "conv_common.h"
@@ -42,16 +39,6 @@ struct Bwd1x1Args {
 constexpr int FB_ROWS = 128, FB_C = 128, FB_ROWB = FB_C * 2, FB_TILE = FB_ROWS * FB_ROWB, FB_NT = 512;
 constexpr int FB_NDX = 2 * 2;      // dx stores per wave and tile: two 32-row groups x 2
 
-__device__ __forceinline__ int fb_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-
-__device__ __forceinline__ bf16x8 fb_tr2(const unsigned char* pa, const unsigned char* pb) {
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)pa);
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)pb);
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
 __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
   typedef __bf16 T;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];   // 2 x [dy tile | u tile]
@@ -60,19 +47,15 @@ __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
   const int r = lane & 31, hh = lane >> 5;
 
   const int ntiles = p.tiles_per_batch * p.B;
-  const int nwg = gridDim.x;
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
-  const int tile_begin = min(ntiles, wg * p.tiles_per_wg);
-  const int tile_end = min(ntiles, tile_begin + p.tiles_per_wg);
+  // indices only, no return: a workgroup without tiles still writes its zero partial slab, which the reducer reads
+  const TileRun run = tile_run(gridDim.x, blockIdx.x, ntiles, p.tiles_per_wg, /*clamp_begin=*/true);
+  const int wg = run.wg, tile_begin = run.begin, tile_end = run.end;
 
   // W^T slice for the data gradient: operand A rows = ci (packed "bwd" layout [ci][co], chunk c of row ci at c ^ (ci & 15))
   bf16x8 wfrag[FB_C / 16];
   {
     const int ci = wn * 32 + r;
-    const unsigned char* wrow = reinterpret_cast<const unsigned char*>(p.w) + (size_t)ci * FB_ROWB;
-#pragma unroll
-    for (int kk = 0; kk < FB_C / 16; ++kk)
-      wfrag[kk] = *reinterpret_cast<const bf16x8*>(wrow + (((2 * kk + hh) ^ (ci & 15)) << 4));
+    load_wfrags(wfrag, reinterpret_cast<const unsigned char*>(p.w) + (size_t)ci * FB_ROWB, hh, ci & 15);
   }
 
   // bias gradient: a dy^T fragment is 8 rows of ONE output channel per lane, so db is a running sum per lane; the four waves
@@ -86,14 +69,11 @@ __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) accw[j][e] = 0.f;
 
-  auto decode = [&](int tile, int& b, int& t0) {           // scalars: the V#s below must live in SGPRs
-    b = __builtin_amdgcn_readfirstlane(tile / p.tiles_per_batch);
-    t0 = __builtin_amdgcn_readfirstlane((tile - b * p.tiles_per_batch) * FB_ROWS);
-  };
+  auto decode = [&](int tile, int& b, int& t0) { tile_decode<FB_ROWS>(tile, p.tiles_per_batch, b, t0); };
   const unsigned pitch_dy = (unsigned)p.lddy * 2u, pitch_u = (unsigned)p.ldu * 2u, pitch_dx = (unsigned)p.lddx * 2u;
-  // group g = wave + 8 q covers rows 4 g + (lane >> 4) = 4 wave + (lane >> 4) + 32 q: fb_swz(row) does not depend on q
+  // group g = wave + 8 q covers rows 4 g + (lane >> 4) = 4 wave + (lane >> 4) + 32 q: swz256_tr(row) does not depend on q
   const int srow = 4 * wave + (lane >> 4);
-  const unsigned schunk = (unsigned)(((lane & 15) ^ fb_swz(srow)) << 4);
+  const unsigned schunk = (unsigned)(((lane & 15) ^ swz256_tr(srow)) << 4);
   auto stage = [&](int tile, int buf) {
     int b, t0;
     decode(tile, b, t0);
@@ -114,11 +94,11 @@ __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
   const int ra = 8 * thh + tq, rb = ra + 4;
   const int col_a = wm * 64 + 16 * (tg & 1) + 4 * tp;          // dy^T fragment of co tile j: + 32 j  (byte offset ^ 64)
   const int col_b = wn * 32 + 16 * (tg & 1) + 4 * tp;          // u fragment
-  const int offa0 = ra * FB_ROWB + (((col_a >> 3) ^ fb_swz(ra)) << 4) + (col_a & 7) * 2;
-  const int offa1 = rb * FB_ROWB + (((col_a >> 3) ^ fb_swz(rb)) << 4) + (col_a & 7) * 2;
-  const int offb0 = ra * FB_ROWB + (((col_b >> 3) ^ fb_swz(ra)) << 4) + (col_b & 7) * 2;
-  const int offb1 = rb * FB_ROWB + (((col_b >> 3) ^ fb_swz(rb)) << 4) + (col_b & 7) * 2;
-  const int swz_r = fb_swz(r);                                   // rows 64 wm + 32 i + r share it
+  const int offa0 = ra * FB_ROWB + (((col_a >> 3) ^ swz256_tr(ra)) << 4) + (col_a & 7) * 2;
+  const int offa1 = rb * FB_ROWB + (((col_a >> 3) ^ swz256_tr(rb)) << 4) + (col_a & 7) * 2;
+  const int offb0 = ra * FB_ROWB + (((col_b >> 3) ^ swz256_tr(ra)) << 4) + (col_b & 7) * 2;
+  const int offb1 = rb * FB_ROWB + (((col_b >> 3) ^ swz256_tr(rb)) << 4) + (col_b & 7) * 2;
+  const int swz_r = swz256_tr(r);                                   // rows 64 wm + 32 i + r share it
 
   if (tile_begin < tile_end) stage(tile_begin, 0);
   vm_wait<0>();                                         // the first tile (and the weights); later tiles: counted wait at the END
@@ -148,7 +128,7 @@ __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int row = wm * 64 + 32 * i + r;
-          bf16x8 bv = *reinterpret_cast<const bf16x8*>(dyt + row * FB_ROWB + (((2 * kk + hh) ^ swz_r) << 4));
+          bf16x8 bv = lds_row_frag(dyt, row, FB_ROWB, kk, hh, swz_r);
           accd[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[kk], bv, accd[i], 0, 0, 0);
         }
       }
@@ -175,6 +155,7 @@ __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
             yp[2 * g + 1] = pack_bf16x2(o[2], o[3]);
           }
           // lanes r / r + 32 hold channels {0-3, 8-11, ..} / {4-7, 12-15, ..} of one row -> 16-byte pieces
+          // (written out: as a call to pair_up8 this kernel compiles to a different instruction order)
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
@@ -182,11 +163,8 @@ __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
               auto sw = __builtin_amdgcn_permlane32_swap(yp[4 * h2 + d], yp[4 * h2 + 2 + d], false, false);
               yp[4 * h2 + d] = sw[0]; yp[4 * h2 + 2 + d] = sw[1];
             }
-          {                                               // rows >= T: out of range, dropped -- but ISSUED (the wait below counts them)
-            const unsigned vo = (unsigned)t * pitch_dx + (unsigned)(wn * 32 + 8 * hh) * 2u;
-            __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[0], (int)yp[1], (int)yp[2], (int)yp[3]}, rdx, (int)vo, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[4], (int)yp[5], (int)yp[6], (int)yp[7]}, rdx, (int)(vo + 32u), 0, 0);
-          }
+          // rows >= T: out of range, dropped -- but ISSUED (the wait below counts them)
+          store_paired(yp, rdx, (unsigned)t * pitch_dx + (unsigned)(wn * 32 + 8 * hh) * 2u);
         }
       }
 
@@ -196,10 +174,10 @@ __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
 #pragma unroll
       for (int k0 = 0; k0 < FB_ROWS / 16; ++k0) {
         const int ko = k0 * 16 * FB_ROWB;
-        const bf16x8 bfr = fb_tr2(ut + offb0 + ko, ut + offb1 + ko);
+        const bf16x8 bfr = lds_tr2(ut + offb0 + ko, ut + offb1 + ko);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const bf16x8 afr = fb_tr2(dyt + ((offa0 + ko) ^ (64 * j)), dyt + ((offa1 + ko) ^ (64 * j)));
+          const bf16x8 afr = lds_tr2(dyt + ((offa0 + ko) ^ (64 * j)), dyt + ((offa1 + ko) ^ (64 * j)));
           accw[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr, bfr, accw[j], 0, 0, 0);
           if (p.with_bias && (k0 & 3) == wn) {
             typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -234,11 +212,8 @@ __global__ __launch_bounds__(FB_NT) void conv1x1_bwd_kernel(Bwd1x1Args p) {
   }
 }
 
-static int bwd1x1_nwg(const smt_conv_desc* d) {
-  const long long ntiles = (long long)((d->t_out + FB_ROWS - 1) / FB_ROWS) * d->batch;
-  // one workgroup per CU (128 KiB of LDS); at least two tiles per workgroup, whole XCD octets
-  long long nwg = std::min<long long>(256, std::max<long long>(8, (ntiles + fused_min_tpw() - 1) / fused_min_tpw()));
-  return (int)((nwg + 7) / 8 * 8);
+static StreamGrid bwd1x1_grid(const smt_conv_desc* d) {   // one workgroup per CU (128 KiB of LDS)
+  return plan_stream((long long)((d->t_out + FB_ROWS - 1) / FB_ROWS) * d->batch, 256, fused_min_tpw());
 }
 
 }  // namespace smt
@@ -254,7 +229,7 @@ static bool bwd1x1_ok(const smt_conv_desc* d) {
 
 extern "C" size_t smt_conv1x1_bwd_workspace_bytes(const smt_conv_desc* d) {
   if (!d) return 0;
-  return (size_t)bwd1x1_nwg(d) * 2 * 2 * 64 * FB_C * sizeof(float);
+  return (size_t)bwd1x1_grid(d).nwg * 2 * 2 * 64 * FB_C * sizeof(float);
 }
 
 extern "C" int smt_conv1x1_bwd(const smt_conv_desc* d, float* dweight, int64_t stride_out, int64_t stride_in,
@@ -266,7 +241,8 @@ extern "C" int smt_conv1x1_bwd(const smt_conv_desc* d, float* dweight, int64_t s
                 "zero_page, act_grad set, no bias/res/act_out/lens_in)");
   SMT_CHECK_ARG(d->ld_x % 8 == 0 && d->ld_y % 8 == 0 && d->ld_act % 8 == 0, "smt_conv1x1_bwd: row pitches must keep 16-byte alignment");
   SMT_CHECK_ARG(workspace_bytes >= smt_conv1x1_bwd_workspace_bytes(d), "smt_conv1x1_bwd: workspace too small");
-  const int nwg = bwd1x1_nwg(d);
+  const StreamGrid grid = bwd1x1_grid(d);
+  const int nwg = grid.nwg;
   if (d->batch > 0 && d->t_out > 0) {
     Bwd1x1Args a;
     a.dy = d->x; a.u = d->act_grad_src; a.w = d->w; a.dx = d->y; a.slab = (float*)workspace;
@@ -275,8 +251,7 @@ extern "C" int smt_conv1x1_bwd(const smt_conv_desc* d, float* dweight, int64_t s
     a.lddy = d->ld_x; a.ldu = d->ld_act; a.lddx = d->ld_y;
     a.B = d->batch; a.T = d->t_out;
     a.tiles_per_batch = (d->t_out + FB_ROWS - 1) / FB_ROWS;
-    const long long ntiles = (long long)a.tiles_per_batch * d->batch;
-    a.tiles_per_wg = (int)((ntiles + nwg - 1) / nwg);
+    a.tiles_per_wg = grid.tiles_per_wg;
     a.with_bias = dbias ? 1 : 0;
     a.scale = d->drop_scale;
     (void)hipFuncSetAttribute((const void*)conv1x1_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

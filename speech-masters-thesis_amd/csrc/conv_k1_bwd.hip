@@ -18,11 +18,9 @@
 // chunk c of row r at c ^ (((r >> 1) & 3) << 1).
 // Each workgroup leaves its partial dW / db in a slab; conv_wgrad_reduce_kernel sums the slabs in fixed order.
 //
-// Round 3: the tile loop owns its vector-memory waits (see conv_k3gate.hip / conv_common.h).  Vector memory completes in
-// issue order, so everything this tile needs from global memory -- the residual rows -- is issued BEFORE the next tile's
-// prefetch, the prefetch and those loads are untracked (no compiler-placed waits), lens[b] is a scalar load, the two
-// workgroup barriers are raw s_barrier + lgkmcnt(0) (a __syncthreads() also drains vector memory), and the stores stay in
-// flight across the tile boundary: per tile the storing waves wait vmcnt(9) for the residual rows and vmcnt(2) at the end.
+// The tile loop follows conv_stream.h.  Specific here: what this tile needs from global memory -- the residual rows -- is
+// issued BEFORE the next tile's prefetch (untracked loads), there are two workgroup barriers per tile, and per tile the
+// storing waves wait vmcnt(9) for the residual rows and vmcnt(2) at the end.
 #include <algorithm>
 
 #include "conv_common.h"
@@ -41,17 +39,6 @@ constexpr int KB_ROWS = 64, KB_CO = 512, KB_CI = 64, KB_NT = 512;
 constexpr int KB_DH = KB_ROWS * KB_CO * 2, KB_X = KB_ROWS * KB_CI * 2, KB_STAGE = KB_DH + KB_X;   // 64 KiB + 8 KiB
 constexpr int KB_RED = 4 * 32 * 32 * 4;   // partial data-gradient tiles of waves 4..7 (behind the two stages)
 
-__device__ __forceinline__ int kb_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int kb_swz_x(int row) { return ((row >> 1) & 3) << 1; }
-
-__device__ __forceinline__ bf16x8 kb_tr2(const unsigned char* pa, const unsigned char* pb) {
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)pa);
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)pb);
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
 __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
   typedef __bf16 T;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];   // 2 x [dh tile | x tile], then the reduction scratch
@@ -59,10 +46,9 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
   const int r = lane & 31, hh = lane >> 5;
 
   const int ntiles = p.tiles_per_batch * p.B;
-  const int nwg = gridDim.x;
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
-  const int tile_begin = min(ntiles, wg * p.tiles_per_wg);
-  const int tile_end = min(ntiles, tile_begin + p.tiles_per_wg);
+  // indices only, no return: a workgroup without tiles still writes its zero partial slab, which the reducer reads
+  const TileRun run = tile_run(gridDim.x, blockIdx.x, ntiles, p.tiles_per_wg, /*clamp_begin=*/true);
+  const int wg = run.wg, tile_begin = run.begin, tile_end = run.end;
 
   // bias gradient: the dh^T fragment of a lane is 8 rows of ONE output channel, so db is a running sum per lane (round 3;
   // the MFMA against a constant-one operand it replaces held 32 accumulator + 4 operand registers and the kernel spilled:
@@ -77,13 +63,10 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
       for (int e = 0; e < 16; ++e) accw[a][c][e] = 0.f;
   }
 
-  auto decode = [&](int tile, int& b, int& t0) {           // scalars: the V#s below must live in SGPRs
-    b = __builtin_amdgcn_readfirstlane(tile / p.tiles_per_batch);
-    t0 = __builtin_amdgcn_readfirstlane((tile - b * p.tiles_per_batch) * KB_ROWS);
-  };
+  auto decode = [&](int tile, int& b, int& t0) { tile_decode<KB_ROWS>(tile, p.tiles_per_batch, b, t0); };
   const unsigned pitch_dh = (unsigned)p.lddh * 2u, pitch_x = (unsigned)p.ldx * 2u, pitch_dx = (unsigned)p.lddx * 2u;
   const int xrow = 8 * wave + (lane >> 3);
-  const unsigned xoff0 = (unsigned)xrow * pitch_x + (unsigned)(((lane & 7) ^ kb_swz_x(xrow)) << 4);
+  const unsigned xoff0 = (unsigned)xrow * pitch_x + (unsigned)(((lane & 7) ^ swz128_tr(xrow)) << 4);
   constexpr int KB_NDMA = KB_ROWS / (KB_NT / 64) + 1;       // LDS-DMA instructions per wave and tile
   constexpr int KB_NDX = 2;                                 // dx stores per wave and tile (waves 0..3)
   auto stage = [&](int tile, int buf) {
@@ -98,7 +81,7 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
 #pragma unroll                                                    // out of the tile loop they cost eight registers and the kernel spills
     for (int q = 0; q < KB_ROWS / (KB_NT / 64); ++q) {            // dh: one 1 KiB row per instruction (rows >= T read as zero)
       const int row = wave + (KB_NT / 64) * q;
-      untracked_dma16(rdh, (unsigned)(t0 + row) * pitch_dh + (unsigned)((ln ^ kb_swz(row)) << 4), base + row * 1024);
+      untracked_dma16(rdh, (unsigned)(t0 + row) * pitch_dh + (unsigned)((ln ^ swz256_tr(row)) << 4), base + row * 1024);
     }
     untracked_dma16(rx, xoff0 + (unsigned)t0 * pitch_x, base + KB_DH + wave * 1024);   // x: 8 rows x 8 chunks (rows >= len: zero)
   };
@@ -108,10 +91,10 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
   const int ra = 8 * thh + tq, rb = ra + 4;
   const int col_a = wave * 64 + 16 * (tg & 1) + 4 * tp;           // dh^T fragment of co tile a: + 32 a (chunk + 4: bit 2 is free)
   const int col_b = 16 * (tg & 1) + 4 * tp;                       // x fragment of ci tile c: + 32 c   (chunk + 4: bit 2 is free)
-  const int offa0 = ra * 1024 + (((col_a >> 3) ^ kb_swz(ra)) << 4) + (col_a & 7) * 2;
-  const int offa1 = rb * 1024 + (((col_a >> 3) ^ kb_swz(rb)) << 4) + (col_a & 7) * 2;
-  const int offb0 = KB_DH + ra * 128 + (((col_b >> 3) ^ kb_swz_x(ra)) << 4) + (col_b & 7) * 2;
-  const int offb1 = KB_DH + rb * 128 + (((col_b >> 3) ^ kb_swz_x(rb)) << 4) + (col_b & 7) * 2;
+  const int offa0 = ra * 1024 + (((col_a >> 3) ^ swz256_tr(ra)) << 4) + (col_a & 7) * 2;
+  const int offa1 = rb * 1024 + (((col_a >> 3) ^ swz256_tr(rb)) << 4) + (col_a & 7) * 2;
+  const int offb0 = KB_DH + ra * 128 + (((col_b >> 3) ^ swz128_tr(ra)) << 4) + (col_b & 7) * 2;
+  const int offb1 = KB_DH + rb * 128 + (((col_b >> 3) ^ swz128_tr(rb)) << 4) + (col_b & 7) * 2;
 
   // data-gradient tile of waves w and w + 4: rows 32 di.., input channels 32 dc..; wave w + 4 takes the upper half of
   // the contraction (output channels 256..511).  W^T fragments (packed [ci][co], plain) live in registers.
@@ -144,10 +127,10 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
       f32x16 accd;
 #pragma unroll
       for (int e = 0; e < 16; ++e) accd[e] = 0.f;
-      const int swz_r = kb_swz(row);
+      const int swz_r = swz256_tr(row);
 #pragma unroll
       for (int kk = 0; kk < KB_CO / 32; ++kk) {
-        const bf16x8 bv = *reinterpret_cast<const bf16x8*>(base + row * 1024 + (((2 * (kk + 16 * kh) + hh) ^ swz_r) << 4));
+        const bf16x8 bv = lds_row_frag(base, row, 1024, kk + 16 * kh, hh, swz_r);
         accd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[kk], bv, accd, 0, 0, 0);
       }
       // residual rows of THIS tile (waves 0..3: channels 32 dc + 8 g + 4 hh + 0..3 of row 32 di + r), THEN the prefetch:
@@ -187,19 +170,9 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
           yp[2 * g] = pack_bf16x2(o[0], o[1]);
           yp[2 * g + 1] = pack_bf16x2(o[2], o[3]);
         }
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-          for (int d = 0; d < 2; ++d) {
-            auto sw = __builtin_amdgcn_permlane32_swap(yp[4 * h2 + d], yp[4 * h2 + 2 + d], false, false);
-            yp[4 * h2 + d] = sw[0]; yp[4 * h2 + 2 + d] = sw[1];
-          }
-        {                                               // rows >= T: out of range, dropped -- but ISSUED
-          const __amdgpu_buffer_rsrc_t rdx = ws_rsrc(p.dx, (long long)b * p.dx_bs * 2, (unsigned)p.T * pitch_dx);
-          const unsigned vo = (unsigned)t * pitch_dx + (unsigned)(32 * dc + 8 * hh) * 2u;
-          __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[0], (int)yp[1], (int)yp[2], (int)yp[3]}, rdx, (int)vo, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[4], (int)yp[5], (int)yp[6], (int)yp[7]}, rdx, (int)(vo + 32u), 0, 0);
-        }
+        pair_up8(yp);
+        const __amdgpu_buffer_rsrc_t rdx = ws_rsrc(p.dx, (long long)b * p.dx_bs * 2, (unsigned)p.T * pitch_dx);
+        store_paired(yp, rdx, (unsigned)t * pitch_dx + (unsigned)(32 * dc + 8 * hh) * 2u);   // rows >= T: dropped -- but ISSUED
       }
     }
 
@@ -209,10 +182,10 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
       bf16x8 bfr[2];
 #pragma unroll
       for (int c = 0; c < 2; ++c)
-        bfr[c] = kb_tr2(base + ((offb0 + k0 * 16 * 128) ^ (64 * c)), base + ((offb1 + k0 * 16 * 128) ^ (64 * c)));
+        bfr[c] = lds_tr2(base + ((offb0 + k0 * 16 * 128) ^ (64 * c)), base + ((offb1 + k0 * 16 * 128) ^ (64 * c)));
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
-        const bf16x8 afr = kb_tr2(base + ((offa0 + k0 * 16 * 1024) ^ (64 * a)), base + ((offa1 + k0 * 16 * 1024) ^ (64 * a)));
+        const bf16x8 afr = lds_tr2(base + ((offa0 + k0 * 16 * 1024) ^ (64 * a)), base + ((offa1 + k0 * 16 * 1024) ^ (64 * a)));
 #pragma unroll
         for (int c = 0; c < 2; ++c) accw[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr, bfr[c], accw[a][c], 0, 0, 0);
         if (p.with_bias) {
@@ -250,10 +223,8 @@ __global__ __launch_bounds__(KB_NT) void conv_k1_bwd_kernel(K1BwdArgs p) {
   }
 }
 
-static int k1_bwd_nwg(int batch, int t) {
-  const long long ntiles = (long long)((t + KB_ROWS - 1) / KB_ROWS) * batch;
-  long long nwg = std::min<long long>(256, std::max<long long>(8, (ntiles + fused_min_tpw() - 1) / fused_min_tpw()));   // one workgroup per CU (144 KiB of LDS)
-  return (int)((nwg + 7) / 8 * 8);
+static StreamGrid k1_bwd_grid(int batch, int t) {       // one workgroup per CU (144 KiB of LDS)
+  return plan_stream((long long)((t + KB_ROWS - 1) / KB_ROWS) * batch, 256, fused_min_tpw());
 }
 
 }  // namespace smt
@@ -261,7 +232,7 @@ static int k1_bwd_nwg(int batch, int t) {
 using namespace smt;
 
 extern "C" size_t smt_conv_k1_bwd_workspace_bytes(int batch, int t) {
-  return (size_t)k1_bwd_nwg(batch, t) * 8 * 2 * 64 * KB_CI * sizeof(float);
+  return (size_t)k1_bwd_grid(batch, t).nwg * 8 * 2 * 64 * KB_CI * sizeof(float);
 }
 
 extern "C" int smt_conv_k1_bwd(const void* dh, int64_t bs_dh, int ld_dh, const void* x, int64_t bs_x, int ld_x,
@@ -273,7 +244,8 @@ extern "C" int smt_conv_k1_bwd(const void* dh, int64_t bs_dh, int ld_dh, const v
   SMT_CHECK_ARG(dh && x && w_packed_bwd && res && dx && zero_page && dweight && workspace, "smt_conv_k1_bwd: null pointer");
   SMT_CHECK_ARG(ld_dh % 8 == 0 && ld_x % 8 == 0 && ld_res % 4 == 0 && ld_dx % 8 == 0, "smt_conv_k1_bwd: row pitches must keep alignment");
   SMT_CHECK_ARG(workspace_bytes >= smt_conv_k1_bwd_workspace_bytes(batch, t), "smt_conv_k1_bwd: workspace too small");
-  const int nwg = k1_bwd_nwg(batch, t);
+  const StreamGrid grid = k1_bwd_grid(batch, t);
+  const int nwg = grid.nwg;
   if (batch > 0 && t > 0) {
     K1BwdArgs a;
     a.dh = dh; a.x = x; a.w = w_packed_bwd; a.res = res; a.dx = dx; a.slab = (float*)workspace; a.lens = lens;
@@ -281,8 +253,7 @@ extern "C" int smt_conv_k1_bwd(const void* dh, int64_t bs_dh, int ld_dh, const v
     a.lddh = ld_dh; a.ldx = ld_x; a.ldres = ld_res; a.lddx = ld_dx;
     a.B = batch; a.T = t;
     a.tiles_per_batch = (t + KB_ROWS - 1) / KB_ROWS;
-    const long long ntiles = (long long)a.tiles_per_batch * batch;
-    a.tiles_per_wg = (int)((ntiles + nwg - 1) / nwg);
+    a.tiles_per_wg = grid.tiles_per_wg;
     a.with_bias = dbias ? 1 : 0;
     (void)hipFuncSetAttribute((const void*)conv_k1_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     conv_k1_bwd_kernel<<<nwg, KB_NT, 2 * KB_STAGE + KB_RED, stream>>>(a);

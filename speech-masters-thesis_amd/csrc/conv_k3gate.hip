@@ -17,12 +17,10 @@
 // re-read from L2 for every (tile, branch) step; the loads are issued right after the step's MFMAs, so they travel while
 // the epilogue stores z.
 //
-// Round 3: the step loop owns its vector-memory waits.  The first version let the compiler place them, and with LDS-DMA in
-// flight hipcc answers the first use of ANY ordinary load result (the weights, the biases) with s_waitcnt vmcnt(0) -- which
-// also drains the slice prefetched for the NEXT step: every step waited for its own prefetch and the double buffer bought
-// nothing (3.2 TB/s).  Now the weights come through loads the compiler does not track (untracked_load16), the biases sit in
-// LDS, slices and stores go through range-checked V#s (always issued), and ONE counted wait per step -- vmcnt(stores of the
-// last row group) -- lets the z stores drain under the next step while the prefetched slice and weights are known to be in.
+// The loop follows conv_stream.h with a (tile, branch) STEP in the place of a tile.  Specific here: the next branch's
+// weights come through loads the compiler does not track (untracked_load16) and the biases sit in LDS -- left to the
+// compiler, the first use of either drained the slice prefetched for the next step (3.2 TB/s) -- and the counted wait per
+// step is vmcnt(stores of the last row group): 2 z stores, + 1 g store in the gate step.
 #include <algorithm>
 
 #include "conv_common.h"
@@ -44,19 +42,14 @@ constexpr int KG_Z_STORES = 2, KG_G_STORES = 1;             // stores per wave a
 __device__ __forceinline__ float kg_lo(unsigned v) { return __uint_as_float(v << 16); }
 __device__ __forceinline__ float kg_hi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
 
-__global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, const __bf16* __restrict__ zero_page,
-                                                            int tiles_per_wg) {
+__global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, int tiles_per_wg) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];   // [u buf 0 | u buf 1 | x buf 0 | x buf 1]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
   const int r = lane & 31, hh = lane >> 5;
 
-  const int ntiles = p.tiles_per_batch * p.B;
-  const int nwg = gridDim.x;
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
-  const int tile_begin = wg * tiles_per_wg;
-  const int tile_end = min(ntiles, tile_begin + tiles_per_wg);
-  if (tile_begin >= tile_end) return;
+  int wg, tile_begin, tile_end;
+  if (!wg_tile_run(p.tiles_per_batch * p.B, tiles_per_wg, wg, tile_begin, tile_end)) return;
 
   const int co = (r >> 4) * 64 + 16 * wn + (r & 15);       // this lane's weight row within a branch (see header)
   bf16x8 wf[8], w2f[4];
@@ -91,14 +84,9 @@ __global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, const 
   // slices through V#s: rows >= T (u2) / >= len (x) are out of range and read as zero
   const unsigned pitch_u = (unsigned)p.ld_u2 * 2u, pitch_x = (unsigned)p.ld_x * 2u;
   const unsigned pitch_z = (unsigned)p.ld_z * 2u, pitch_g = (unsigned)p.ld_g * 2u;
-  const unsigned uoff0 = (unsigned)(4 * wave + (lane >> 4)) * pitch_u + (unsigned)(((lane & 15) ^ ((4 * wave + (lane >> 4)) & 15)) << 4);
-  const unsigned xoff0 = (unsigned)(8 * wave + (lane >> 3)) * pitch_x + (unsigned)(((lane & 7) ^ (((8 * wave + (lane >> 3)) >> 1) & 7)) << 4);
-  // tile -> (batch item, first row), as SCALARS: the V#s below must live in SGPRs (a divergent-looking descriptor costs a
-  // waterfall loop per DMA instruction, and a vector load of lens[b] would be a tracked load again)
-  auto decode = [&](int tile, int& b, int& t0) {
-    b = __builtin_amdgcn_readfirstlane(tile / p.tiles_per_batch);
-    t0 = __builtin_amdgcn_readfirstlane((tile - b * p.tiles_per_batch) * KG_ROWS);
-  };
+  const unsigned uoff0 = (unsigned)(4 * wave + (lane >> 4)) * pitch_u + (unsigned)(((lane & 15) ^ swz256_row(4 * wave + (lane >> 4))) << 4);
+  const unsigned xoff0 = (unsigned)(8 * wave + (lane >> 3)) * pitch_x + (unsigned)(((lane & 7) ^ swz128_row(8 * wave + (lane >> 3))) << 4);
+  auto decode = [&](int tile, int& b, int& t0) { tile_decode<KG_ROWS>(tile, p.tiles_per_batch, b, t0); };
   auto stage_u = [&](int tile, int d, int buf) {
     int b, t0;
     decode(tile, b, t0);
@@ -159,12 +147,12 @@ __global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, const 
         for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
         for (int kk = 0; kk < 8; ++kk) {
-          const bf16x8 bv = *reinterpret_cast<const bf16x8*>(ut + row * 256 + (((2 * kk + hh) ^ (row & 15)) << 4));
+          const bf16x8 bv = lds_row_frag(ut, row, 256, kk, hh, swz256_row(row));
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kk], bv, acc, 0, 0, 0);
         }
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-          const bf16x8 bv = *reinterpret_cast<const bf16x8*>(xt + row * 128 + (((2 * kk + hh) ^ ((row >> 1) & 7)) << 4));
+          const bf16x8 bv = lds_row_frag(xt, row, 128, kk, hh, swz128_row(row));
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2f[kk], bv, acc, 0, 0, 0);
         }
         if (i == 1 && more) {
@@ -185,6 +173,7 @@ __global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, const 
           if (d < 3) hist[d][i][e] = yp[e];
           last[e] = yp[e];
         }
+        // lane pairing (written out: as a call to pair_up8 this kernel compiles to a different instruction order)
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
@@ -192,11 +181,8 @@ __global__ __launch_bounds__(KG_NT) void conv_k3gate_kernel(K3GateArgs p, const 
             auto sw = __builtin_amdgcn_permlane32_swap(yp[4 * h2 + dd], yp[4 * h2 + 2 + dd], false, false);
             yp[4 * h2 + dd] = sw[0]; yp[4 * h2 + 2 + dd] = sw[1];
           }
-        {                                                     // rows >= T are out of the V#'s range: dropped, but ISSUED
-          const unsigned vo = (unsigned)t * pitch_z + (unsigned)(16 * wn + 8 * hh) * 2u;   // 8 consecutive t channels, then the s ones
-          __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[0], (int)yp[1], (int)yp[2], (int)yp[3]}, rz, (int)vo, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[4], (int)yp[5], (int)yp[6], (int)yp[7]}, rz, (int)(vo + 128u), 0, 0);
-        }
+        // rows >= T are out of the V#'s range: dropped, but ISSUED; 8 consecutive t channels, then (128 B on) the s ones
+        store_paired(yp, rz, (unsigned)t * pitch_z + (unsigned)(16 * wn + 8 * hh) * 2u, 128u);
         if (d == 3) {
           // the gate, with the arithmetic of gate_mix_fwd_kernel on the bf16-rounded z (what backward will read)
           unsigned gq[4];
@@ -269,12 +255,9 @@ extern "C" int smt_conv_k3gate_fwd(const void* u2, int64_t bs_u2, int ld_u2, con
   p.bs_u2 = bs_u2; p.bs_x = bs_x; p.bs_z = bs_z; p.bs_g = bs_g;
   p.ld_u2 = ld_u2; p.ld_x = ld_x; p.ld_z = ld_z; p.ld_g = ld_g;
   p.B = batch; p.T = t; p.tiles_per_batch = (t + KG_ROWS - 1) / KG_ROWS;
-  const int ntiles = p.tiles_per_batch * batch;
-  int nwg = std::min(256, std::max(8, ntiles));              // one workgroup per CU (96 KiB of LDS)
-  nwg = (nwg + 7) / 8 * 8;
-  const int tpw = (ntiles + nwg - 1) / nwg;
+  const StreamGrid grid = plan_stream((long long)p.tiles_per_batch * batch, 256, 1);   // one workgroup per CU (96 KiB of LDS)
   (void)hipFuncSetAttribute((const void*)conv_k3gate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, KG_LDS);
-  conv_k3gate_kernel<<<nwg, KG_NT, KG_LDS, stream>>>(p, (const __bf16*)zero_page, tpw);
+  conv_k3gate_kernel<<<grid.nwg, KG_NT, KG_LDS, stream>>>(p, grid.tiles_per_wg);
   SMT_CHECK_LAUNCH("conv_k3gate");
   return 0;
 }

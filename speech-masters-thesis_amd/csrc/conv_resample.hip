@@ -39,20 +39,14 @@ __device__ __forceinline__ void rs_store(const f32x16& acc, const float* bval, f
     yp[2 * g] = pack_bf16x2((acc[4 * g] + bval[4 * g]) * keep, (acc[4 * g + 1] + bval[4 * g + 1]) * keep);
     yp[2 * g + 1] = pack_bf16x2((acc[4 * g + 2] + bval[4 * g + 2]) * keep, (acc[4 * g + 3] + bval[4 * g + 3]) * keep);
   }
-#pragma unroll
-  for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-      auto sw = __builtin_amdgcn_permlane32_swap(yp[4 * h2 + d], yp[4 * h2 + 2 + d], false, false);
-      yp[4 * h2 + d] = sw[0]; yp[4 * h2 + 2 + d] = sw[1];
-    }
-  __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[0], (int)yp[1], (int)yp[2], (int)yp[3]}, ry, (int)vo, 0, 0);
-  __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[4], (int)yp[5], (int)yp[6], (int)yp[7]}, ry, (int)(vo + 32u), 0, 0);
+  pair_up8(yp);
+  store_paired(yp, ry, vo);
 }
 
-// Round 3: both tile loops own their vector-memory waits (conv_common.h, conv_k3gate.hip): untracked LDS-DMA through a V#
-// (rows before the item wrap to huge offsets, rows >= len are beyond it: both read as zero), scalar lens loads, one counted
-// wait per tile that leaves the tile's stores in flight.
+// Both tile loops follow conv_stream.h.  Rows before the item wrap to huge offsets, rows >= len are beyond the V#: both read
+// as zero.  The counted wait at the end of a tile is vmcnt(RS_STORES x the wave's 32-row groups).  (zero_page is no longer
+// read; it stays a kernel parameter because without it the compiler merges the kernel-argument loads differently and the
+// instruction stream of all four kernels changes.)
 
 // ------------------------------------------------------------------------------------------ transposed, C_in = 64
 constexpr int CT_TM = 128;                                   // input rows per tile (256 output rows)
@@ -70,12 +64,8 @@ __global__ __launch_bounds__(RS_NT) void convt4s2_kernel(RsArgs p, const __bf16*
   const int ph = wave & 1, cg = (wave >> 1) % NCG, rh = (wave >> 1) / NCG;
   const int rb = rh * (CT_TM / NRH);                         // first tile row of this wave
 
-  const int ntiles = p.tiles_per_batch * p.B;
-  const int nwg = gridDim.x;
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
-  const int tile_begin = wg * tiles_per_wg;
-  const int tile_end = min(ntiles, tile_begin + tiles_per_wg);
-  if (tile_begin >= tile_end) return;
+  int wg, tile_begin, tile_end;
+  if (!wg_tile_run(p.tiles_per_batch * p.B, tiles_per_wg, wg, tile_begin, tile_end)) return;
 
   // phase 0: taps (3, offset -1), (1, offset 0); phase 1: taps (2, offset 0), (0, offset +1) -- in increasing input offset,
   // the accumulation order of the per-phase launches this kernel replaces (bit-identical results)
@@ -95,10 +85,7 @@ __global__ __launch_bounds__(RS_NT) void convt4s2_kernel(RsArgs p, const __bf16*
 #pragma unroll
   for (int e = 0; e < 16; ++e) bval[e] = p.bias ? p.bias[cg * 32 + 4 * hh + 8 * (e >> 2) + (e & 3)] : 0.f;
 
-  auto decode = [&](int tile, int& b, int& m0) {
-    b = __builtin_amdgcn_readfirstlane(tile / p.tiles_per_batch);
-    m0 = __builtin_amdgcn_readfirstlane((tile - b * p.tiles_per_batch) * CT_TM);
-  };
+  auto decode = [&](int tile, int& b, int& m0) { tile_decode<CT_TM>(tile, p.tiles_per_batch, b, m0); };
   const unsigned pitch_x = (unsigned)p.ldx * 2u, pitch_y = (unsigned)p.ldy * 2u;
   auto stage = [&](int tile, int buf) {
     int b, m0;
@@ -111,7 +98,7 @@ __global__ __launch_bounds__(RS_NT) void convt4s2_kernel(RsArgs p, const __bf16*
       const int gi = wave + (RS_NT / 64) * q;                                   // the third round is wave 0's alone -- see the wait)
       if (gi < CT_ROWS / 8) {
         const int row = 8 * gi + (lane >> 3), pos = lane & 7;
-        untracked_dma16(rx, (unsigned)(m0 - 1 + row) * pitch_x + (unsigned)((pos ^ ((row >> 1) & 7)) << 4), base + gi * 1024);
+        untracked_dma16(rx, (unsigned)(m0 - 1 + row) * pitch_x + (unsigned)((pos ^ swz128_row(row)) << 4), base + gi * 1024);
       }
     }
   };
@@ -137,12 +124,12 @@ __global__ __launch_bounds__(RS_NT) void convt4s2_kernel(RsArgs p, const __bf16*
       const int la = lm + 1 + off_a, lb = lm + 1 + off_b;     // staged rows of the two taps
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
-        const bf16x8 va = *reinterpret_cast<const bf16x8*>(xt + la * 128 + (((2 * kk + hh) ^ ((la >> 1) & 7)) << 4));
+        const bf16x8 va = lds_row_frag(xt, la, 128, kk, hh, swz128_row(la));
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[kk], va, acc, 0, 0, 0);
       }
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
-        const bf16x8 vb = *reinterpret_cast<const bf16x8*>(xt + lb * 128 + (((2 * kk + hh) ^ ((lb >> 1) & 7)) << 4));
+        const bf16x8 vb = lds_row_frag(xt, lb, 128, kk, hh, swz128_row(lb));
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wb[kk], vb, acc, 0, 0, 0);
       }
       const int m = m0 + lm, t = 2 * m + ph;
@@ -169,12 +156,8 @@ __global__ __launch_bounds__(RS_NT) void conv4s2_kernel(RsArgs p, const __bf16* 
   const int r = lane & 31, hh = lane >> 5;
   const int cg = wave & 1, rg = wave >> 1;                   // 32 output channels, 32 output rows
 
-  const int ntiles = p.tiles_per_batch * p.B;
-  const int nwg = gridDim.x;
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
-  const int tile_begin = wg * tiles_per_wg;
-  const int tile_end = min(ntiles, tile_begin + tiles_per_wg);
-  if (tile_begin >= tile_end) return;
+  int wg, tile_begin, tile_end;
+  if (!wg_tile_run(p.tiles_per_batch * p.B, tiles_per_wg, wg, tile_begin, tile_end)) return;
 
   bf16x8 wf[4][KS];
   {
@@ -192,10 +175,7 @@ __global__ __launch_bounds__(RS_NT) void conv4s2_kernel(RsArgs p, const __bf16* 
 
   // chunk c of staged row l sits at c ^ swz(l): consecutive output rows read staged rows 2 apart
   auto swz = [](int l) { return (l >> 1) & (CPR - 1); };
-  auto decode = [&](int tile, int& b, int& t0) {
-    b = __builtin_amdgcn_readfirstlane(tile / p.tiles_per_batch);
-    t0 = __builtin_amdgcn_readfirstlane((tile - b * p.tiles_per_batch) * CS_TO);
-  };
+  auto decode = [&](int tile, int& b, int& t0) { tile_decode<CS_TO>(tile, p.tiles_per_batch, b, t0); };
   const unsigned pitch_x = (unsigned)p.ldx * 2u, pitch_y = (unsigned)p.ldy * 2u;
   auto stage = [&](int tile, int buf) {
     int b, t0;
@@ -245,13 +225,6 @@ __global__ __launch_bounds__(RS_NT) void conv4s2_kernel(RsArgs p, const __bf16* 
   }
 }
 
-static int rs_grid(int ntiles, int* tpw) {
-  int nwg = std::min(256, std::max(8, ntiles));
-  nwg = (nwg + 7) / 8 * 8;
-  *tpw = (ntiles + nwg - 1) / nwg;
-  return nwg;
-}
-
 }  // namespace smt
 
 using namespace smt;
@@ -268,8 +241,8 @@ extern "C" int smt_convt4s2(const void* x, int64_t bs_x, int ld_x, const void* w
   p.x = (const __bf16*)x; p.w = (const __bf16*)w_packed; p.bias = bias; p.y = (__bf16*)y; p.lens_in = lens_in; p.lens_out = lens_out;
   p.x_bs = bs_x; p.y_bs = bs_y; p.ldx = ld_x; p.ldy = ld_y;
   p.B = batch; p.Tin = t_in; p.Tout = 2 * t_in; p.tiles_per_batch = (t_in + CT_TM - 1) / CT_TM;
-  int tpw;
-  const int nwg = rs_grid(p.tiles_per_batch * batch, &tpw);
+  const StreamGrid grid = plan_stream((long long)p.tiles_per_batch * batch, 256, 1);
+  const int nwg = grid.nwg, tpw = grid.tiles_per_wg;
   if (c_out == 128) {
     (void)hipFuncSetAttribute((const void*)convt4s2_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CT_BUF);
     convt4s2_kernel<128><<<nwg, RS_NT, 2 * CT_BUF, stream>>>(p, (const __bf16*)zero_page, tpw);
@@ -294,8 +267,8 @@ extern "C" int smt_conv4s2(const void* x, int64_t bs_x, int ld_x, const void* w_
   p.x = (const __bf16*)x; p.w = (const __bf16*)w_packed; p.bias = bias; p.y = (__bf16*)y; p.lens_in = lens_in; p.lens_out = lens_out;
   p.x_bs = bs_x; p.y_bs = bs_y; p.ldx = ld_x; p.ldy = ld_y;
   p.B = batch; p.Tin = t_in; p.Tout = t_in / 2; p.tiles_per_batch = (p.Tout + CS_TO - 1) / CS_TO;
-  int tpw;
-  const int nwg = rs_grid(p.tiles_per_batch * batch, &tpw);
+  const StreamGrid grid = plan_stream((long long)p.tiles_per_batch * batch, 256, 1);
+  const int nwg = grid.nwg, tpw = grid.tiles_per_wg;
   if (c_in == 128) {
     constexpr int BUF = (2 * CS_TO + 2 + 3) / 4 * 4 * 256;
     (void)hipFuncSetAttribute((const void*)conv4s2_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BUF);

@@ -50,11 +50,7 @@ __device__ __forceinline__ int tr_lane_row(int lane) { return 8 * (lane >> 5) + 
 __device__ __forceinline__ int tr_lane_col(int lane) { return 16 * ((lane >> 4) & 1) + 4 * (lane & 3); }
 __device__ __forceinline__ bf16x8 tr_read2(const void* a0, int step4_bytes) {
   const unsigned char* a = reinterpret_cast<const unsigned char*>(a0);
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + step4_bytes));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
+  return lds_tr2(a, a + step4_bytes);
 }
 __device__ __forceinline__ bf16x8 frag_tr_bf16(const __bf16* tile, int pitch, int row0, int col0, int lane) {
   return tr_read2(tile + (row0 + tr_lane_row(lane)) * pitch + col0 + tr_lane_col(lane), 4 * pitch * 2);
@@ -267,7 +263,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_dma_kernel(WgradArgs p) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
-  // Untracked LDS-DMA through range-checked V#s (conv_common.h): the compiler used to put a wait for the NEXT tile's
+  // Untracked LDS-DMA through range-checked V#s (conv_stream.h): the compiler used to put a wait for the NEXT tile's
   // prefetch in front of the first transposed read of the current tile, so nothing overlapped.  An offset of ~0 is out of
   // range of any descriptor: such lanes read zero (rows past the chunk, before the item, past the valid length).
   const UntrackedRsrc rdy = untracked_rsrc(dyg + co0, 0, (unsigned)min((long long)0xfffffff0ll, (long long)p.Tout * p.ldy * 2));
@@ -420,7 +416,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_shift_kernel(ShiftArgs p, cons
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
-  // Staging through range-checked V#s (conv_common.h: ws_rsrc / ws_dma16), as in conv_ws.hip: one descriptor per operand
+  // Staging through range-checked V#s (conv_stream.h: ws_rsrc / ws_dma16), as in conv_ws.hip: one descriptor per operand
   // and tile covers the valid class-domain rows of the tile's item (dy: Tc rows, x: len_in rows), a lane's source is a 32-bit
   // byte offset = tile-invariant lane part + a scalar per tile, and whatever lies outside -- rows before the item (the offset
   // wraps to ~4 GiB), rows at or past Tc / len_in, rows no tap reads -- is out of range and lands in LDS as zero.  (The plan

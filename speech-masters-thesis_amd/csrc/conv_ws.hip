@@ -54,7 +54,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 // compiled kernels stayed instruction-identical.  Pieces that did not pass that check are still written out per kernel: the
 // loops of the weight-slice load, of the activation staging (stage_a) and of the epilogue-operand staging (stage_epi), and
 // in conv_ws2_kernel the tap bases and the lane pairing.  (The persistent tile split and the lane pairing with its stores
-// are in conv_common.h: wg_tile_run, pair_up8, store_paired.)
+// are in conv_stream.h: wg_tile_run, pair_up8, store_paired.)
 
 // weight fragment kk of output channel co (row wrow of the packed block; packed swizzled: chunk c of row co sits at
 // c ^ (co & 15)): a wave keeps its 32 output channels of every tap in registers
@@ -72,7 +72,7 @@ __device__ __forceinline__ void ws_decode(int tiles_per_batch, int rs, int tile,
 // fragment address of step (s, kk) = tap_base[s] ^ (32 kk): buffers are 1 KiB-aligned, so the XOR swizzle of the 16-byte
 // chunk index (bits 4..7) can be applied after the buffer base has been added.  ar = lane row + tap offset: rows
 // ar + 32 i share the swizzle term (ar & 15).
-__device__ __forceinline__ unsigned ws_tap_base(unsigned abase, int ar, int hh) { return abase + ar * WS_ROWB + ((hh ^ (ar & 15)) << 4); }
+__device__ __forceinline__ unsigned ws_tap_base(unsigned abase, int ar, int hh) { return abase + ar * WS_ROWB + ((hh ^ swz256_row(ar)) << 4); }
 template <int NTAPS>
 __device__ __forceinline__ unsigned ws_frag_addr(const unsigned (&tap_base)[NTAPS], int q) {
   return tap_base[q / WS_KSTEPS] ^ (32u * (q % WS_KSTEPS));
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_kernel(ConvArgs p, const __bf16
   // [0, valid rows) are out of range of the V# and read as zero.  Group g = wave + 4 j covers rows 16 j + 4 wave + lrow,
   // so the swizzle term (row & 15) does not depend on j.
   const unsigned pitch_x = (unsigned)p.ldx * rs * 2u;
-  const unsigned voff_a0 = (unsigned)(4 * wave + lrow) * pitch_x + (unsigned)((lch ^ ((4 * wave + lrow) & 15)) << 4);
+  const unsigned voff_a0 = (unsigned)(4 * wave + lrow) * pitch_x + (unsigned)((lch ^ swz256_row(4 * wave + lrow)) << 4);
   const int ngroups = rows_pad >> 2;
   auto stage_a = [&](int tile, int buf) {
     int b, cls, t0;
@@ -453,7 +453,7 @@ __global__ __launch_bounds__(WS_NT) void conv_ws_pipe_kernel(ConvArgs p, const _
   auto decode = [&](int tile, int& b, int& cls, int& t0) { ws_decode(p.tiles_per_batch, rs, tile, b, cls, t0); };
   // buffer addressing as in conv_ws_kernel: one per-lane offset, a scalar per tile, out-of-range rows read as zero
   const unsigned pitch_x = (unsigned)p.ldx * rs * 2u;
-  const unsigned voff_a0 = (unsigned)(4 * wave + lrow) * pitch_x + (unsigned)((lch ^ ((4 * wave + lrow) & 15)) << 4);
+  const unsigned voff_a0 = (unsigned)(4 * wave + lrow) * pitch_x + (unsigned)((lch ^ swz256_row(4 * wave + lrow)) << 4);
   const int ngroups = rows_pad >> 2;
   auto stage_a = [&](int tile, int buf) {
     int b, cls, t0;
@@ -705,7 +705,7 @@ __global__ __launch_bounds__(WS2_NT) void conv_ws2_kernel(ConvArgs p, const __bf
 #pragma unroll
   for (int j = 0; j < NG; ++j) {
     const int row = 4 * (wave + 8 * j) + (lane >> 4);
-    voff_a[j] = (unsigned)row * pitch_x + (unsigned)(((lane & 15) ^ (row & 15)) << 4);
+    voff_a[j] = (unsigned)row * pitch_x + (unsigned)(((lane & 15) ^ swz256_row(row)) << 4);
   }
   const unsigned pitch_o = (MODE == 2 ? (unsigned)p.ldy : (unsigned)p.ldya) * rs * 2u;    // output rows
   const unsigned voff_o = (unsigned)(64 * rhalf + r) * pitch_o + (unsigned)hh * 16u;      // row block i: + 32 i pitch_o
@@ -789,9 +789,7 @@ __global__ __launch_bounds__(WS2_NT) void conv_ws2_kernel(ConvArgs p, const __bf
           auto sw = __builtin_amdgcn_permlane32_swap(yp[4 * h2 + d], yp[4 * h2 + 2 + d], false, false);
           yp[4 * h2 + d] = sw[0]; yp[4 * h2 + 2 + d] = sw[1];
         }
-      const unsigned vo = voff_o + so + (unsigned)(32 * i) * pitch_o;    // rows >= Tc are out of range: dropped by the hardware
-      __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[0], (int)yp[1], (int)yp[2], (int)yp[3]}, ry, (int)vo, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(i32x4v{(int)yp[4], (int)yp[5], (int)yp[6], (int)yp[7]}, ry, (int)(vo + 32u), 0, 0);
+      store_paired(yp, ry, voff_o + so + (unsigned)(32 * i) * pitch_o);    // rows >= Tc are out of range: dropped by the hardware
     }
   };
 
@@ -828,7 +826,7 @@ __global__ __launch_bounds__(WS2_NT) void conv_ws2_kernel(ConvArgs p, const __bf
 #pragma unroll
     for (int s = 0; s < NTAPS; ++s) {
       const int ar = r + s * p.dil;                 // rows ar + 32 i (+ 64 rhalf) share the swizzle term (ar & 15)
-      tap_base[s] = abase + ar * ROWB + ((hh ^ (ar & 15)) << 4);
+      tap_base[s] = abase + ar * ROWB + ((hh ^ swz256_row(ar)) << 4);
     }
     auto frag_addr = [&](int q) -> unsigned { return ws_frag_addr(tap_base, q); };
     bf16x8 afr[3][MW];

@@ -246,9 +246,19 @@ def test_lds_dma_conv_kernel_matches_generic_kernel(k, dil):
     """The LDS-DMA variant (bf16, C % 128 == 0, XOR-swizzled operands) against the register-staged generic
     kernel on the same inputs: same MFMA, same k order -> bit-identical outputs; ragged lens, residual,
     activation-derivative epilogue and the activated second output included."""
+    lds_dma_conv_vs_generic(k, dil, 700)
+
+
+def test_persistent_1x1_kernel_at_three_tiles_per_workgroup():
+    """conv1x1_dma as above at 3 x 44000 rows: 1032 tiles on 512 workgroups, three tiles per workgroup -- the second reuse
+    of a staging buffer, which the 700-row case (two tiles per workgroup) does not reach."""
+    lds_dma_conv_vs_generic(1, 1, 44000)
+
+
+def lds_dma_conv_vs_generic(k, dil, t):
     from smt_amd import convops as C
     g = torch.Generator(device="cuda").manual_seed(k)
-    b, t, c = 3, 700, 128
+    b, c = 3, 128
     big = torch.randn(b, t, 512, device="cuda", generator=g).to(torch.bfloat16)
     x = big[:, :, 128:256]                                   # channel slice: row pitch 512
     w = torch.randn(c, c, k, device="cuda", generator=g) / (c * k) ** 0.5
@@ -362,10 +372,11 @@ def test_fused_1x1_backward_matches_separate_kernels(b, t):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("b,t", [(3, 700), (2, 20011)])
+@pytest.mark.parametrize("b,t", [(3, 700), (2, 20011), (3, 44000)])
 def test_folded_1x1_conv_matches_float64(b, t):
     """conv1x1_fold (y = W u + b + W2 x2 + b2, the K3 + recomputed-K1 residual of GatedHiFiBlock) against a float64
-    evaluation of the same bf16 operands; x2 rows beyond lens read as 0, u rows are not masked."""
+    evaluation of the same bf16 operands; x2 rows beyond lens read as 0, u rows are not masked.  (3, 44000): 1032 tiles on
+    256 workgroups, five tiles per workgroup -- every staging buffer is reused, the last run is short."""
     from smt_amd import convops as C
     g = torch.Generator(device="cuda").manual_seed(11 * b + t)
     c, w_in = 128, 64
@@ -424,10 +435,11 @@ def test_shifted_fragment_wgrad_matches_float64(k, dil):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("b,t,train", [(3, 700, True), (2, 20011, True), (2, 1000, False)])
+@pytest.mark.parametrize("b,t,train", [(3, 700, True), (2, 20011, True), (2, 1000, False), (3, 44000, True)])
 def test_k1_activated_output_kernel_matches_generic_kernel(b, t, train):
     """conv_k1act (64 -> 512, only u = relu(dropout(W x + b)) written, four dropout sites) against the generic
-    kernel on the same inputs: bit-identical, ragged lens included."""
+    kernel on the same inputs: bit-identical, ragged lens included.  (3, 44000): 1032 tiles on 512 workgroups, three tiles
+    per workgroup -- the second reuse of a staging buffer."""
     from smt_amd import convops as C
     g = torch.Generator(device="cuda").manual_seed(13 * b + t)
     w_in, c_out = 64, 512
@@ -457,10 +469,11 @@ def test_k1_activated_output_kernel_matches_generic_kernel(b, t, train):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("b,t", [(3, 700), (2, 20011), (1, 1), (2, 128)])
+@pytest.mark.parametrize("b,t", [(3, 700), (2, 20011), (1, 1), (2, 128), (3, 44000)])
 def test_gate_conv_forward_kernel_matches_generic_kernel(b, t):
     """conv1x1_c64 (the 64 -> 64 gate conv with the block input as residual, out = W g + b + x) against the generic kernel on
-    the same inputs: bit-identical, ragged lens and channel-sliced (pitch 256) operands included."""
+    the same inputs: bit-identical, ragged lens and channel-sliced (pitch 256) operands included.  (3, 44000): 2064 tiles on
+    1024 workgroups, three tiles per workgroup -- the second reuse of a staging buffer."""
     from smt_amd import convops as C
     g = torch.Generator(device="cuda").manual_seed(17 * b + t)
     big = torch.randn(b, t, 128, device="cuda", generator=g).to(torch.bfloat16)
@@ -567,10 +580,11 @@ def test_pack_cache_follows_in_place_weight_updates():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("b,t", [(3, 700), (2, 20011), (1, 1)])
+@pytest.mark.parametrize("b,t", [(3, 700), (2, 20011), (1, 1), (3, 44000)])
 def test_fused_gate_conv_backward_matches_separate_kernels(b, t):
     """smt_conv_gate_bwd (one pass over dout) against the data-gradient conv it replaces (bit-identical: same MFMA
-    chain) and a float64 reference for the fp32 weight / bias gradients; ragged lens included."""
+    chain) and a float64 reference for the fp32 weight / bias gradients; ragged lens included.  (3, 44000): 1032 tiles on
+    512 workgroups, three tiles per workgroup (the second reuse of a staging buffer), 168 workgroups without a tile."""
     from smt_amd import convops as C
     g_ = torch.Generator(device="cuda").manual_seed(19 * b + t)
     c = 64
@@ -832,10 +846,22 @@ def test_resampling_stream_kernels_match_the_generic_kernel(c_wide):
     """smt_conv4s2 / smt_convt4s2 (k = 4, stride 2, padding 1, width 64) against the generic implicit-GEMM launches they
     replace: forward and data gradient of the strided conv (c_wide -> 64) and of the transposed conv (64 -> c_wide),
     ragged lens, a length that is not a multiple of the 128-row tile, bias, bit-identical outputs."""
+    resampling_stream_vs_generic(c_wide, 2 * 1237)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c_wide", [64, 128])
+def test_resampling_stream_kernels_at_three_tiles_per_workgroup(c_wide):
+    """As above on 2 x 22001 input rows: 516 tiles on 256 workgroups, three tiles per workgroup -- the second reuse of a
+    staging buffer, which the short case (one tile per workgroup) does not reach."""
+    resampling_stream_vs_generic(c_wide, 2 * 22001)
+
+
+def resampling_stream_vs_generic(c_wide, t):
     from smt_amd import convops as C
     from smt_amd import profiler
     g = torch.Generator(device="cuda").manual_seed(c_wide)
-    b, t = 3, 2 * 1237
+    b = 3
     lens = torch.tensor([t, t - 501, 64], device="cuda", dtype=torch.int32)
     x = torch.randn(b, t, c_wide, device="cuda", generator=g).to(torch.bfloat16)
     w = torch.randn(64, c_wide, 4, device="cuda", generator=g) / (c_wide * 4) ** 0.5

@@ -107,16 +107,27 @@ def test_fused_k3_gate_kernel_is_bit_identical_to_the_unfused_path():
     """smt_conv_k3gate_fwd (K3 of the four branches + tanh * softmax gate in one pass) against the four folded K3 launches
     + gate_mix_fwd it replaces: same z, same g -> the block output and every gradient are bit-identical; ragged lens, a
     row count that is not a multiple of the 128-row tile, train mode."""
+    fused_k3_gate_vs_unfused(5000 + 77, [5000 + 77, 4000, 129])
+
+
+def test_fused_k3_gate_kernel_at_five_tiles_per_workgroup():
+    """As above at 3 x 44000 rows: 1032 tiles on 256 workgroups, five tiles per workgroup with a short last run -- the
+    staging buffers are reused, which the 5077-row case (one tile per workgroup) does not reach.  The other streaming
+    kernels of the block (K1, the fused backward kernels, the gate conv) run at three or more tiles per workgroup here."""
+    fused_k3_gate_vs_unfused(44000, [44000, 30000, 129])
+
+
+def fused_k3_gate_vs_unfused(t, lens):
     from models.vqvae.resnet import GatedHiFiBlock
     from smt_amd import convops, profiler
     torch.manual_seed(3)
     blk = GatedHiFiBlock(64, 4, dilation_growth_rate=3, kernel_size_growth_rate=2, zero_out=False, dropout=0.1,
                          site_base=8).cuda().train()
     g = torch.Generator().manual_seed(9)
-    b, t = 3, 5000 + 77
+    b = 3
     x = torch.randn(b, t, 64, generator=g).cuda().to(torch.bfloat16)
     dy = torch.randn(b, t, 64, generator=g).cuda().to(torch.bfloat16)
-    lens = torch.tensor([t, 4000, 129], dtype=torch.int32).cuda()
+    lens = torch.tensor(lens, dtype=torch.int32).cuda()
     outs = []
     for fused in (True, False):
         convops._K3GATE = fused
