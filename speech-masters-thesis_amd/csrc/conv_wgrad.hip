@@ -16,6 +16,7 @@
 // gradient rides along as one extra "tap" whose x operand is the constant 1.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "conv_common.h"
 
@@ -68,15 +69,80 @@ __device__ __forceinline__ WgBlock wgrad_block(int nblk_ci, int nblk_co) {
   return w;
 }
 
+#ifndef SMT_WGRAD_STAMP
+#define SMT_WGRAD_STAMP 0   // diagnostic build (tools/wgrad_phases.sh): per-wave cycle sums of the phases of conv_wgrad_kernel and conv_wgrad_shift_kernel
+#endif
+#if SMT_WGRAD_STAMP
+// [workgroup < 256][wave][barrier | stage | k-loop | slab store | tiles]: written here, read by smt_wgrad_debug_dump only
+__device__ unsigned long long wg_dbg[256 * 8 * 8];
+__device__ __forceinline__ unsigned long long wg_stamp() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+// the sums stay in scalar registers during the tile loop and leave the kernel once, after the slab store
+#define WG_SUMS unsigned long long wg_sum[5] = {0, 0, 0, 0, 0}
+#define WG_T(var) const unsigned long long var = wg_stamp()
+#define WG_ACC(k, a, b) wg_sum[k] += (b) - (a)
+#define WG_DUMP do { if (lane == 0 && blockIdx.x < 256) for (int k_ = 0; k_ < 5; ++k_) wg_dbg[(blockIdx.x * 8 + wave) * 8 + k_] += wg_sum[k_]; } while (0)
+#else
+#define WG_SUMS do {} while (0)
+#define WG_T(var) do {} while (0)
+#define WG_ACC(k, a, b) do {} while (0)
+#define WG_DUMP do {} while (0)
+#endif
+
+// Quotient by a divisor fixed for the launch: q = n / s as one v_mul_hi_u32 with magic = ceil(2^32 / s); exact while
+// n * s < 2^32 (here n is a staged row, below 1,000)
+__device__ __forceinline__ unsigned div_magic(int s) { return 0xffffffffu / (unsigned)s + 1u; }
+
 // NT = accumulator planes (taps + bias plane); CIB = input channels per workgroup; STRIDED = stride > 1
+//
+// The tile loop overlaps staging with the k-loop through a register prefetch: the global loads of tile i+1 are issued
+// right before the k-loop of tile i and retired into LDS after it, behind the barrier that frees the (single) LDS buffer.
+// A thread keeps the dy tile and the first XS slots of the x tile that way (9 or 13 16-byte vectors at 64 channels), which is
+// the whole tile for a halo of up to 32 rows at stride 1 and for the k = 4 stride-2 conv; what a wider halo adds is loaded
+// at the store, as the whole tile used to be.  (On the flagship's 64-channel resampling convs the prefetch is worth 2-4 % at
+// the largest level and nothing measurable below it; the k-loop changes carry the gain: profiles/wgrad_generic_ab.txt.)
+//
+// bf16, STRIDED: the haloed x rows are staged into `stride` planes by row residue (plane q holds the staged rows
+// == q mod stride, in order; the planes follow each other, so the tile takes the same rows_x rows of LDS).  The x row of
+// (k, tap j), k * stride + j * dil, is then row k + (j * dil) / stride of plane (j * dil) % stride: 16 consecutive k are 16
+// consecutive LDS rows, and the B fragment of a tap is the same pair of transposed reads as at stride 1.
+//
+// Per instance: whether the prefetch is on, and the waves per SIMD the register allocation must leave room for
+// (profiles/wgrad_generic_ab.txt has the table these come from).
+#ifndef SMT_WGRAD_PREFETCH
+#define SMT_WGRAD_PREFETCH -1   // diagnostic builds: 0 / 1 = the prefetch off / on in every instance
+#endif
+#ifndef SMT_WGRAD_WAVES
+#define SMT_WGRAD_WAVES 0       // diagnostic builds: waves per SIMD of every instance
+#endif
+constexpr bool wgrad_prefetch(int esz, int nt, int cib, bool strided) {
+  if (SMT_WGRAD_PREFETCH >= 0) return SMT_WGRAD_PREFETCH != 0;
+  return true;                                        // every instance holds it without scratch at the occupancy below
+}
+// The most waves the LDS tile admits anyway (three 49 KB workgroups of 64 bf16 channels at stride 1; two at stride 2) that
+// the accumulators, the prefetch and two fragment requests fit without scratch.
+constexpr int wgrad_waves_per_simd(int esz, int nt, int cib, bool strided) {
+  if (SMT_WGRAD_WAVES > 0) return SMT_WGRAD_WAVES;
+  if (cib == 128) return 2;                           // 8 waves per workgroup
+  if (esz == 2) return (!strided && nt <= 4) ? 3 : 2;
+  return nt <= (strided ? 4 : 5) ? 3 : 2;
+}
 template <typename T, int NT, int CIB, bool STRIDED>
-__global__ __launch_bounds__(CIB * 4) void conv_wgrad_kernel(WgradArgs p) {
+__global__ __launch_bounds__(CIB * 4) __attribute__((amdgpu_waves_per_eu(wgrad_waves_per_simd(sizeof(T), NT, CIB, STRIDED))))
+void conv_wgrad_kernel(WgradArgs p) {
   constexpr int EPV = Tr<T>::EPV;
   constexpr int R = WTr<T>::R;          // rows per staged tile
   constexpr int CB = 64;                // output channels per block
   constexpr int WNC = CIB / 32;         // wave columns
   constexpr int NTHR = 128 * WNC;
   constexpr int PITCH_DY = WTr<T>::pitch(CB), PITCH_X = WTr<T>::pitch(CIB);
+  constexpr bool PLANES = STRIDED && sizeof(T) == 2;
+  constexpr bool PREFETCH = wgrad_prefetch(sizeof(T), NT, CIB, STRIDED);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WNC, wn = wave % WNC;
@@ -97,7 +163,15 @@ __global__ __launch_bounds__(CIB * 4) void conv_wgrad_kernel(WgradArgs p) {
   const T* dyg = reinterpret_cast<const T*>(p.dy) + (long long)b * p.dy_bs;
   const int len_in = p.lens_in ? min(p.lens_in[b], p.Tin) : p.Tin;
   const bool bias_plane = p.with_bias && (ci0 == 0);
-  const int ntaps = p.taps;
+
+  // LDS row of staged x row `row` (0 <= row < rows_x): planes 0 .. rows_x % stride - 1 hold one row more than the others
+  const unsigned s_magic = PLANES ? div_magic(p.stride) : 0u;
+  const int plane_q = PLANES ? rows_x / p.stride : 0, plane_rem = PLANES ? rows_x % p.stride : 0;
+  auto lds_row_x = [&](int row) {
+    if constexpr (!PLANES) return row;
+    const int q = (int)__umulhi((unsigned)row, s_magic), pl = row - q * p.stride;
+    return pl * plane_q + min(pl, plane_rem) + q;
+  };
 
   f32x16 acc[NT];
 #pragma unroll
@@ -105,84 +179,152 @@ __global__ __launch_bounds__(CIB * 4) void conv_wgrad_kernel(WgradArgs p) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
-  for (int t0 = t_begin; t0 < t_end; t0 += R) {
-    __syncthreads();
-    // dy tile (rows t0..t0+R, channels co0..co0+64) and haloed x tile: all loads of a batch are
-    // issued before the first LDS store so that one memory latency covers UB vectors per thread
-    constexpr int VPR_DY = CB / EPV, VPR_X = CIB / EPV;
-    constexpr int UB = (NT > 6) ? 4 : 8;   // fewer in-flight staging registers when the accumulators are many
-    const int tin0 = t0 * p.stride - p.pad;
-    const int n_dy = R * VPR_DY, n_x = rows_x * VPR_X;
-    for (int f0 = tid; f0 < n_dy + n_x; f0 += NTHR * UB) {
-      Vec<T, EPV> v[UB];
+  // Staging: a thread moves one 16-byte vector per slot, always the same channels; a slot is RPS_DY rows of the dy tile (rows
+  // t0.., channels co0..co0+64) or RPS_X rows of the haloed x tile.  Rows >= t_end, ty >= Ty, tin outside [0, len_in) and
+  // channels beyond Cin / Cout are zeros.  Slots 0 .. DYS-1 (dy) and the first XS of x are prefetched.
+  typedef Vec<T, EPV> V;
+  constexpr int VPR_DY = CB / EPV, VPR_X = CIB / EPV;
+  constexpr int RPS_DY = NTHR / VPR_DY, RPS_X = NTHR / VPR_X;
+  constexpr int DYS = R / RPS_DY;
+  constexpr int XS = STRIDED ? 9 : 5;    // 5: a halo of up to 32 (fp32: 16) rows at stride 1; 9: k = 4 at stride 2
+  constexpr int UB = 4;                  // beyond them: loads in flight per thread
+  static_assert(R % RPS_DY == 0, "whole slots");
+  const int rd = tid / VPR_DY, cd = (tid % VPR_DY) * EPV, rx = tid / VPR_X, cx = (tid % VPR_X) * EPV;
+  const bool cd_ok = co0 + cd < p.Cout, cx_ok = ci0 + cx < p.Cin;
+  auto fetch_dy = [&](int t0, int slot_row) {
+    V v;
 #pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int f = f0 + NTHR * u;
+    for (int e = 0; e < EPV; ++e) v.v[e] = (T)0.f;
+    const int t = t0 + slot_row + rd;
+    const int ty = t * p.out_stride + p.out_offset;
+    if (t < t_end && ty < p.Ty && cd_ok) v = *reinterpret_cast<const V*>(dyg + (long long)ty * p.ldy + co0 + cd);
+    return v;
+  };
+  auto fetch_x = [&](int t0, int slot_row) {
+    V v;
 #pragma unroll
-        for (int e = 0; e < EPV; ++e) v[u].v[e] = (T)0.f;
-        if (f < n_dy) {
-          const int row = f / VPR_DY, cv = f % VPR_DY;
-          const int t = t0 + row;
-          const int ty = t * p.out_stride + p.out_offset;
-          if (t < t_end && ty < p.Ty && co0 + cv * EPV < p.Cout)
-            v[u] = *reinterpret_cast<const Vec<T, EPV>*>(dyg + (long long)ty * p.ldy + co0 + cv * EPV);
-        } else if (f < n_dy + n_x) {
-          const int g = f - n_dy;
-          const int row = g / VPR_X, cv = g % VPR_X;
-          const int tin = tin0 + row;
-          if (tin >= 0 && tin < len_in && ci0 + cv * EPV < p.Cin)
-            v[u] = *reinterpret_cast<const Vec<T, EPV>*>(xg + (long long)tin * p.ldx + ci0 + cv * EPV);
-        }
-      }
+    for (int e = 0; e < EPV; ++e) v.v[e] = (T)0.f;
+    const int row = slot_row + rx;
+    const int tin = t0 * p.stride - p.pad + row;
+    if (row < rows_x && tin >= 0 && tin < len_in && cx_ok) v = *reinterpret_cast<const V*>(xg + (long long)tin * p.ldx + ci0 + cx);
+    return v;
+  };
+  auto put_dy = [&](int slot_row, const V& v) { *reinterpret_cast<V*>(lds_dy + (slot_row + rd) * PITCH_DY + cd) = v; };
+  auto put_x = [&](int slot_row, const V& v) {
+    const int row = slot_row + rx;
+    if (row < rows_x) *reinterpret_cast<V*>(lds_x + lds_row_x(row) * PITCH_X + cx) = v;
+  };
+  V pf_dy[DYS], pf_x[XS];
+  auto prefetch = [&](int t0) {
 #pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int f = f0 + NTHR * u;
-        if (f < n_dy) {
-          *reinterpret_cast<Vec<T, EPV>*>(lds_dy + (f / VPR_DY) * PITCH_DY + (f % VPR_DY) * EPV) = v[u];
-        } else if (f < n_dy + n_x) {
-          const int g = f - n_dy;
-          *reinterpret_cast<Vec<T, EPV>*>(lds_x + (g / VPR_X) * PITCH_X + (g % VPR_X) * EPV) = v[u];
-        }
+    for (int u = 0; u < DYS; ++u) pf_dy[u] = fetch_dy(t0, u * RPS_DY);
+#pragma unroll
+    for (int u = 0; u < XS; ++u) pf_x[u] = fetch_x(t0, u * RPS_X);
+  };
+
+  // bf16: per-lane LDS byte addresses of the transposed fragments of k-step 0 (dy, and x per tap)
+  static_assert(NT >= 2, "at least one tap and the bias plane");
+  constexpr int NB = NT - 1;                // taps: the launch picks the instance with NT == taps + 1 (SMT_WG_BY_PLANES)
+  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  struct Frags { u32x2 a0, a1, b0[NB], b1[NB]; };
+  constexpr int NREAD = 2 + 2 * NB;         // ds_read instructions per request
+  static_assert(NREAD <= 15, "lgkmcnt counts up to 15");
+  unsigned a_addr = 0, x_addr[NB];
+  if constexpr (sizeof(T) == 2) {
+    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
+    a_addr = lds0 + (unsigned)(tr_lane_row(lane) * PITCH_DY + wm * 32 + tr_lane_col(lane)) * 2u;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const int row_j = lds_row_x(j * p.dil);
+      x_addr[j] = lds0 + (unsigned)(R * PITCH_DY + (row_j + tr_lane_row(lane)) * PITCH_X + wn * 32 + tr_lane_col(lane)) * 2u;
+    }
+  }
+  // The fragments of k-step k+1 are requested (asm, so that the requests stay where they are written) before the MFMAs of
+  // k-step k; `s_waitcnt lgkmcnt(NREAD)` then retires exactly the older request (LDS returns in order), and the wait
+  // pins the fragments so that nothing that uses them can be scheduled above it.  Two requests are in flight at most:
+  // hoisting the reads of all eight k-steps would spill.
+  // (the k-step arrives as a type, so that its row offset goes into the instructions' offset fields)
+  auto request = [&](Frags& f, auto ks_) {
+    constexpr int KS = decltype(ks_)::value;
+    const unsigned pa = a_addr;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.a0) : "v"(pa), "n"(KS * 16 * PITCH_DY * 2));
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.a1) : "v"(pa), "n"((KS * 16 + 4) * PITCH_DY * 2));
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const unsigned px = x_addr[j];
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.b0[j]) : "v"(px), "n"(KS * 16 * PITCH_X * 2));
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.b1[j]) : "v"(px), "n"((KS * 16 + 4) * PITCH_X * 2));
+    }
+  };
+  static_assert((R + 4) * PITCH_X * 2 < 65536, "the k-step offsets fit the 16-bit offset field");
+  bf16x8 ones;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
+  Frags fr[2];
+  auto k_step = [&](auto ks_) {
+    constexpr int KS = decltype(ks_)::value;
+    Frags& f = fr[KS & 1];
+    if constexpr (KS + 1 < R / 16) {
+      request(fr[(KS + 1) & 1], std::integral_constant<int, KS + 1>{});
+      lgkm_wait<NREAD>(f.a0, f.a1, f.b0, f.b1);
+    } else {
+      lgkm_wait<0>(f.a0, f.a1, f.b0, f.b1);
+    }
+    const u32x4 aw = {f.a0[0], f.a0[1], f.a1[0], f.a1[1]};
+    const bf16x8 a = __builtin_bit_cast(bf16x8, aw);               // A[co][k] = dy[k][co]
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      if (j < NB) {
+        const int jb = j < NB ? j : 0;
+        const u32x4 bw = {f.b0[jb][0], f.b0[jb][1], f.b1[jb][0], f.b1[jb][1]};   // B[k][ci] = x[k * stride + j * dil][ci]
+        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, bw), acc[j], 0, 0, 0);
       }
     }
+    if (bias_plane) acc[NB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, acc[NB], 0, 0, 0);
+  };
+
+  WG_SUMS;
+  if constexpr (PREFETCH) prefetch(t_begin);
+  for (int t0 = t_begin; t0 < t_end; t0 += R) {
+    WG_T(c0);
+    __syncthreads();                       // every wave has left the k-loop of the previous tile: the LDS tile is free
+    WG_T(c1);
+    if constexpr (!PREFETCH) prefetch(t0);   // no overlap: all loads of the tile, then the stores
+#pragma unroll
+    for (int u = 0; u < DYS; ++u) put_dy(u * RPS_DY, pf_dy[u]);
+#pragma unroll
+    for (int u = 0; u < XS; ++u) put_x(u * RPS_X, pf_x[u]);
+    for (int row0 = XS * RPS_X; row0 < rows_x; row0 += UB * RPS_X) {   // a wider halo: what is not prefetched
+      V v[UB];
+#pragma unroll
+      for (int u = 0; u < UB; ++u) v[u] = fetch_x(t0, row0 + u * RPS_X);
+      // every path waits for these loads here: left to the stores, the wait sits in a branch that rows beyond the halo skip,
+      // and the compiler would then wait for ALL vector memory -- the prefetch included -- at the first k-step
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        f32x4 t = __builtin_bit_cast(f32x4, v[u]);
+        pin_v(t);
+        v[u] = __builtin_bit_cast(V, t);
+      }
+#pragma unroll
+      for (int u = 0; u < UB; ++u) put_x(row0 + u * RPS_X, v[u]);
+    }
+    WG_T(c2);
     __syncthreads();
+    WG_T(c3);
+    if constexpr (PREFETCH)
+      if (t0 + R < t_end) prefetch(t0 + R);   // in flight during the k-loop
 
     if constexpr (sizeof(T) == 2) {
-      const __bf16* dyt = reinterpret_cast<const __bf16*>(lds_dy);
-      const __bf16* xt = reinterpret_cast<const __bf16*>(lds_x);
-      bf16x8 ones;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
-      // bound the unrolling: hoisting every transposed read of 8 k-steps x NT taps would spill
-#pragma unroll 1
-      for (int k0 = 0; k0 < R; k0 += 16) {
-        bf16x8 a = frag_tr_bf16(dyt, PITCH_DY, k0, wm * 32, lane);   // A[co][k] = dy[k][co]
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          if (j < ntaps) {
-            // B[k][ci] = x[(k)*stride + j*dil][ci]   (stride 1 for every transposed read;
-            // strided convs read rows k*stride: handled by row index arithmetic below)
-            bf16x8 bfrag;
-            if constexpr (!STRIDED) {
-              bfrag = frag_tr_bf16(xt, PITCH_X, k0 + j * p.dil, wn * 32, lane);
-            } else {
-              // strided rows are not a dense 4-row block: gather element-wise
-              typedef short s16x8 __attribute__((ext_vector_type(8)));
-              s16x8 tmp;
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                const short* sp = reinterpret_cast<const short*>(xt) +
-                                  ((k0 + 8 * hh + e) * p.stride + j * p.dil) * PITCH_X + wn * 32 + r;
-                tmp[e] = *sp;
-              }
-              bfrag = __builtin_bit_cast(bf16x8, tmp);
-            }
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bfrag, acc[j], 0, 0, 0);
-          } else if (j == ntaps && bias_plane) {
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, acc[j], 0, 0, 0);
-          }
-        }
-      }
+      static_assert(sizeof(T) != 2 || R == 128, "eight k-steps, written out");
+      __builtin_amdgcn_sched_barrier(0);   // the lgkmcnt counts of the k-steps must see these LDS reads only
+      request(fr[0], std::integral_constant<int, 0>{});
+      k_step(std::integral_constant<int, 0>{}); k_step(std::integral_constant<int, 1>{});
+      k_step(std::integral_constant<int, 2>{}); k_step(std::integral_constant<int, 3>{});
+      k_step(std::integral_constant<int, 4>{}); k_step(std::integral_constant<int, 5>{});
+      k_step(std::integral_constant<int, 6>{}); k_step(std::integral_constant<int, 7>{});
+      __builtin_amdgcn_sched_barrier(0);
     } else {
       const float* dyt = reinterpret_cast<const float*>(lds_dy);
       const float* xt = reinterpret_cast<const float*>(lds_x);
@@ -191,22 +333,23 @@ __global__ __launch_bounds__(CIB * 4) void conv_wgrad_kernel(WgradArgs p) {
         const float a = dyt[(k0 + hh) * PITCH_DY + wm * 32 + r];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-          if (j < ntaps) {
+          if (j < NB) {
             const float bv = xt[((k0 + hh) * p.stride + j * p.dil) * PITCH_X + wn * 32 + r];
             acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv, acc[j], 0, 0, 0);
-          } else if (j == ntaps && bias_plane) {
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, 1.0f, acc[j], 0, 0, 0);
           }
         }
+        if (bias_plane) acc[NB] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, 1.0f, acc[NB], 0, 0, 0);
       }
     }
+    WG_T(c4);
+    WG_ACC(0, c0, c1); WG_ACC(0, c2, c3); WG_ACC(1, c1, c2); WG_ACC(2, c3, c4); WG_ACC(4, c0, c0 + 1);
   }
+  WG_T(c5);
   // partial block -> slab[chunk_global][blk][plane][co 64][ci CIB]
-  const int planes = ntaps + 1;   // slab layout always carries the bias plane (zeros when not requested)
-  float* out = p.slab + ((size_t)w.cgl * w.nblk + w.blk) * (size_t)planes * CB * CIB;
+  // (the slab layout always carries the bias plane: zeros when not requested)
+  float* out = p.slab + ((size_t)w.cgl * w.nblk + w.blk) * (size_t)NT * CB * CIB;
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
-    if (j >= planes) break;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int row = wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;  // co
@@ -214,6 +357,9 @@ __global__ __launch_bounds__(CIB * 4) void conv_wgrad_kernel(WgradArgs p) {
       out[((size_t)j * CB + row) * CIB + col] = acc[j][e];
     }
   }
+  WG_T(c6);
+  WG_ACC(3, c5, c6);
+  WG_DUMP;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -364,31 +510,6 @@ struct ShiftArgs {
   int B, Tin, Tout, pad, rs;
   int tiles_per_item, tiles_per_wg, n_chunks, nblk_ci, nblk_co, with_bias;
 };
-
-#ifndef SMT_WGRAD_STAMP
-#define SMT_WGRAD_STAMP 0   // diagnostic build (tools/wgrad_phases.sh): per-wave cycle sums of the phases of conv_wgrad_shift_kernel
-#endif
-#if SMT_WGRAD_STAMP
-// [workgroup < 256][wave][barrier | stage | k-loop | slab store | tiles]: written here, read by smt_wgrad_debug_dump only
-__device__ unsigned long long wg_dbg[256 * 8 * 8];
-__device__ __forceinline__ unsigned long long wg_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-// the sums stay in scalar registers during the tile loop and leave the kernel once, after the slab store
-#define WG_SUMS unsigned long long wg_sum[5] = {0, 0, 0, 0, 0}
-#define WG_T(var) const unsigned long long var = wg_stamp()
-#define WG_ACC(k, a, b) wg_sum[k] += (b) - (a)
-#define WG_DUMP do { if (lane == 0 && blockIdx.x < 256) for (int k_ = 0; k_ < 5; ++k_) wg_dbg[(blockIdx.x * 8 + wave) * 8 + k_] += wg_sum[k_]; } while (0)
-#else
-#define WG_SUMS do {} while (0)
-#define WG_T(var) do {} while (0)
-#define WG_ACC(k, a, b) do {} while (0)
-#define WG_DUMP do {} while (0)
-#endif
 
 constexpr int SH_R = 128, SH_XROWS = SH_R + 8, SH_DY = SH_R * 128, SH_X = SH_XROWS * 256, SH_STAGE = SH_DY + SH_X;
 
