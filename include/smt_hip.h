@@ -671,6 +671,32 @@ int smt_lm_mmi_fwd(const float* logits, const int64_t* target, const float* coun
 int smt_lm_mmi_bwd(const float* logits, const int64_t* target, const float* lse, const float* logm, const float* coef,
                    float* dlogits, int64_t rows, int vocab, smt_stream_t stream);
 
+/* The dense projections with bf16 operands (model.compute_dtype: bf16; csrc/lm_linear.hip).  Activations, gradients and the
+ * bias stay fp32 in memory: x / dy are rounded to bf16 (round to nearest even, what tensor.to(torch.bfloat16) gives on finite
+ * values) as they are loaded, products accumulate in fp32 on the bf16 MFMA, results are stored as fp32.
+ *   fwd    y[r, o]  = bias[o] + sum_i bf16(x[r, i]) * w[o][i]                 bias fp32 [n_out] or NULL, added in fp32
+ *   dgrad  dx[r, i] = sum_o bf16(dy[r, o]) * w[o][i]
+ *   wgrad  dweight[o * n_in + i] = sum_r bf16(dy[r, o]) * bf16(x[r, i]);  dbias[o] = sum_r dy[r, o] in fp32 from the UNROUNDED
+ *          dy (NULL = not wanted)
+ * w_packed = smt_pack_weight(dtype SMT_BF16, one tap, swizzle 0) of the weight as [n_out][n_in]; w_packed_t = the same weight
+ * packed [n_in][n_out] (the pack's n_out / n_in and strides swapped).
+ * Shapes: n_in a positive multiple of 32, n_out a positive multiple of 16, rows >= 0 arbitrary (rows beyond `rows` are
+ * neither read nor written; columns outside a row's width are neither read nor written).  x / y / dy / dx are rows with an
+ * explicit pitch in elements (>= the width, a multiple of 4); dweight [n_out][n_in] and dbias [n_out] are dense.  Every
+ * pointer is 16-byte aligned (bias: 4).  Row offsets are formed in 64 bits: rows * pitch may exceed 2^31.
+ * Argument errors (a dimension off these rules, a negative rows, a null or misaligned pointer, a pitch below the width or
+ * off the multiple, an output that overlaps an input, a workspace below the queried size) return 1 before any HIP call and
+ * are named by smt_last_error.  rows = 0 returns 0 without a launch; wgrad then zeroes dweight and dbias (the sum over nothing).
+ * No allocation, no host synchronisation, no atomics: wgrad splits the rows over several workgroups per output tile, each
+ * writes a slab into `workspace`, and a second launch adds the slabs in slab order, so equal inputs give equal bits. */
+int smt_lm_linear_fwd(const float* x, int64_t ld_x, const void* w_packed, const float* bias, float* y, int64_t ld_y,
+                      int64_t rows, int n_in, int n_out, smt_stream_t stream);
+int smt_lm_linear_dgrad(const float* dy, int64_t ld_dy, const void* w_packed_t, float* dx, int64_t ld_dx, int64_t rows,
+                        int n_in, int n_out, smt_stream_t stream);
+size_t smt_lm_linear_wgrad_workspace_bytes(int64_t rows, int n_in, int n_out);
+int smt_lm_linear_wgrad(const float* x, int64_t ld_x, const float* dy, int64_t ld_dy, float* dweight, float* dbias,
+                        int64_t rows, int n_in, int n_out, void* workspace, size_t workspace_bytes, smt_stream_t stream);
+
 /* Incremental decoding (TransformerLM.sample(causal=True)): one new token per step against a key/value cache.  fp32, eval
  * mode (no dropout), head dim 32, batch 1..32.  What changes from step to step -- the position, the tokens, the uniforms --
  * lives in device memory, so a step is a fixed sequence of launches with fixed arguments.  Like the dropout keys above,

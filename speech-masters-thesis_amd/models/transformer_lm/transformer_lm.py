@@ -2,7 +2,8 @@
 
 Same constructor keys, parameter names (a reference state_dict loads as is), ``forward`` / ``sample`` /
 ``reconstruct`` / ``load_vqvae`` surface and loss definition as the reference, which builds the stack from
-``torch.nn.TransformerEncoder``.  Here a layer is five library GEMMs with everything between them in the HIP kernels
+``torch.nn.TransformerEncoder``.  Here a layer is its dense projections (``smt_amd.lm.linear``: library GEMMs in fp32, or with
+``model.compute_dtype: bf16`` the native bf16-operand GEMMs of csrc/lm_linear.hip) with everything between them in the HIP kernels
 of csrc/lm.hip (attention core, add + dropout + LayerNorm, bias + ReLU + dropout, embedding, the three losses); activations
 are batch-major [B, L, d] instead of the reference's [L, B, d].  Dropout uses the counter-based generator keyed by
 (step counter, site): site 0 = positional-encoding dropout, 1 + 4 i + {0, 1, 2, 3} = layer i's attention-weight,
@@ -18,6 +19,9 @@ import torch.nn.functional as F
 
 from models.base import TokenToWaveformModel
 from smt_amd import lm as K
+from smt_amd import packing
+
+COMPUTE_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
 
 
 class PositionalEncoding(nn.Module):
@@ -54,8 +58,9 @@ class _SelfAttention(nn.Module):
 class _EncoderLayer(nn.Module):
     """Post-norm encoder layer with nn.TransformerEncoderLayer's parameter names."""
 
-    def __init__(self, d_model, nhead, dim_feedforward, dropout, layer_norm_eps=1e-5):
+    def __init__(self, d_model, nhead, dim_feedforward, dropout, layer_norm_eps=1e-5, compute_dtype=torch.float32):
         super().__init__()
+        self.compute_dtype = compute_dtype      # of the four projections' operands (smt_amd.lm.linear)
         self.self_attn = _SelfAttention(d_model, nhead)
         self.linear1 = nn.Linear(d_model, dim_feedforward)
         self.linear2 = nn.Linear(dim_feedforward, d_model)
@@ -64,14 +69,14 @@ class _EncoderLayer(nn.Module):
         self.p = dropout
 
     def forward(self, x, lens, causal, seed, site0, kd=None):
-        sa, tr, p = self.self_attn, self.training, self.p
-        qkv = F.linear(x, sa.in_proj_weight, sa.in_proj_bias)
+        sa, tr, p, cd = self.self_attn, self.training, self.p, self.compute_dtype
+        qkv = K.linear(x, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=cd)
         ctx = K.attention(qkv, lens, sa.num_heads, causal, K.Drop(p, tr, seed, site0, kd))
-        a = F.linear(ctx, sa.out_proj.weight)                      # its bias is added (and differentiated) inside add_layer_norm
+        a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)    # its bias is added (and differentiated) inside add_layer_norm
         x = K.add_layer_norm(x, a, self.norm1.weight, self.norm1.bias, self.norm1.eps, K.Drop(p, tr, seed, site0 + 1, kd),
                              h_bias=sa.out_proj.bias)
-        f = K.bias_relu_dropout_(F.linear(x, self.linear1.weight), self.linear1.bias, K.Drop(p, tr, seed, site0 + 2, kd))
-        f = F.linear(f, self.linear2.weight)
+        f = K.bias_relu_dropout_(K.linear(x, self.linear1.weight, compute_dtype=cd), self.linear1.bias, K.Drop(p, tr, seed, site0 + 2, kd))
+        f = K.linear(f, self.linear2.weight, compute_dtype=cd)
         return K.add_layer_norm(x, f, self.norm2.weight, self.norm2.bias, self.norm2.eps, K.Drop(p, tr, seed, site0 + 3, kd),
                                 h_bias=self.linear2.bias)
 
@@ -79,16 +84,16 @@ class _EncoderLayer(nn.Module):
         """Eval-mode `forward` over a prompt x [B, P, d] (causal, no lengths, no dropout) that also writes the P key / value
         rows into the decoding cache; the last layer stops there (nothing reads its output: the next decoding step attends
         to the cache only) and returns None."""
-        sa = self.self_attn
-        qkv = F.linear(x, sa.in_proj_weight, sa.in_proj_bias)
+        sa, cd = self.self_attn, self.compute_dtype
+        qkv = K.linear(x, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=cd)
         K.decode_prefill_kv(qkv, k_cache, v_cache)
         if last:
             return None
         ctx = K.attention(qkv, None, sa.num_heads, True)
-        a = F.linear(ctx, sa.out_proj.weight)
+        a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)
         x = K.add_layer_norm(x, a, self.norm1.weight, self.norm1.bias, self.norm1.eps, h_bias=sa.out_proj.bias)
-        f = K.bias_relu_dropout_(F.linear(x, self.linear1.weight), self.linear1.bias)
-        f = F.linear(f, self.linear2.weight)
+        f = K.bias_relu_dropout_(K.linear(x, self.linear1.weight, compute_dtype=cd), self.linear1.bias)
+        f = K.linear(f, self.linear2.weight, compute_dtype=cd)
         return K.add_layer_norm(x, f, self.norm2.weight, self.norm2.bias, self.norm2.eps, h_bias=self.linear2.bias)
 
 
@@ -114,11 +119,21 @@ class TransformerLM(TokenToWaveformModel):
         assert m.embed_dim == m.d_model, "the embedding feeds the encoder directly"
         if m.get("norm_first", False) or m.get("activation", "relu") != "relu":
             raise ValueError("native TransformerLM path: post-norm layers with ReLU (the reference's construction)")
+        # operands of the six dense projections: fp32 = library GEMMs, bf16 = csrc/lm_linear.hip (everything else stays fp32,
+        # the incremental decoding path included: it reads the fp32 master weights)
+        name = m.get("compute_dtype", "fp32")
+        if name not in COMPUTE_DTYPES:
+            raise ValueError(f"model.compute_dtype must be fp32 or bf16 (got {name!r})")
+        self.compute_dtype = COMPUTE_DTYPES[name]
+        if self.compute_dtype == torch.bfloat16:
+            for key, mult in (("d_model", 32), ("dim_feedforward", 32), ("vocab_size", 16)):
+                if m[key] % mult:
+                    raise ValueError(f"model.compute_dtype bf16: {key}={m[key]} must be a multiple of {mult} (the GEMM kernels' limit)")
         self.d_model = m.d_model
         self.embedding = nn.Embedding(m.vocab_size + TransformerLM.OFFSET, m.embed_dim, padding_idx=TransformerLM.PAD)
         self.pos_encoding = PositionalEncoding(m.d_model, m.dropout, m.max_len)
         # the reference's layers keep nn.TransformerEncoderLayer's default eps; only the final norm takes the config's
-        layer = _EncoderLayer(m.d_model, m.nhead, m.dim_feedforward, m.dropout)
+        layer = _EncoderLayer(m.d_model, m.nhead, m.dim_feedforward, m.dropout, compute_dtype=self.compute_dtype)
         self.transformer = _Encoder(layer, m.num_layers, nn.LayerNorm(m.d_model, eps=float(m.layer_norm_eps)))
         self.classifier = nn.Linear(m.d_model, m.vocab_size)
         self.vqvae = TransformerLM.load_vqvae(m.vqvae.log_dir, m.vqvae.ckpt_num)
@@ -177,6 +192,7 @@ class TransformerLM(TokenToWaveformModel):
             keep_t = torch.arange(y.shape[1], device=y.device)[None, :] < y_lens[:, None]
         return (y * keep_t).float()
 
+    @packing.forward_scope
     def logits(self, x, lens, causal=True):
         """tokens [B, L] int64 (+ int32 lengths or None) -> next-token logits [B, L, vocab]."""
         seed, tr, kd = self._drop_seed, self.training, self._keys_dev
@@ -186,8 +202,9 @@ class TransformerLM(TokenToWaveformModel):
             h = layer(h, lens, causal, seed, 1 + 4 * i, kd)
         norm = self.transformer.norm
         h = K.add_layer_norm(h, None, norm.weight, norm.bias, norm.eps)
-        return F.linear(h, self.classifier.weight, self.classifier.bias)
+        return K.linear(h, self.classifier.weight, self.classifier.bias, compute_dtype=self.compute_dtype)
 
+    @packing.forward_scope
     def forward(self, x, x_lengths, y, y_lengths, speaker=None):
         l = x.shape[1]
         lens = x_lengths.to(device=x.device, dtype=torch.int32)

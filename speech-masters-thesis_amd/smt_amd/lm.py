@@ -1,16 +1,20 @@
 """Autograd bindings of the TransformerLM kernels (csrc/lm.hip, include/smt_hip.h "TransformerLM").
 
 Everything between the dense projections of the reference's nn.TransformerEncoder stack
-(models/transformer_lm/transformer_lm.py:54-66) runs in these kernels; the projections themselves are library GEMMs
-(torch.nn.functional.linear -> hipBLASLt).  Activations are [batch, len, dim] fp32; dropout masks come from the
+(models/transformer_lm/transformer_lm.py:54-66) runs in these kernels; the projections themselves go through ``linear``
+below: library GEMMs (torch.nn.functional.linear -> hipBLASLt) in fp32, csrc/lm_linear.hip with bf16 operands.  Activations are [batch, len, dim] fp32; dropout masks come from the
 counter-based generator (smt_hip.h "dropout") keyed per (step seed, site), so backward recomputes them instead of
 storing a mask per site.
 """
 import math
 
+import ctypes
+
 import torch
+import torch.nn.functional as F
 
 from . import native as N
+from . import packing
 from . import profiler
 from .convops import dropout_key
 
@@ -324,6 +328,99 @@ def mmi_loss(logits, target):
     rank's own rows under data parallelism, as in the reference).  No scored row: loss and accuracy nan."""
     assert target.dtype == torch.int64
     return _MMILoss.apply(logits, target)
+
+
+# ------------------------------------------------------------------------------------------------ dense projections
+# csrc/lm_linear.hip, include/smt_hip.h "The dense projections with bf16 operands".
+def _rows(t, width):
+    """(tensor whose storage the kernel reads, row pitch in elements) of t [..., width]: t itself when its last axis is dense,
+    its leading axes collapse to one row index, and pitch and address suit the kernels' 16-byte accesses (a column slice of a
+    wider contiguous tensor does); a contiguous copy otherwise."""
+    if t.dim() >= 2 and t.stride(-1) == 1 and t.numel() > 0:
+        pitch = t.stride(-2)
+        ok = pitch >= width and pitch % 4 == 0 and t.data_ptr() % 16 == 0
+        for i in range(t.dim() - 2):
+            ok = ok and (t.shape[i] == 1 or t.stride(i) == t.stride(i + 1) * t.shape[i + 1])
+        if ok:
+            return t, pitch
+    return t.contiguous(), width
+
+
+def _addr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _packed_bf16(weight, transposed):
+    """The bf16 operand copy of weight [n_out, n_in]: as it stands (forward) or as [n_in][n_out] (data gradient).  A Parameter's
+    copy lives in the pack cache and is refreshed once per optimizer step with all the others (smt_amd.packing)."""
+    n_out, n_in = weight.shape
+    if not weight.is_contiguous():
+        weight = weight.contiguous()
+    if transposed:
+        return packing.pack([packing.Part.dense(weight, n_in, n_out, 1, n_in, 1, (0,))], torch.bfloat16, (1, n_in, n_out))
+    return packing.pack([packing.Part.dense(weight, n_out, n_in, n_in, 1, 1, (0,))], torch.bfloat16, (1, n_out, n_in))
+
+
+class _LinearBF16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        n_out, n_in = weight.shape
+        assert x.shape[-1] == n_in and (bias is None or bias.shape == (n_out,))
+        for t in (x, weight, bias):
+            assert t is None or (t.dtype == torch.float32 and t.is_cuda), "lm.linear in bf16 takes fp32 device tensors"
+        xs, ld_x = _rows(x, n_in)
+        rows = x.numel() // n_in
+        y = torch.empty(*x.shape[:-1], n_out, device=x.device, dtype=torch.float32)
+        ctx.save_for_backward(x, weight)
+        ctx.with_bias = bias is not None
+        if rows == 0:
+            return y
+        wp = _packed_bf16(weight, False)
+        with profiler.region("lm_linear_fwd", flops=2 * rows * n_in * n_out, bound="mfma", dtype="bf16"):
+            N.check(N.lib().smt_lm_linear_fwd(_addr(xs), ld_x, N.ptr(wp), N.ptr(None if bias is None else bias.contiguous()), N.ptr(y),
+                                              n_out, rows, n_in, n_out, N.stream_ptr()), "smt_lm_linear_fwd")
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        n_out, n_in = weight.shape
+        rows = x.numel() // n_in
+        lib = N.lib()
+        if rows == 0:                                                   # no row: an empty dx, the sums over nothing
+            return (torch.empty_like(x), torch.zeros_like(weight),
+                    torch.zeros(n_out, device=x.device, dtype=torch.float32) if ctx.with_bias else None)
+        dys, ld_dy = _rows(dy, n_out)
+        dx = dweight = dbias = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(*x.shape[:-1], n_in, device=x.device, dtype=torch.float32)
+            wt = _packed_bf16(weight, True)
+            with profiler.region("lm_linear_dgrad", flops=2 * rows * n_in * n_out, bound="mfma", dtype="bf16"):
+                N.check(lib.smt_lm_linear_dgrad(_addr(dys), ld_dy, N.ptr(wt), N.ptr(dx), n_in, rows, n_in, n_out, N.stream_ptr()),
+                        "smt_lm_linear_dgrad")
+        if ctx.needs_input_grad[1] or (ctx.with_bias and ctx.needs_input_grad[2]):
+            xs, ld_x = _rows(x, n_in)
+            dweight = torch.empty(n_out, n_in, device=x.device, dtype=torch.float32)
+            dbias = torch.empty(n_out, device=x.device, dtype=torch.float32) if ctx.with_bias else None
+            ws_bytes = lib.smt_lm_linear_wgrad_workspace_bytes(rows, n_in, n_out)
+            ws = N.workspace.get(max(int(ws_bytes), 16), x.device)      # consumed inside this call
+            with profiler.region("lm_linear_wgrad", flops=2 * rows * n_in * n_out, bound="mfma", dtype="bf16"):
+                N.check(lib.smt_lm_linear_wgrad(_addr(xs), ld_x, _addr(dys), ld_dy, N.ptr(dweight), N.ptr(dbias), rows, n_in, n_out,
+                                                N.ptr(ws), ws.numel(), N.stream_ptr()), "smt_lm_linear_wgrad")
+        return dx, dweight, dbias
+
+
+def linear(x, weight, bias=None, *, compute_dtype=torch.float32):
+    """x [..., n_in] @ weight [n_out, n_in]^T (+ bias).  compute_dtype fp32: torch.nn.functional.linear (the library GEMM), the
+    very call the model made before it had a choice.  bf16: the native GEMMs of csrc/lm_linear.hip -- x, dy and the weight
+    are rounded to bf16 as operands, sums and the bias add are fp32, every tensor in memory stays fp32; n_in a multiple of 32,
+    n_out of 16.  x is read in place when its last axis is dense and its leading axes are contiguous (a column slice of a
+    wider tensor is); backward keeps x and the weight, as F.linear does."""
+    if compute_dtype == torch.float32:
+        return F.linear(x, weight, bias)
+    if compute_dtype != torch.bfloat16:
+        raise ValueError(f"lm.linear: compute_dtype must be torch.float32 or torch.bfloat16 (got {compute_dtype!r})")
+    return _LinearBF16.apply(x, weight, bias)
 
 
 # ------------------------------------------------------------------------------------------------ incremental decoding

@@ -135,6 +135,10 @@ _SIGNATURES = {
     "smt_lm_mmi_workspace_bytes": (c_size, [c_i64, c_int]),
     "smt_lm_mmi_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_size, c_ptr]),
     "smt_lm_mmi_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_ptr]),
+    "smt_lm_linear_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr]),
+    "smt_lm_linear_dgrad": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr]),
+    "smt_lm_linear_wgrad_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
+    "smt_lm_linear_wgrad": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_size, c_ptr]),
     "smt_lm_decode_embed": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_f32, c_int, c_ptr, c_ptr]),
     "smt_lm_decode_linear": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "smt_lm_decode_attention_workspace_bytes": (c_size, [c_int, c_int, c_int]),

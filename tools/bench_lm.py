@@ -21,7 +21,7 @@ import torch  # noqa: E402
 
 def build(tmp, precision="fp32", device="cuda:0"):
     """(model, optimizer, scheduler) of the reference configuration around a throw-away VQ-VAE run directory.  fp32 is the
-    only precision (bf16 projections were measured and dropped)."""
+    only precision of this tool (tools/bench_lm_linear.py measures `model.compute_dtype: bf16`)."""
     assert precision == "fp32"
     from models.transformer_lm.transformer_lm import TransformerLM
     from utils import config as C
