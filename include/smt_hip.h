@@ -617,6 +617,37 @@ int smt_lm_add_ln_bwd(const float* x, const float* h, const float* h_bias, const
                       const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, void* workspace,
                       size_t workspace_bytes, smt_stream_t stream);
 
+/* The residual step of a pre-norm stack (TransformerEncoderLayer, norm_first = True), where every residual add is followed
+ * by a LayerNorm -- the same layer's norm2, the next layer's norm1 or the encoder's final norm:
+ *   s = x + dropout(h + h_bias)              the new residual stream [rows, dim], stored
+ *   y = LayerNorm(s) * gamma + beta          the input of the next projection;  stats [rows, 2] = (mean, rstd) of s
+ * x and h are both required; h_bias, the dropout index, the key pair and the dim set 64 * {1,2,3,4,8,12,16,32} are those of
+ * smt_lm_add_ln_*.  s and y alias neither an input nor each other.
+ * bwd takes two incoming gradients, either NULL (= zero): ds of the stream (from everything downstream of it) and dy of the
+ * normed output.  With xhat = (s - mean) * rstd recomputed from the stored s (neither x nor h is read) and g = dy * gamma:
+ *   dpre = ds + rstd * (g - mean(g) - xhat * mean(g * xhat));   dx = dpre;   dh = dpre * keep      (dx / dh may be NULL)
+ *   dparams [3, dim] = dgamma, dbeta, dh_bias (column sums of dh): per-workgroup partials merged in a fixed order, no float
+ *   atomics -- equal inputs give equal bits.
+ * rows = 0: no launch, bwd zeroes dparams.  A dim outside the built set is an argument error named by smt_last_error. */
+int smt_lm_res_ln_fwd(const float* x, const float* h, const float* h_bias, const float* gamma, const float* beta, float* s,
+                      float* y, float* stats, int64_t rows, int dim, float eps, uint32_t drop_key, const uint32_t* drop_key_dev,
+                      uint32_t drop_thresh16, float drop_scale, smt_stream_t stream);
+size_t smt_lm_res_ln_bwd_workspace_bytes(int64_t rows, int dim);
+int smt_lm_res_ln_bwd(const float* s, const float* ds, const float* dy, const float* gamma, const float* stats, float* dx,
+                      float* dh, float* dparams, int64_t rows, int dim, uint32_t drop_key, const uint32_t* drop_key_dev,
+                      uint32_t drop_thresh16, float drop_scale, void* workspace, size_t workspace_bytes, smt_stream_t stream);
+
+/* a = dropout(gelu(h + bias)), gelu(u) = 0.5 u (1 + erf(u / sqrt 2)): the exact form (activation = "gelu"), not the tanh
+ * approximation.  Not in place (a != h): h, the bias-free output of linear1, is kept for the backward, which recomputes
+ * u = h + bias and gives dh = da * keep * (Phi(u) + u phi(u)) (dh aliases neither h nor da) and dbias [dim] = its column
+ * sums in a fixed order.  Element index, key pair and rows = 0 behaviour as smt_lm_bias_relu_*. */
+int smt_lm_bias_gelu_fwd(const float* h, const float* bias, float* a, int64_t rows, int dim, uint32_t drop_key,
+                         const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream);
+size_t smt_lm_bias_gelu_bwd_workspace_bytes(int64_t rows, int dim);
+int smt_lm_bias_gelu_bwd(const float* h, const float* bias, const float* da, float* dh, float* dbias, int64_t rows, int dim,
+                         uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, void* workspace,
+                         size_t workspace_bytes, smt_stream_t stream);
+
 /* h <- dropout(relu(h + bias)) in place (linear1 -> activation -> dropout of the feed-forward).  bwd: dh = da * keep *
  * [a != 0] (a = the forward's result; dh may alias da), dbias [dim] = its column sums in a fixed order. */
 int smt_lm_bias_relu_fwd(float* h, const float* bias, int64_t rows, int dim, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16,
@@ -709,9 +740,10 @@ int smt_lm_linear_wgrad(const float* x, int64_t ld_x, const float* dy, int64_t l
 int smt_lm_decode_embed(const int64_t* tokens, const float* emb, const float* pe, float* out, int batch, int tok_len, int dim,
                         int vocab_rows, int pe_rows, float mul, int pos, const int* pos_dev, smt_stream_t stream);
 
-/* out [batch, out_dim] = x [batch, in_dim] . w [out_dim, in_dim]^T (+ bias [out_dim] if non-NULL) (ReLU if relu != 0): the
- * weight matrix (an nn.Linear weight as is) is streamed once.  in_dim % 64 == 0, out_dim >= 1; fp32 products and sums. */
-int smt_lm_decode_linear(const float* x, const float* w, const float* bias, float* out, int batch, int in_dim, int out_dim, int relu,
+/* out [batch, out_dim] = act(x [batch, in_dim] . w [out_dim, in_dim]^T (+ bias [out_dim] if non-NULL)), act: 0 none, 1 ReLU,
+ * 2 exact GELU (0.5 u (1 + erf(u / sqrt 2))); any other value is an argument error.  The weight matrix (an nn.Linear weight
+ * as is) is streamed once.  in_dim % 64 == 0, out_dim >= 1; fp32 products and sums. */
+int smt_lm_decode_linear(const float* x, const float* w, const float* bias, float* out, int batch, int in_dim, int out_dim, int act,
                          smt_stream_t stream);
 
 /* One layer's attention for the token at `pos`: qkv [batch, 3*heads*32] (q | k | v as in_proj produces them); the k and v

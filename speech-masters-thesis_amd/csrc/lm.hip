@@ -7,6 +7,8 @@
 //   lm_attention    softmax(Q K^T / sqrt(dh) + causal + key-padding mask), dropout, . V        (nn.MultiheadAttention)
 //   lm_add_ln       LayerNorm(x + dropout(h))                                                   (TransformerEncoderLayer, post-norm)
 //   lm_bias_relu    dropout(relu(h + b))  in place                                              (linear1 -> activation -> dropout)
+//   lm_res_ln       s = x + dropout(h), y = LayerNorm(s): a residual add and the NEXT norm     (TransformerEncoderLayer, norm_first)
+//   lm_bias_gelu    dropout(gelu(h + b)), the exact erf form, out of place                      (activation = "gelu")
 //   lm_ce           masked mean cross-entropy + accuracy over the next-token logits              (transformer_lm.py:121-128)
 //   lm_focal/lm_mmi the other two losses of the config (loss_type focal | mmi), same conventions as lm_ce     (losses.py:8-103)
 //
@@ -425,13 +427,116 @@ __global__ __launch_bounds__(256) void lm_add_ln_bwd_kernel(const float* __restr
     part[(size_t)blockIdx.x * 3 * C + c] = a;
   }
 }
-#define LM_LN_DISPATCH(dim, CALL)                                                       \
+#define LM_LN_DISPATCH_AS(name, dim, CALL)                                              \
   switch ((dim) / 64) {                                                                 \
     case 1: CALL(1); break;  case 2: CALL(2); break;  case 3: CALL(3); break;           \
     case 4: CALL(4); break;  case 8: CALL(8); break;  case 12: CALL(12); break;         \
     case 16: CALL(16); break; case 32: CALL(32); break;                                 \
-    default: SMT_CHECK_ARG(false, "add_ln: dim %d not built (64 x {1,2,3,4,8,12,16,32})", (int)(dim)); \
+    default: SMT_CHECK_ARG(false, name ": dim %d not built (64 x {1,2,3,4,8,12,16,32})", (int)(dim)); \
   }
+#define LM_LN_DISPATCH(dim, CALL) LM_LN_DISPATCH_AS("add_ln", dim, CALL)
+
+// ------------------------------------------------------------------------------------------------ residual add + next LayerNorm
+// The pre-norm stack's residual step: s = x + dropout(h + hbias) is the new stream (stored: the next residual adds to it
+// and the backward recomputes xhat from it), y = LN(s) * gamma + beta the input of the next projection.  The layout, the
+// dim set and the dropout index are lm_add_ln_fwd_kernel's.
+template <int PER>
+__global__ __launch_bounds__(256) void lm_res_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ hh,
+                                                            const float* __restrict__ hbias,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float* __restrict__ sout, float* __restrict__ y,
+                                                            float* __restrict__ stats, long long rows, float eps, unsigned key,
+                                                            const unsigned* __restrict__ key_dev, unsigned thr, float dscale) {
+  if (key_dev) key = *key_dev;                                // device-resident key (graph replay): overrides the by-value one
+  constexpr int C = PER * 64;
+  const int lane = threadIdx.x & 63;
+  const long long row = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  if (row >= rows) return;
+  float v[PER];
+  float s = 0.f;
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const long long e = row * C + lane + 64 * q;
+    const float hb = hbias ? hbias[lane + 64 * q] : 0.f;
+    const float a = x[e] + (hh[e] + hb) * lm_keep((unsigned long long)e, key, thr, dscale);
+    sout[e] = a;
+    v[q] = a; s += a;
+  }
+  const float mean = wave_sum(s) / (float)C;
+  float s2 = 0.f;
+#pragma unroll
+  for (int q = 0; q < PER; ++q) { const float dlt = v[q] - mean; s2 = fmaf(dlt, dlt, s2); }
+  const float rstd = rsqrtf(wave_sum(s2) / (float)C + eps);
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    const int c = lane + 64 * q;
+    y[row * C + c] = (v[q] - mean) * rstd * gamma[c] + beta[c];
+  }
+  if (lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
+}
+// Two incoming gradients, either NULL (= zero): ds of the stream, dy of the normed output.  xhat = (s - mean) rstd from the
+// stored stream (neither x nor h is read); g = dy gamma; dpre = ds + rstd (g - mean(g) - xhat mean(g xhat)); dx = dpre,
+// dh = dpre * mask; the dgamma / dbeta / dhbias partials per workgroup as in lm_add_ln_bwd_kernel -> part [nwg][3][C]
+template <int PER>
+__global__ __launch_bounds__(256) void lm_res_ln_bwd_kernel(const float* __restrict__ sin, const float* __restrict__ ds,
+                                                            const float* __restrict__ dy, const float* __restrict__ gamma,
+                                                            const float* __restrict__ stats, float* __restrict__ dx,
+                                                            float* __restrict__ dh, float* __restrict__ part, long long rows,
+                                                            unsigned key, const unsigned* __restrict__ key_dev, unsigned thr, float dscale) {
+  if (key_dev) key = *key_dev;                                // device-resident key (graph replay): overrides the by-value one
+  constexpr int C = PER * 64;
+  extern __shared__ float red[];                              // [4][3][C]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float pg[PER], pb[PER], ph[PER], gm[PER];
+#pragma unroll
+  for (int q = 0; q < PER; ++q) { pg[q] = 0.f; pb[q] = 0.f; ph[q] = 0.f; gm[q] = gamma[lane + 64 * q]; }
+  const long long row = (long long)blockIdx.x * LN_RPB + wave;
+  if (row < rows) {                                           // wave-uniform
+    float dp[PER];
+    if (dy) {
+      float xh[PER], g[PER];
+      float sg = 0.f, sgx = 0.f;
+      const float mean = stats[2 * row], rstd = stats[2 * row + 1];
+#pragma unroll
+      for (int q = 0; q < PER; ++q) {
+        const long long e = row * C + lane + 64 * q;
+        const float dyv = dy[e];
+        const float xv = (sin[e] - mean) * rstd, gv = dyv * gm[q];
+        xh[q] = xv; g[q] = gv; sg += gv; sgx = fmaf(gv, xv, sgx);
+        pg[q] = dyv * xv; pb[q] = dyv;
+      }
+      sg = wave_sum(sg) / (float)C; sgx = wave_sum(sgx) / (float)C;
+#pragma unroll
+      for (int q = 0; q < PER; ++q) dp[q] = rstd * (g[q] - sg - xh[q] * sgx);
+    } else {
+#pragma unroll
+      for (int q = 0; q < PER; ++q) dp[q] = 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const long long e = row * C + lane + 64 * q;
+      const float dpre = ds ? ds[e] + dp[q] : dp[q];
+      if (dx) dx[e] = dpre;
+      const float dhv = dpre * lm_keep((unsigned long long)e, key, thr, dscale);
+      if (dh) dh[e] = dhv;
+      ph[q] = dhv;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < PER; ++q) {
+    red[(wave * 3 + 0) * C + lane + 64 * q] = pg[q];
+    red[(wave * 3 + 1) * C + lane + 64 * q] = pb[q];
+    red[(wave * 3 + 2) * C + lane + 64 * q] = ph[q];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < 3 * C; c += 256) {
+    const int plane = c / C, cc = c % C;
+    float a = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) a += red[(w * 3 + plane) * C + cc];
+    part[(size_t)blockIdx.x * 3 * C + c] = a;
+  }
+}
 // fixed-order column sums of part [n][width] -> out [width]: a workgroup takes 64 columns, its four waves a quarter of
 // the rows each; a wave keeps eight loads in flight (row r goes to accumulator r % 8) and the partial sums are combined
 // in a fixed order.
@@ -475,6 +580,55 @@ __global__ __launch_bounds__(256) void lm_bias_relu_bwd_kernel(const float* __re
       const long long e = r * C + c;
       // a = relu(.) * keep: a != 0 <=> pre-activation > 0 and kept (the derivative of both at once)
       const float g = a[e] != 0.f ? da[e] * lm_keep((unsigned long long)e, key, thr, dscale) : 0.f;
+      dh[e] = g; s += g;
+    }
+    part[(size_t)blockIdx.x * C + c] = s;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ bias + gelu + dropout
+// The exact form, gelu(u) = u Phi(u) with Phi(u) = 0.5 (1 + erf(u / sqrt 2)) (torch's activation="gelu"), not the tanh one.
+// Not in place: the derivative Phi(u) + u phi(u) needs the pre-activation, which the result does not determine.
+__device__ __forceinline__ float lm_gelu(float u) { return 0.5f * u * (1.f + erff(u * 0.70710678118654752f)); }
+__device__ __forceinline__ float lm_gelu_grad(float u) {
+  return 0.5f * (1.f + erff(u * 0.70710678118654752f)) + u * 0.39894228040143268f * expf(-0.5f * u * u);
+}
+// a = gelu(h + bias) * keep; four consecutive elements per thread when the width allows (a row is then a whole number of
+// float4s, so one column index serves the four) and the pointers are 16-byte aligned, else one
+__global__ __launch_bounds__(256) void lm_bias_gelu_fwd_kernel(const float* __restrict__ h, const float* __restrict__ bias,
+                                                               float* __restrict__ a, long long rows, int C, int vec, unsigned key,
+                                                               const unsigned* __restrict__ key_dev, unsigned thr, float dscale) {
+  if (key_dev) key = *key_dev;                                // device-resident key (graph replay): overrides the by-value one
+  const long long total = rows * C;
+  if (vec) {                                                  // C % 4 == 0 and 16-byte aligned pointers (the host's check)
+    for (long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; e < total; e += (long long)gridDim.x * 1024) {
+      const int c = (int)(e % C);
+      const float4 hv = *(const float4*)(h + e), bv = *(const float4*)(bias + c);
+      float4 o;
+      o.x = lm_gelu(hv.x + bv.x) * lm_keep((unsigned long long)e, key, thr, dscale);
+      o.y = lm_gelu(hv.y + bv.y) * lm_keep((unsigned long long)e + 1, key, thr, dscale);
+      o.z = lm_gelu(hv.z + bv.z) * lm_keep((unsigned long long)e + 2, key, thr, dscale);
+      o.w = lm_gelu(hv.w + bv.w) * lm_keep((unsigned long long)e + 3, key, thr, dscale);
+      *(float4*)(a + e) = o;
+    }
+  } else {
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256)
+      a[e] = lm_gelu(h[e] + bias[e % C]) * lm_keep((unsigned long long)e, key, thr, dscale);
+  }
+}
+// dh = da * keep * (Phi(u) + u phi(u)), u = h + bias recomputed; bias-gradient partials per workgroup row block -> part [nblk][C]
+__global__ __launch_bounds__(256) void lm_bias_gelu_bwd_kernel(const float* __restrict__ h, const float* __restrict__ bias,
+                                                               const float* __restrict__ da, float* __restrict__ dh,
+                                                               float* __restrict__ part, long long rows, int C, int rows_per_blk,
+                                                               unsigned key, const unsigned* __restrict__ key_dev, unsigned thr, float dscale) {
+  if (key_dev) key = *key_dev;                                // device-resident key (graph replay): overrides the by-value one
+  const long long r0 = (long long)blockIdx.x * rows_per_blk;
+  for (int c = blockIdx.y * 256 + threadIdx.x; c < C; c += 256 * gridDim.y) {
+    const float b = bias[c];
+    float s = 0.f;
+    for (long long r = r0; r < min(rows, r0 + rows_per_blk); ++r) {
+      const long long e = r * C + c;
+      const float g = da[e] * lm_keep((unsigned long long)e, key, thr, dscale) * lm_gelu_grad(h[e] + b);
       dh[e] = g; s += g;
     }
     part[(size_t)blockIdx.x * C + c] = s;
@@ -769,6 +923,53 @@ extern "C" int smt_lm_add_ln_bwd(const float* x, const float* h, const float* h_
   return 0;
 }
 
+extern "C" int smt_lm_res_ln_fwd(const float* x, const float* h, const float* h_bias, const float* gamma, const float* beta, float* s,
+                                 float* y, float* stats, int64_t rows, int dim, float eps, uint32_t drop_key, const uint32_t* drop_key_dev,
+                                 uint32_t drop_thresh16, float drop_scale, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (rows <= 0) return 0;
+  SMT_CHECK_ARG(x && h && gamma && beta && s && y && stats, "smt_lm_res_ln_fwd: null pointer");
+  SMT_CHECK_ARG(s != x && s != h && y != x && y != h && y != s, "smt_lm_res_ln_fwd: s and y must not alias an input or each other");
+  SMT_CHECK_ARG(dim % 64 == 0 && dim <= 2048, "smt_lm_res_ln_fwd: dim must be a multiple of 64 up to 2048 (got %d)", dim);
+#define LM_CALL(P) lm_res_ln_fwd_kernel<P><<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(x, h, h_bias, gamma, beta, s, y, stats, rows, eps, \
+                                                                                     drop_key, drop_key_dev, drop_thresh16, drop_scale)
+  LM_LN_DISPATCH_AS("res_ln", dim, LM_CALL)
+#undef LM_CALL
+  SMT_CHECK_LAUNCH("lm_res_ln_fwd");
+  return 0;
+}
+
+extern "C" size_t smt_lm_res_ln_bwd_workspace_bytes(int64_t rows, int dim) { return smt_lm_add_ln_bwd_workspace_bytes(rows, dim); }
+
+extern "C" int smt_lm_res_ln_bwd(const float* s, const float* ds, const float* dy, const float* gamma, const float* stats, float* dx,
+                                 float* dh, float* dparams, int64_t rows, int dim, uint32_t drop_key, const uint32_t* drop_key_dev,
+                                 uint32_t drop_thresh16, float drop_scale, void* workspace, size_t workspace_bytes, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(dparams, "smt_lm_res_ln_bwd: null pointer");
+  if (rows <= 0) {
+    (void)hipMemsetAsync(dparams, 0, 3 * (size_t)dim * sizeof(float), stream);
+    return 0;
+  }
+  SMT_CHECK_ARG(gamma && workspace && (!dy || (s && stats)), "smt_lm_res_ln_bwd: null pointer");
+  SMT_CHECK_ARG((!dx || (dx != ds && dx != dy && dx != s && dx != dh)) && (!dh || (dh != ds && dh != dy && dh != s)),
+                "smt_lm_res_ln_bwd: dx and dh must not alias an input or each other");
+  SMT_CHECK_ARG(dim % 64 == 0 && dim <= 2048, "smt_lm_res_ln_bwd: dim must be a multiple of 64 up to 2048 (got %d)", dim);
+  SMT_CHECK_ARG(workspace_bytes >= smt_lm_res_ln_bwd_workspace_bytes(rows, dim), "smt_lm_res_ln_bwd: workspace too small");
+  const int nblk = (int)((rows + LN_RPB - 1) / LN_RPB);
+  float* part = (float*)workspace;                           // [nblk][3][dim]: dgamma, dbeta, dh_bias partials
+  const size_t lds = 12 * (size_t)dim * sizeof(float);
+#define LM_CALL(P)                                                                                                        \
+  (void)hipFuncSetAttribute((const void*)lm_res_ln_bwd_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   \
+  lm_res_ln_bwd_kernel<P><<<nblk, 256, lds, stream>>>(s, ds, dy, gamma, stats, dx, dh, part, rows, drop_key, drop_key_dev, \
+                                                      drop_thresh16, drop_scale)
+  LM_LN_DISPATCH_AS("res_ln", dim, LM_CALL)
+#undef LM_CALL
+  SMT_CHECK_LAUNCH("lm_res_ln_bwd");
+  lm_colsum_kernel<<<(3 * dim + 63) / 64, 256, 0, stream>>>(part, dparams, nblk, 3 * dim);
+  SMT_CHECK_LAUNCH("lm_colsum");
+  return 0;
+}
+
 extern "C" int smt_lm_bias_relu_fwd(float* h, const float* bias, int64_t rows, int dim, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16,
                                     float drop_scale, smt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
@@ -792,6 +993,37 @@ extern "C" int smt_lm_bias_relu_bwd(const float* a, const float* da, float* dh, 
   const int nblk = (int)((rows + 15) / 16);
   lm_bias_relu_bwd_kernel<<<dim3(nblk, (dim + 255) / 256), 256, 0, stream>>>(a, da, dh, (float*)workspace, rows, dim, 16, drop_key, drop_key_dev, drop_thresh16, drop_scale);
   SMT_CHECK_LAUNCH("lm_bias_relu_bwd");
+  lm_colsum_kernel<<<(dim + 63) / 64, 256, 0, stream>>>((const float*)workspace, dbias, nblk, dim);
+  SMT_CHECK_LAUNCH("lm_colsum");
+  return 0;
+}
+
+extern "C" int smt_lm_bias_gelu_fwd(const float* h, const float* bias, float* a, int64_t rows, int dim, uint32_t drop_key,
+                                    const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (rows <= 0) return 0;
+  SMT_CHECK_ARG(h && bias && a && a != h && dim >= 1, "smt_lm_bias_gelu_fwd: null pointer, a aliasing h, or dim < 1");
+  const int vec = dim % 4 == 0 && (((uintptr_t)h | (uintptr_t)bias | (uintptr_t)a) & 15) == 0;
+  lm_bias_gelu_fwd_kernel<<<lm_grid(vec ? (rows * dim + 3) / 4 : rows * dim), 256, 0, stream>>>(h, bias, a, rows, dim, vec, drop_key, drop_key_dev,
+                                                                                          drop_thresh16, drop_scale);
+  SMT_CHECK_LAUNCH("lm_bias_gelu_fwd");
+  return 0;
+}
+
+extern "C" size_t smt_lm_bias_gelu_bwd_workspace_bytes(int64_t rows, int dim) { return smt_lm_bias_relu_bwd_workspace_bytes(rows, dim); }
+
+extern "C" int smt_lm_bias_gelu_bwd(const float* h, const float* bias, const float* da, float* dh, float* dbias, int64_t rows, int dim,
+                                    uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, void* workspace,
+                                    size_t workspace_bytes, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(dbias && dim >= 1, "smt_lm_bias_gelu_bwd: null pointer or dim < 1");
+  if (rows <= 0) { (void)hipMemsetAsync(dbias, 0, dim * sizeof(float), stream); return 0; }
+  SMT_CHECK_ARG(h && bias && da && dh && workspace && dh != h && dh != da, "smt_lm_bias_gelu_bwd: null pointer, or dh aliasing h / da");
+  SMT_CHECK_ARG(workspace_bytes >= smt_lm_bias_gelu_bwd_workspace_bytes(rows, dim), "smt_lm_bias_gelu_bwd: workspace too small");
+  const int nblk = (int)((rows + 15) / 16);
+  lm_bias_gelu_bwd_kernel<<<dim3(nblk, (dim + 255) / 256), 256, 0, stream>>>(h, bias, da, dh, (float*)workspace, rows, dim, 16, drop_key, drop_key_dev,
+                                                                          drop_thresh16, drop_scale);
+  SMT_CHECK_LAUNCH("lm_bias_gelu_bwd");
   lm_colsum_kernel<<<(dim + 63) / 64, 256, 0, stream>>>((const float*)workspace, dbias, nblk, dim);
   SMT_CHECK_LAUNCH("lm_colsum");
   return 0;

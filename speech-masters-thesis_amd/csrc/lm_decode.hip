@@ -71,12 +71,12 @@ __device__ __forceinline__ void dec_reduce32(float (&v)[32], int lane) {
 // split over its waves, DEC_KW elements each: a lane keeps its two x elements of every batch row in registers (2 BP) and
 // streams two elements of each of the eight weight rows -- a wave reads 512 contiguous bytes per weight row, all eight
 // loads in flight before the first product.  The 8 * BP per-lane products-of-two are summed over the lanes 32 at a
-// time (dec_reduce32), then over the waves through LDS in wave order; bias and ReLU on the way out.  Products and sums
-// are fp32 FMAs.  accumulate != 0 adds to `out` (the second and later launches of a contraction longer than DEC_KMAX).
+// time (dec_reduce32), then over the waves through LDS in wave order; bias and the activation (act: 0 none, 1 ReLU, 2 exact
+// GELU) on the way out.  Products and sums are fp32 FMAs.  accumulate != 0 adds to `out` (the second and later launches of a contraction longer than DEC_KMAX).
 template <int BP, int MAXT>
 __global__ __launch_bounds__(MAXT) void lm_decode_linear_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                                 const float* __restrict__ bias, float* out, int B, int N, int kc,
-                                                                int ldx, int ldw, int relu, int accumulate) {
+                                                                int ldx, int ldw, int act, int accumulate) {
   constexpr int R = 32 / BP;                                  // weight rows per group of 32 values
   __shared__ float red[MAXT / 64][DEC_ROWS * BP];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(MAXT) void lm_decode_linear_kernel(const float* __r
       float* dst = out + (size_t)b * N + n;
       if (accumulate) s += *dst;
       if (bias) s += bias[n];
-      *dst = relu ? fmaxf(s, 0.f) : s;
+      *dst = act == 1 ? fmaxf(s, 0.f) : act == 2 ? 0.5f * s * (1.f + erff(s * 0.70710678118654752f)) : s;
     }
   }
 }
@@ -429,13 +429,13 @@ __global__ void lm_decode_advance_kernel(int* pos_dev) {
 static int dec_splits(int l_max) { return (l_max + DEC_CHUNK - 1) / DEC_CHUNK; }
 
 template <int BP>
-static void dec_linear_launch(const float* x, const float* w, const float* bias, float* out, int B, int N, int kc, int ld, int relu,
+static void dec_linear_launch(const float* x, const float* w, const float* bias, float* out, int B, int N, int kc, int ld, int act,
                               int accumulate, hipStream_t stream) {
   const int nw = (kc + DEC_KW - 1) / DEC_KW, grid = (N + DEC_ROWS - 1) / DEC_ROWS;
   if (nw <= 4)
-    lm_decode_linear_kernel<BP, 256><<<grid, 64 * nw, 0, stream>>>(x, w, bias, out, B, N, kc, ld, ld, relu, accumulate);
+    lm_decode_linear_kernel<BP, 256><<<grid, 64 * nw, 0, stream>>>(x, w, bias, out, B, N, kc, ld, ld, act, accumulate);
   else
-    lm_decode_linear_kernel<BP, 1024><<<grid, 64 * nw, 0, stream>>>(x, w, bias, out, B, N, kc, ld, ld, relu, accumulate);
+    lm_decode_linear_kernel<BP, 1024><<<grid, 64 * nw, 0, stream>>>(x, w, bias, out, B, N, kc, ld, ld, act, accumulate);
 }
 
 }  // namespace smt
@@ -456,16 +456,17 @@ extern "C" int smt_lm_decode_embed(const int64_t* tokens, const float* emb, cons
 }
 
 extern "C" int smt_lm_decode_linear(const float* x, const float* w, const float* bias, float* out, int batch, int in_dim, int out_dim,
-                                    int relu, smt_stream_t stream_) {
+                                    int act, smt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SMT_CHECK_ARG(x && w && out, "smt_lm_decode_linear: null pointer");
   SMT_CHECK_ARG(batch >= 1 && batch <= 32, "smt_lm_decode_linear: batch must be 1..32 (got %d)", batch);
   SMT_CHECK_ARG(in_dim >= 64 && in_dim % 64 == 0 && out_dim >= 1, "smt_lm_decode_linear: in_dim must be a positive multiple of 64, out_dim >= 1 (got %d, %d)",
                 in_dim, out_dim);
+  SMT_CHECK_ARG(act >= 0 && act <= 2, "smt_lm_decode_linear: act must be 0 (none), 1 (ReLU) or 2 (GELU) (got %d)", act);
   for (int k0 = 0; k0 < in_dim; k0 += DEC_KMAX) {
     const int kc = std::min(DEC_KMAX, in_dim - k0), last = k0 + kc == in_dim;
     const float* bl = last ? bias : nullptr;
-    const int rl = last ? relu : 0, acc = k0 > 0;
+    const int rl = last ? act : 0, acc = k0 > 0;
     if (batch <= 4) dec_linear_launch<4>(x + k0, w + k0, bl, out, batch, out_dim, kc, in_dim, rl, acc, stream);
     else if (batch <= 8) dec_linear_launch<8>(x + k0, w + k0, bl, out, batch, out_dim, kc, in_dim, rl, acc, stream);
     else if (batch <= 16) dec_linear_launch<16>(x + k0, w + k0, bl, out, batch, out_dim, kc, in_dim, rl, acc, stream);

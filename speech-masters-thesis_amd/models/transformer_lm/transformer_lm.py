@@ -5,9 +5,11 @@ Same constructor keys, parameter names (a reference state_dict loads as is), ``f
 ``torch.nn.TransformerEncoder``.  Here a layer is its dense projections (``smt_amd.lm.linear``: library GEMMs in fp32, or with
 ``model.compute_dtype: bf16`` the native bf16-operand GEMMs of csrc/lm_linear.hip) with everything between them in the HIP kernels
 of csrc/lm.hip (attention core, add + dropout + LayerNorm, bias + ReLU + dropout, embedding, the three losses); activations
-are batch-major [B, L, d] instead of the reference's [L, B, d].  Dropout uses the counter-based generator keyed by
-(step counter, site): site 0 = positional-encoding dropout, 1 + 4 i + {0, 1, 2, 3} = layer i's attention-weight,
-attention-output, feed-forward-inner and feed-forward-output dropouts.
+are batch-major [B, L, d] instead of the reference's [L, B, d].  ``model.norm_first`` and ``model.activation`` are
+nn.TransformerEncoderLayer's arguments of those names: pre-norm layers run their residual adds fused with the NEXT LayerNorm
+(``smt_amd.lm.residual_layer_norm``), ``gelu`` is the exact form (``smt_amd.lm.bias_gelu_dropout``).  Dropout uses the
+counter-based generator keyed by (step counter, site): site 0 = positional-encoding dropout, 1 + 4 i + {0, 1, 2, 3} = layer
+i's attention-weight, attention-output, feed-forward-inner and feed-forward-output dropouts.
 """
 import copy
 import math
@@ -22,6 +24,7 @@ from smt_amd import lm as K
 from smt_amd import packing
 
 COMPUTE_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+ACTIVATIONS = {"relu": K.ACT_RELU, "gelu": K.ACT_GELU}
 
 
 class PositionalEncoding(nn.Module):
@@ -56,17 +59,26 @@ class _SelfAttention(nn.Module):
 
 
 class _EncoderLayer(nn.Module):
-    """Post-norm encoder layer with nn.TransformerEncoderLayer's parameter names."""
+    """Encoder layer with nn.TransformerEncoderLayer's parameter names; post-norm (`forward`, `prefill`) or pre-norm
+    (`forward_pre`, `prefill_pre`: the encoder calls the pair that matches its norm_first), ReLU or exact-GELU feed-forward."""
 
-    def __init__(self, d_model, nhead, dim_feedforward, dropout, layer_norm_eps=1e-5, compute_dtype=torch.float32):
+    def __init__(self, d_model, nhead, dim_feedforward, dropout, layer_norm_eps=1e-5, compute_dtype=torch.float32, activation="relu"):
         super().__init__()
         self.compute_dtype = compute_dtype      # of the four projections' operands (smt_amd.lm.linear)
+        self.act = ACTIVATIONS[activation]
         self.self_attn = _SelfAttention(d_model, nhead)
         self.linear1 = nn.Linear(d_model, dim_feedforward)
         self.linear2 = nn.Linear(dim_feedforward, d_model)
         self.norm1 = nn.LayerNorm(d_model, eps=layer_norm_eps)
         self.norm2 = nn.LayerNorm(d_model, eps=layer_norm_eps)
         self.p = dropout
+
+    def _ff_inner(self, x, drop=K.NO_DROP):
+        """dropout(activation(linear1(x))): the bias, the activation and the dropout in one kernel after the bias-free GEMM."""
+        h = K.linear(x, self.linear1.weight, compute_dtype=self.compute_dtype)
+        if self.act == K.ACT_GELU:
+            return K.bias_gelu_dropout(h, self.linear1.bias, drop)
+        return K.bias_relu_dropout_(h, self.linear1.bias, drop)
 
     def forward(self, x, lens, causal, seed, site0, kd=None):
         sa, tr, p, cd = self.self_attn, self.training, self.p, self.compute_dtype
@@ -75,10 +87,24 @@ class _EncoderLayer(nn.Module):
         a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)    # its bias is added (and differentiated) inside add_layer_norm
         x = K.add_layer_norm(x, a, self.norm1.weight, self.norm1.bias, self.norm1.eps, K.Drop(p, tr, seed, site0 + 1, kd),
                              h_bias=sa.out_proj.bias)
-        f = K.bias_relu_dropout_(K.linear(x, self.linear1.weight, compute_dtype=cd), self.linear1.bias, K.Drop(p, tr, seed, site0 + 2, kd))
+        f = self._ff_inner(x, K.Drop(p, tr, seed, site0 + 2, kd))
         f = K.linear(f, self.linear2.weight, compute_dtype=cd)
         return K.add_layer_norm(x, f, self.norm2.weight, self.norm2.bias, self.norm2.eps, K.Drop(p, tr, seed, site0 + 3, kd),
                                 h_bias=self.linear2.bias)
+
+    def forward_pre(self, s, y, nxt, lens, causal, seed, site0, kd=None):
+        """Pre-norm layer: s [B, L, d] is the residual stream, y = norm1(s) already formed by whoever produced s, `nxt` the
+        LayerNorm that follows this layer (the next layer's norm1 or the encoder's final norm).  Returns (s', nxt(s')): each
+        residual add runs fused with the norm after it, so a layer is the same four launches as the post-norm one."""
+        sa, tr, p, cd = self.self_attn, self.training, self.p, self.compute_dtype
+        qkv = K.linear(y, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=cd)
+        ctx = K.attention(qkv, lens, sa.num_heads, causal, K.Drop(p, tr, seed, site0, kd))
+        a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)    # its bias is added (and differentiated) inside residual_layer_norm
+        s, y = K.residual_layer_norm(s, a, self.norm2.weight, self.norm2.bias, self.norm2.eps, K.Drop(p, tr, seed, site0 + 1, kd),
+                                     h_bias=sa.out_proj.bias)
+        f = self._ff_inner(y, K.Drop(p, tr, seed, site0 + 2, kd))
+        f = K.linear(f, self.linear2.weight, compute_dtype=cd)
+        return K.residual_layer_norm(s, f, nxt.weight, nxt.bias, nxt.eps, K.Drop(p, tr, seed, site0 + 3, kd), h_bias=self.linear2.bias)
 
     def prefill(self, x, k_cache, v_cache, last):
         """Eval-mode `forward` over a prompt x [B, P, d] (causal, no lengths, no dropout) that also writes the P key / value
@@ -92,9 +118,22 @@ class _EncoderLayer(nn.Module):
         ctx = K.attention(qkv, None, sa.num_heads, True)
         a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)
         x = K.add_layer_norm(x, a, self.norm1.weight, self.norm1.bias, self.norm1.eps, h_bias=sa.out_proj.bias)
-        f = K.bias_relu_dropout_(K.linear(x, self.linear1.weight, compute_dtype=cd), self.linear1.bias)
+        f = self._ff_inner(x)
         f = K.linear(f, self.linear2.weight, compute_dtype=cd)
         return K.add_layer_norm(x, f, self.norm2.weight, self.norm2.bias, self.norm2.eps, h_bias=self.linear2.bias)
+
+    def prefill_pre(self, s, y, nxt, k_cache, v_cache, last):
+        """`prefill` of a pre-norm layer, on the (s, y) pair of `forward_pre`; returns the next pair, or None from the last layer."""
+        sa, cd = self.self_attn, self.compute_dtype
+        qkv = K.linear(y, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=cd)
+        K.decode_prefill_kv(qkv, k_cache, v_cache)
+        if last:
+            return None
+        ctx = K.attention(qkv, None, sa.num_heads, True)
+        a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)
+        s, y = K.residual_layer_norm(s, a, self.norm2.weight, self.norm2.bias, self.norm2.eps, h_bias=sa.out_proj.bias)
+        f = K.linear(self._ff_inner(y), self.linear2.weight, compute_dtype=cd)
+        return K.residual_layer_norm(s, f, nxt.weight, nxt.bias, nxt.eps, h_bias=self.linear2.bias)
 
 
 class _Encoder(nn.Module):
@@ -117,8 +156,13 @@ class TransformerLM(TokenToWaveformModel):
         super().__init__()
         m = config.model
         assert m.embed_dim == m.d_model, "the embedding feeds the encoder directly"
-        if m.get("norm_first", False) or m.get("activation", "relu") != "relu":
-            raise ValueError("native TransformerLM path: post-norm layers with ReLU (the reference's construction)")
+        # nn.TransformerEncoderLayer's arguments of the same names; absent = the reference's construction (post-norm, ReLU)
+        self.norm_first = m.get("norm_first", False)
+        if not isinstance(self.norm_first, bool):
+            raise ValueError(f"model.norm_first must be true or false (got {self.norm_first!r})")
+        activation = m.get("activation", "relu")
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"model.activation must be relu or gelu (got {activation!r})")
         # operands of the six dense projections: fp32 = library GEMMs, bf16 = csrc/lm_linear.hip (everything else stays fp32,
         # the incremental decoding path included: it reads the fp32 master weights)
         name = m.get("compute_dtype", "fp32")
@@ -133,7 +177,7 @@ class TransformerLM(TokenToWaveformModel):
         self.embedding = nn.Embedding(m.vocab_size + TransformerLM.OFFSET, m.embed_dim, padding_idx=TransformerLM.PAD)
         self.pos_encoding = PositionalEncoding(m.d_model, m.dropout, m.max_len)
         # the reference's layers keep nn.TransformerEncoderLayer's default eps; only the final norm takes the config's
-        layer = _EncoderLayer(m.d_model, m.nhead, m.dim_feedforward, m.dropout, compute_dtype=self.compute_dtype)
+        layer = _EncoderLayer(m.d_model, m.nhead, m.dim_feedforward, m.dropout, compute_dtype=self.compute_dtype, activation=activation)
         self.transformer = _Encoder(layer, m.num_layers, nn.LayerNorm(m.d_model, eps=float(m.layer_norm_eps)))
         self.classifier = nn.Linear(m.d_model, m.vocab_size)
         self.vqvae = TransformerLM.load_vqvae(m.vqvae.log_dir, m.vqvae.ckpt_num)
@@ -198,9 +242,17 @@ class TransformerLM(TokenToWaveformModel):
         seed, tr, kd = self._drop_seed, self.training, self._keys_dev
         h = K.embed(x, self.embedding.weight, self.pos_encoding.table(), K.Drop(self.pos_encoding.p, tr, seed, 0, kd),
                     TransformerLM.PAD)
-        for i, layer in enumerate(self.transformer.layers):
+        layers, norm = self.transformer.layers, self.transformer.norm
+        if self.norm_first:
+            # layer 0's norm1 is the only LayerNorm on its own; every other one runs inside the residual add before it, the
+            # final norm inside the last layer's second add
+            n1 = layers[0].norm1
+            y = K.add_layer_norm(h, None, n1.weight, n1.bias, n1.eps)
+            for i, layer in enumerate(layers):
+                h, y = layer.forward_pre(h, y, layers[i + 1].norm1 if i + 1 < len(layers) else norm, lens, causal, seed, 1 + 4 * i, kd)
+            return K.linear(y, self.classifier.weight, self.classifier.bias, compute_dtype=self.compute_dtype)
+        for i, layer in enumerate(layers):
             h = layer(h, lens, causal, seed, 1 + 4 * i, kd)
-        norm = self.transformer.norm
         h = K.add_layer_norm(h, None, norm.weight, norm.bias, norm.eps)
         return K.linear(h, self.classifier.weight, self.classifier.bias, compute_dtype=self.compute_dtype)
 
@@ -247,17 +299,38 @@ class TransformerLM(TokenToWaveformModel):
         arguments only (the position is read from st.pos_dev), no allocation, no host synchronisation."""
         pd = st.pos_dev
         K.decode_embed(st.tokens, self.embedding.weight, self.pos_encoding.table(), st.h, 0, pd)
+        if self.norm_first:
+            return self._decode_logits_pre(st)
         for i, layer in enumerate(self.transformer.layers):
             sa, n1, n2 = layer.self_attn, layer.norm1, layer.norm2
             K.decode_linear(st.h, sa.in_proj_weight, sa.in_proj_bias, st.qkv)
             K.decode_attention(st.qkv, st.kv[i, 0], st.kv[i, 1], st.ctx, st.attn_ws, 0, pd)
             K.decode_linear(st.ctx, sa.out_proj.weight, None, st.a)     # its bias goes through the LayerNorm kernel, as in forward
             K.decode_layer_norm(st.h, st.a, sa.out_proj.bias, n1.weight, n1.bias, n1.eps, st.h1, st.stats)
-            K.decode_linear(st.h1, layer.linear1.weight, layer.linear1.bias, st.f, relu=True)
+            K.decode_linear(st.h1, layer.linear1.weight, layer.linear1.bias, st.f, act=layer.act)
             K.decode_linear(st.f, layer.linear2.weight, None, st.a)
             K.decode_layer_norm(st.h1, st.a, layer.linear2.bias, n2.weight, n2.bias, n2.eps, st.h, st.stats)
         norm = self.transformer.norm
         K.decode_layer_norm(st.h, None, None, norm.weight, norm.bias, norm.eps, st.h1, st.stats)
+        K.decode_linear(st.h1, self.classifier.weight, self.classifier.bias, st.logits)
+
+    def _decode_logits_pre(self, st):
+        """`_decode_logits` after the embedding for pre-norm layers, launch for launch the post-norm sequence: the stream
+        alternates between st.h (a layer's input) and st.s (between its sub-layers), the normed rows are always st.h1."""
+        pd = st.pos_dev
+        layers, norm = self.transformer.layers, self.transformer.norm
+        n1 = layers[0].norm1
+        K.decode_layer_norm(st.h, None, None, n1.weight, n1.bias, n1.eps, st.h1, st.stats)
+        for i, layer in enumerate(layers):
+            sa, n2 = layer.self_attn, layer.norm2
+            nxt = layers[i + 1].norm1 if i + 1 < len(layers) else norm
+            K.decode_linear(st.h1, sa.in_proj_weight, sa.in_proj_bias, st.qkv)
+            K.decode_attention(st.qkv, st.kv[i, 0], st.kv[i, 1], st.ctx, st.attn_ws, 0, pd)
+            K.decode_linear(st.ctx, sa.out_proj.weight, None, st.a)     # its bias goes through the LayerNorm kernel, as in forward
+            K.decode_residual_layer_norm(st.h, st.a, sa.out_proj.bias, n2.weight, n2.bias, n2.eps, st.s, st.h1, st.stats)
+            K.decode_linear(st.h1, layer.linear1.weight, layer.linear1.bias, st.f, act=layer.act)
+            K.decode_linear(st.f, layer.linear2.weight, None, st.a)
+            K.decode_residual_layer_norm(st.s, st.a, layer.linear2.bias, nxt.weight, nxt.bias, nxt.eps, st.h, st.h1, st.stats)
         K.decode_linear(st.h1, self.classifier.weight, self.classifier.bias, st.logits)
 
     def _decode_step(self, st, sigma, top_k=None, top_p=None):
@@ -302,8 +375,15 @@ class TransformerLM(TokenToWaveformModel):
         state.codes[:, :p] = codes
         h = K.embed(state.tokens[:, :p].contiguous(), self.embedding.weight, self.pos_encoding.table(), K.NO_DROP, TransformerLM.PAD)
         layers = self.transformer.layers
-        for i, layer in enumerate(layers):
-            h = layer.prefill(h, state.kv[i, 0], state.kv[i, 1], i + 1 == len(layers))
+        if self.norm_first:
+            n1 = layers[0].norm1
+            pair = (h, K.add_layer_norm(h, None, n1.weight, n1.bias, n1.eps))
+            for i, layer in enumerate(layers):
+                last = i + 1 == len(layers)
+                pair = layer.prefill_pre(*pair, None if last else layers[i + 1].norm1, state.kv[i, 0], state.kv[i, 1], last)
+        else:
+            for i, layer in enumerate(layers):
+                h = layer.prefill(h, state.kv[i, 0], state.kv[i, 1], i + 1 == len(layers))
         state.prefill_done(p)
 
     @torch.no_grad()

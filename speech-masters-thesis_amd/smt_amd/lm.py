@@ -4,7 +4,9 @@ Everything between the dense projections of the reference's nn.TransformerEncode
 (models/transformer_lm/transformer_lm.py:54-66) runs in these kernels; the projections themselves go through ``linear``
 below: library GEMMs (torch.nn.functional.linear -> hipBLASLt) in fp32, csrc/lm_linear.hip with bf16 operands.  Activations are [batch, len, dim] fp32; dropout masks come from the
 counter-based generator (smt_hip.h "dropout") keyed per (step seed, site), so backward recomputes them instead of
-storing a mask per site.
+storing a mask per site.  The post-norm ReLU stack of the reference uses ``add_layer_norm`` and ``bias_relu_dropout_``;
+``residual_layer_norm`` (a residual add fused with the LayerNorm that follows it) and ``bias_gelu_dropout`` serve
+``norm_first`` and ``activation="gelu"`` of nn.TransformerEncoderLayer.
 """
 import math
 
@@ -169,6 +171,90 @@ def add_layer_norm(x, h, gamma, beta, eps=1e-5, drop=NO_DROP, h_bias=None):
     projection that produced h, whose gradient then comes out of this op's backward); h = None -> LayerNorm(x)."""
     assert h_bias is None or (h is not None and h_bias.dtype == torch.float32 and h_bias.is_contiguous())
     return _AddLayerNorm.apply(x, h, h_bias, gamma, beta, eps, drop)
+
+
+class _ResidualLayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, h, h_bias, gamma, beta, eps, drop):
+        d = x.shape[-1]
+        rows = x.numel() // d
+        x, h = _f32(x), _f32(h)
+        s = torch.empty_like(x)
+        y = torch.empty_like(x)
+        stats = torch.empty(rows, 2, device=x.device, dtype=torch.float32)
+        with profiler.region("lm_res_ln:fwd", nbytes=4 * rows * d * 4, bound="hbm"):
+            N.check(N.lib().smt_lm_res_ln_fwd(N.ptr(x), N.ptr(h), N.ptr(h_bias), N.ptr(_f32(gamma)), N.ptr(_f32(beta)), N.ptr(s), N.ptr(y),
+                                              N.ptr(stats), rows, d, eps, drop.key, N.ptr(drop.key_dev), drop.thresh, drop.scale, N.stream_ptr()),
+                    "smt_lm_res_ln_fwd")
+        ctx.save_for_backward(s, gamma, stats)
+        ctx.meta = (rows, d, drop, h_bias is not None)
+        ctx.set_materialize_grads(False)                        # an unused output's gradient arrives as None, not as zeros
+        return s, y
+
+    @staticmethod
+    def backward(ctx, ds, dy):
+        s, gamma, stats = ctx.saved_tensors
+        rows, d, drop, with_bias = ctx.meta
+        lib = N.lib()
+        ds = _f32(ds) if ds is not None else None
+        dy = _f32(dy) if dy is not None else None
+        dx = torch.empty_like(s) if ctx.needs_input_grad[0] else None
+        dh = torch.empty_like(s) if ctx.needs_input_grad[1] else None
+        dparams = torch.empty(3, d, device=s.device, dtype=torch.float32)
+        ws_bytes = lib.smt_lm_res_ln_bwd_workspace_bytes(rows, d)
+        ws = torch.empty(ws_bytes, device=s.device, dtype=torch.uint8)
+        n_io = (ds is not None) + 2 * (dy is not None) + (dx is not None) + (dh is not None)
+        with profiler.region("lm_res_ln:bwd", nbytes=n_io * rows * d * 4, bound="hbm"):
+            N.check(lib.smt_lm_res_ln_bwd(N.ptr(s), N.ptr(ds), N.ptr(dy), N.ptr(_f32(gamma)), N.ptr(stats), N.ptr(dx), N.ptr(dh),
+                                          N.ptr(dparams), rows, d, drop.key, N.ptr(drop.key_dev), drop.thresh, drop.scale, N.ptr(ws),
+                                          ws_bytes, N.stream_ptr()), "smt_lm_res_ln_bwd")
+        return dx, dh, (dparams[2] if with_bias else None), dparams[0], dparams[1], None, None
+
+
+def residual_layer_norm(x, h, gamma, beta, eps=1e-5, drop=NO_DROP, h_bias=None):
+    """The residual step of a pre-norm layer: (s, y) with s = x + dropout(h + h_bias), the new residual stream, and
+    y = LayerNorm(s) * gamma + beta, the input of the next projection (gamma / beta / eps of the NEXT norm: the layer's norm2,
+    the next layer's norm1 or the encoder's final norm).  h_bias as in `add_layer_norm`.  Either output may go unused: its
+    gradient then counts as zero."""
+    assert x.shape == h.shape and (h_bias is None or (h_bias.dtype == torch.float32 and h_bias.is_contiguous()))
+    return _ResidualLayerNorm.apply(x, h, h_bias, gamma, beta, eps, drop)
+
+
+class _BiasGeluDrop(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, bias, drop):
+        d = h.shape[-1]
+        rows = h.numel() // d
+        h, bias = _f32(h), _f32(bias)
+        a = torch.empty_like(h)
+        with profiler.region("lm_bias_gelu:fwd", nbytes=2 * rows * d * 4, bound="hbm"):
+            N.check(N.lib().smt_lm_bias_gelu_fwd(N.ptr(h), N.ptr(bias), N.ptr(a), rows, d, drop.key, N.ptr(drop.key_dev), drop.thresh,
+                                                 drop.scale, N.stream_ptr()), "smt_lm_bias_gelu_fwd")
+        ctx.save_for_backward(h, bias)
+        ctx.meta = (rows, d, drop)
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        h, bias = ctx.saved_tensors
+        rows, d, drop = ctx.meta
+        lib = N.lib()
+        da = _f32(da)
+        dh = torch.empty_like(h)
+        dbias = torch.empty(d, device=h.device, dtype=torch.float32)
+        ws_bytes = lib.smt_lm_bias_gelu_bwd_workspace_bytes(rows, d)
+        ws = torch.empty(ws_bytes, device=h.device, dtype=torch.uint8)
+        with profiler.region("lm_bias_gelu:bwd", nbytes=3 * rows * d * 4, bound="hbm"):
+            N.check(lib.smt_lm_bias_gelu_bwd(N.ptr(h), N.ptr(bias), N.ptr(da), N.ptr(dh), N.ptr(dbias), rows, d, drop.key,
+                                             N.ptr(drop.key_dev), drop.thresh, drop.scale, N.ptr(ws), ws_bytes, N.stream_ptr()),
+                    "smt_lm_bias_gelu_bwd")
+        return dh, dbias, None
+
+
+def bias_gelu_dropout(h, bias, drop=NO_DROP):
+    """dropout(gelu(h + bias)), the exact (erf) GELU, on the (bias-free) output of linear1.  Not in place: h stays as it is
+    and is kept for the backward, which needs the pre-activation."""
+    return _BiasGeluDrop.apply(h, bias, drop)
 
 
 class _BiasReluDrop(torch.autograd.Function):
@@ -443,16 +529,24 @@ def decode_embed(tokens, weight, pe, out, pos=0, pos_dev=None):
     return out
 
 
-def decode_linear(x, weight, bias=None, out=None, relu=False):
-    """out [batch, n] = x [batch, k] @ weight [n, k]^T (+ bias) (ReLU); batch <= 32, k % 64 == 0 (else RuntimeError)."""
+ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
+
+
+def decode_linear(x, weight, bias=None, out=None, relu=False, act=None):
+    """out [batch, n] = act(x [batch, k] @ weight [n, k]^T (+ bias)); act: 0 none, 1 ReLU, 2 exact GELU (`relu=True` is act=1);
+    batch <= 32, k % 64 == 0 (else RuntimeError)."""
     b, k = x.shape
     n = weight.shape[0]
     assert weight.shape == (n, k) and (bias is None or bias.shape == (n,))
+    if act is None:
+        act = ACT_RELU if relu else ACT_NONE
+    elif relu and act != ACT_RELU:
+        raise ValueError(f"decode_linear: relu=True and act={act!r} contradict each other")
     if out is None:
         out = torch.empty(b, n, device=x.device, dtype=torch.float32)
     assert out.shape == (b, n) and out.dtype == torch.float32
     N.check(N.lib().smt_lm_decode_linear(N.ptr(_f32(x)), N.ptr(_f32(weight)), N.ptr(None if bias is None else _f32(bias)), N.ptr(out),
-                                         b, k, n, int(relu), N.stream_ptr()), "smt_lm_decode_linear")
+                                         b, k, n, int(act), N.stream_ptr()), "smt_lm_decode_linear")
     return out
 
 
@@ -528,6 +622,15 @@ def decode_layer_norm(x, h, h_bias, gamma, beta, eps, out, stats):
     return out
 
 
+def decode_residual_layer_norm(x, h, h_bias, gamma, beta, eps, s_out, out, stats):
+    """smt_lm_res_ln_fwd on `rows = batch` without dropout: s_out = x + h + h_bias (the new stream), out = LayerNorm(s_out), both
+    caller-owned and distinct from x and h."""
+    rows, d = x.shape
+    N.check(N.lib().smt_lm_res_ln_fwd(N.ptr(x), N.ptr(h), N.ptr(h_bias), N.ptr(_f32(gamma)), N.ptr(_f32(beta)), N.ptr(s_out), N.ptr(out),
+                                      N.ptr(stats), rows, d, eps, 0, None, 0, 1.0, N.stream_ptr()), "smt_lm_res_ln_fwd")
+    return s_out, out
+
+
 class DecodeState:
     """Every buffer of an incremental decoding loop (TransformerLM.sample(causal=True) / step_logits): the key/value cache
     [layers, 2, batch, heads, l_max, 32], the token [batch, n_steps + 1] and code [batch, n_steps] buffers, the position
@@ -549,6 +652,7 @@ class DecodeState:
         assert self.uniforms.shape == (n_steps, batch)
         self.kept = torch.zeros(n_steps, batch, device=device, dtype=torch.int32)
         self.h, self.h1, self.ctx, self.a = (torch.empty(batch, dim, **f32) for _ in range(4))
+        self.s = torch.empty(batch, dim, **f32)        # pre-norm layers: the residual stream between a layer's two sub-layers
         self.qkv = torch.empty(batch, 3 * dim, **f32)
         self.f = torch.empty(batch, dim_ff, **f32)
         self.stats = torch.empty(batch, 2, **f32)

@@ -125,6 +125,15 @@ _SIGNATURES = {
     "smt_lm_add_ln_bwd_workspace_bytes": (c_size, [c_i64, c_int]),
     "smt_lm_add_ln_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_u32, c_ptr,
                                   c_u32, c_f32, c_ptr, c_size, c_ptr]),
+    "smt_lm_res_ln_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f32, c_u32, c_ptr, c_u32,
+                                  c_f32, c_ptr]),
+    "smt_lm_res_ln_bwd_workspace_bytes": (c_size, [c_i64, c_int]),
+    "smt_lm_res_ln_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_u32, c_ptr, c_u32, c_f32,
+                                  c_ptr, c_size, c_ptr]),
+    "smt_lm_bias_gelu_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_u32, c_ptr, c_u32, c_f32, c_ptr]),
+    "smt_lm_bias_gelu_bwd_workspace_bytes": (c_size, [c_i64, c_int]),
+    "smt_lm_bias_gelu_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_u32, c_ptr, c_u32, c_f32, c_ptr, c_size,
+                                     c_ptr]),
     "smt_lm_bias_relu_fwd": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_u32, c_ptr, c_u32, c_f32, c_ptr]),
     "smt_lm_bias_relu_bwd_workspace_bytes": (c_size, [c_i64, c_int]),
     "smt_lm_bias_relu_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_u32, c_ptr, c_u32, c_f32, c_ptr, c_size, c_ptr]),
