@@ -603,6 +603,25 @@ int smt_lm_attention_bwd(const float* qkv, const int* lens, const float* ctx, co
                          float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
                          const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream);
 
+/* The same two calls with the five (forward: two) 32-channel products on v_mfma_f32_32x32x16_bf16 (model.attention_dtype:
+ * bf16).  Tensors, layouts, limits, argument checks, workgroup ownership, merge order, dropout indices and keys are those
+ * of the f32 entries above; every tensor stays f32 in memory.  The arithmetic has exactly these rounding points:
+ *   operands   q, k, v and dctx are rounded to bf16 (nearest even, v_cvt_pk_bf16_f32) as loaded, unscaled: 1/sqrt(32) and
+ *              log2(e) multiply the f32 score accumulator, so a bf16-representable input is used exactly
+ *   forward    s = q^ . k^ accumulated in f32;  the running max m, the sum z of the UNROUNDED p = exp2(s - m) and lse are
+ *              f32;  the second product's operand is bf16(p * keep * drop_scale), one rounding;  ctx accumulates in f32,
+ *              takes the f32 rescale and 1/z, and is stored f32
+ *   dq kernel  delta = dctx . ctx in f32 from the unrounded values;  dP = dctx^ . v^;
+ *              dS = p (keep * drop_scale * dP - delta) in f32, rounded once to bf16;  dq = (dS^ . k^) / sqrt(32)
+ *   dkv kernel dv = bf16(p * keep * drop_scale)^T . dctx^;  dk = (dS^^T . q^) / sqrt(32)
+ * (x^ = x rounded to bf16; in the backward p = exp2(s - lse), the normalised weight). */
+int smt_lm_attention_bf16_fwd(const float* qkv, const int* lens, float* ctx, float* lse, int batch, int len, int heads,
+                              int causal, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale,
+                              smt_stream_t stream);
+int smt_lm_attention_bf16_bwd(const float* qkv, const int* lens, const float* ctx, const float* lse, const float* dctx,
+                              float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
+                              const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream);
+
 /* y = LayerNorm(x + dropout(h + h_bias)) * gamma + beta over the last dim (TransformerEncoderLayer, norm_first = False):
  * h is the bias-free output of out_proj / linear2 and h_bias [dim] that projection's bias (NULL = none), so that the
  * bias gradient falls out of this kernel's backward instead of a separate reduction; with h = NULL the plain final

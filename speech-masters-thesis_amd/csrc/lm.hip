@@ -5,6 +5,7 @@
 //
 //   lm_embed        tokens -> emb[token] * sqrt(d) + pe[pos], dropout                          (transformer_lm.py:114-116, :27-29)
 //   lm_attention    softmax(Q K^T / sqrt(dh) + causal + key-padding mask), dropout, . V        (nn.MultiheadAttention)
+//                   (smt_lm_attention_bf16_*: the same kernels with their products on bf16 MFMAs, model.attention_dtype)
 //   lm_add_ln       LayerNorm(x + dropout(h))                                                   (TransformerEncoderLayer, post-norm)
 //   lm_bias_relu    dropout(relu(h + b))  in place                                              (linear1 -> activation -> dropout)
 //   lm_res_ln       s = x + dropout(h), y = LayerNorm(s): a residual add and the NEXT norm     (TransformerEncoderLayer, norm_first)
@@ -110,6 +111,40 @@ __device__ __forceinline__ f32x16v at_zero16() {
   for (int i = 0; i < 16; ++i) z[i] = 0.f;
   return z;
 }
+// The product step as a compile-time policy.  BF = false is at_mfma16 above.  BF = true rounds both operands to bf16 at
+// the product (the compiler's conversion: v_cvt_pk_bf16_f32, round to nearest even) and issues two
+// v_mfma_f32_32x32x16_bf16: registers 8 s .. 8 s + 7 of a lane are k-step s, k = 8 (lane >> 5) + j inside it.  The same
+// index permutation applies to both operands, so every fragment pair that is consistent for at_mfma16 -- row with row,
+// column with accumulator -- is consistent here, and the contraction still covers the same 32 indices.
+__device__ __forceinline__ bf16x8 at_round8(const float (&r)[16], int s) {
+  return bf16x8{(__bf16)r[8 * s], (__bf16)r[8 * s + 1], (__bf16)r[8 * s + 2], (__bf16)r[8 * s + 3],
+                (__bf16)r[8 * s + 4], (__bf16)r[8 * s + 5], (__bf16)r[8 * s + 6], (__bf16)r[8 * s + 7]};
+}
+template <bool BF>
+__device__ __forceinline__ f32x16v at_prod(const float (&a)[16], const float (&b)[16], f32x16v c) {
+  if constexpr (BF) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_round8(a, s), at_round8(b, s), c, 0, 0, 0);
+    return c;
+  } else {
+    return at_mfma16(a, b, c);
+  }
+}
+// The scores a . b in base-2 units, s2 = log2(e) / sqrt(32): the f32 kernels fold s2 into one operand as they load it, the
+// bf16 kernels load both unscaled and multiply the f32 accumulator.
+template <bool BF>
+__device__ __forceinline__ f32x16v at_scores(const float (&a)[16], const float (&b)[16], float s2) {
+  f32x16v st = at_prod<BF>(a, b, at_zero16());
+  if constexpr (BF) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) st[i] *= s2;
+  }
+  return st;
+}
+// Arithmetic of the bf16 instantiations (smt_lm_attention_bf16_*; include/smt_hip.h lists the rounding points): q, k, v and
+// dctx are rounded as loaded, unscaled, so that a bf16-representable input is used exactly; 1/sqrt(32) and log2(e)
+// multiply the f32 score accumulator instead of the operand.  m, z, lse, delta, the rescales and every accumulator are
+// f32; p keep dscale and dS are rounded once, where they become an operand.
 // Sum the four waves' transposed accumulators (each scaled by its own `scale`) through LDS red [4][16][64]; wave w then
 // stores channel group w -- channels 8 w + 4 hh + {0..3} -- of the row this lane's column stands for, times mul.
 __device__ __forceinline__ void at_merge_store(float* red, const f32x16v& o, float scale, int w, int lane, int hh, float mul, bool live,
@@ -149,6 +184,7 @@ __device__ __forceinline__ void at_keep16(float (&kf)[16], unsigned long long e_
 }
 constexpr float LM_LOG2E = 1.4426950408889634f;
 
+template <bool BF>
 __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restrict__ qkv, const int* __restrict__ lens,
                                                           float* __restrict__ ctx, float* __restrict__ lse, int L, int H,
                                                           int causal, unsigned key, const unsigned* __restrict__ key_dev, unsigned thr, float dscale) {
@@ -165,8 +201,9 @@ __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restric
   const int len = lens ? max(0, min(lens[b], L)) : L;
   const int q0 = qb * 32, qi = q0 + col, qc = min(qi, L - 1);
   const int kend = causal ? min(len, min(L, q0 + 32)) : len;  // keys any query of this block can see
+  const float s2 = rsqrtf((float)LM_DH) * LM_LOG2E;           // scores in base-2 units: exp2 is ONE instruction
   float qf[16];
-  at_row_frag(qf, qm, pitch, qi, L - 1, hh, rsqrtf((float)LM_DH) * LM_LOG2E);   // scores in base-2 units: exp2 is ONE instruction
+  at_row_frag(qf, qm, pitch, qi, L - 1, hh, BF ? 1.f : s2);
   f32x16v o = at_zero16();
   float m = -INFINITY, z = 0.f;
   const unsigned long long e0 = (((unsigned long long)b * H + h) * L + qc) * L;
@@ -174,7 +211,7 @@ __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restric
     float kf[16], vf[16];
     at_row_frag(kf, km, pitch, k0 + col, L - 1, hh, 1.f);
     at_col_frag(vf, vm, pitch, k0, L - 1, col, hh);
-    f32x16v st = at_mfma16(kf, qf, at_zero16());
+    f32x16v st = at_scores<BF>(kf, qf, s2);
     float mloc = -INFINITY;
     if (k0 + 32 <= kend && (!causal || k0 + 31 <= q0)) {      // uniform: every key of the block visible to every query
 #pragma unroll
@@ -202,7 +239,7 @@ __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restric
       z += p;
       pk[i] *= p;
     }
-    o = at_mfma16(vf, pk, o);
+    o = at_prod<BF>(vf, pk, o);
   }
   // merge the four waves' partial softmaxes (m is per query = the same in both lane halves; z is a per-half partial)
   red_m[w][lane] = m; red_z[w][lane] = z;
@@ -224,6 +261,7 @@ __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restric
 // dS_ij = P_ij (keep_ij dPd_ij - delta_i); dq_i = sum_j dS_ij k_j / sqrt(dh); dk_j = sum_i dS_ij q_i / sqrt(dh);
 // dv_j = sum_i P_ij keep_ij dctx_i.
 // dq: 32 queries per workgroup (the accumulator column): S^T = K Q^T, dPd^T = V dctx^T, dq^T += K^T dS^T; leaves delta.
+template <bool BF>
 __global__ __launch_bounds__(256) void lm_attn_dq_kernel(const float* __restrict__ qkv, const int* __restrict__ lens,
                                                          const float* __restrict__ ctx, const float* __restrict__ lse,
                                                          const float* __restrict__ dctx, float* __restrict__ dqkv,
@@ -243,7 +281,7 @@ __global__ __launch_bounds__(256) void lm_attn_dq_kernel(const float* __restrict
   const int kend = causal ? min(len, min(L, q0 + 32)) : len;
   const float sc = rsqrtf((float)LM_DH);
   float qf[16], gf[16];
-  at_row_frag(qf, qm, pitch, qi, L - 1, hh, sc * LM_LOG2E);    // base-2 scores, as in the forward (lse is base-2)
+  at_row_frag(qf, qm, pitch, qi, L - 1, hh, BF ? 1.f : sc * LM_LOG2E);   // base-2 scores, as in the forward (lse is base-2)
   at_row_frag(gf, dctx + (size_t)b * L * d + h * LM_DH, d, qi, L - 1, hh, 1.f);
   float dl = 0.f;
   {
@@ -262,8 +300,8 @@ __global__ __launch_bounds__(256) void lm_attn_dq_kernel(const float* __restrict
     at_row_frag(kf, km, pitch, k0 + col, L - 1, hh, 1.f);
     at_row_frag(vf, vm, pitch, k0 + col, L - 1, hh, 1.f);
     at_col_frag(kc, km, pitch, k0, L - 1, col, hh);
-    const f32x16v st = at_mfma16(kf, qf, at_zero16());
-    const f32x16v dp = at_mfma16(vf, gf, at_zero16());
+    const f32x16v st = at_scores<BF>(kf, qf, sc * LM_LOG2E);
+    const f32x16v dp = at_prod<BF>(vf, gf, at_zero16());
     float ds[16];
     at_keep16(ds, e0 + k0, hh, key, thr, dscale);
     if (k0 + 32 <= kend && (!causal || k0 + 31 <= q0)) {      // uniform: no mask inside the block
@@ -277,13 +315,14 @@ __global__ __launch_bounds__(256) void lm_attn_dq_kernel(const float* __restrict
         ds[i] = p * (ds[i] * dp[i] - dl);
       }
     }
-    dq = at_mfma16(kc, ds, dq);
+    dq = at_prod<BF>(kc, ds, dq);
   }
   at_merge_store(red, dq, 1.f, w, lane, hh, sc, qi < L, dqkv + ((size_t)b * L + qc) * pitch + h * LM_DH);
 }
 
 // dk, dv: 32 keys per workgroup (the accumulator column): S = Q K^T and dPd = dctx V^T with the queries in the accumulator
 // rows, then dv^T += dctx^T (P keep), dk^T += Q^T dS.  lse and delta of the 16 query rows a lane holds are loaded per block.
+template <bool BF>
 __global__ __launch_bounds__(256) void lm_attn_dkv_kernel(const float* __restrict__ qkv, const int* __restrict__ lens,
                                                           const float* __restrict__ lse, const float* __restrict__ dctx,
                                                           const float* __restrict__ delta, float* __restrict__ dqkv, int L,
@@ -302,7 +341,7 @@ __global__ __launch_bounds__(256) void lm_attn_dkv_kernel(const float* __restric
   const int kj = kb * 32 + col, kc = min(kj, L - 1);
   const float sc = rsqrtf((float)LM_DH);
   float kf[16], vf[16];
-  at_row_frag(kf, qm + d, pitch, kj, L - 1, hh, sc * LM_LOG2E); // 1/sqrt(dh) and the base-2 conversion folded into the key
+  at_row_frag(kf, qm + d, pitch, kj, L - 1, hh, BF ? 1.f : sc * LM_LOG2E);   // f32: 1/sqrt(dh) and the base-2 conversion folded into the key
   at_row_frag(vf, qm + 2 * d, pitch, kj, L - 1, hh, 1.f);
   f32x16v dk = at_zero16(), dv = at_zero16();
   const unsigned long long e0 = ((unsigned long long)b * H + h) * L;
@@ -313,8 +352,8 @@ __global__ __launch_bounds__(256) void lm_attn_dkv_kernel(const float* __restric
       at_row_frag(ga, gm, d, q0 + col, L - 1, hh, 1.f);
       at_col_frag(qc, qm, pitch, q0, L - 1, col, hh);
       at_col_frag(gc, gm, d, q0, L - 1, col, hh);
-      const f32x16v st = at_mfma16(qa, kf, at_zero16());
-      const f32x16v dp = at_mfma16(ga, vf, at_zero16());
+      const f32x16v st = at_scores<BF>(qa, kf, sc * LM_LOG2E);
+      const f32x16v dp = at_prod<BF>(ga, vf, at_zero16());
       float pk[16], ds[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
@@ -323,8 +362,8 @@ __global__ __launch_bounds__(256) void lm_attn_dkv_kernel(const float* __restric
         pk[i] = p * lm_keep((e0 + qrc) * L + kc, key, thr, dscale);
         ds[i] = pk[i] * dp[i] - p * drow[qrc];
       }
-      dv = at_mfma16(gc, pk, dv);
-      dk = at_mfma16(qc, ds, dk);
+      dv = at_prod<BF>(gc, pk, dv);
+      dk = at_prod<BF>(qc, ds, dk);
     }
   }
   float* dst = dqkv + ((size_t)b * L + kc) * pitch + h * LM_DH;
@@ -844,35 +883,62 @@ extern "C" int smt_lm_embed_bwd(const int64_t* tokens, const float* dout, float*
   return 0;
 }
 
-extern "C" int smt_lm_attention_fwd(const float* qkv, const int* lens, float* ctx, float* lse, int batch, int len, int heads,
-                                    int causal, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream_) {
+// One launcher per pass for both operand types: the argument checks, the grid and the kernels' arguments are the same.
+template <bool BF>
+static int lm_attention_fwd_launch(const char* name, const float* qkv, const int* lens, float* ctx, float* lse, int batch, int len, int heads,
+                                   int causal, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (batch <= 0 || len <= 0) return 0;
-  SMT_CHECK_ARG(qkv && ctx && lse, "smt_lm_attention_fwd: null pointer");
-  SMT_CHECK_ARG(heads >= 1 && lm_len_ok(len, heads), "smt_lm_attention_fwd: len * 3 * heads * 32 must be < 2^31 (len %d, heads %d)", len, heads);
-  SMT_CHECK_ARG((long long)batch * heads <= 65535, "smt_lm_attention_fwd: batch * heads must be <= 65535");
-  lm_attn_fwd_kernel<<<dim3((len + 31) / 32, batch * heads), 256, 0, stream>>>(qkv, lens, ctx, lse, len, heads, causal, drop_key, drop_key_dev,
-                                                                           drop_thresh16, drop_scale);
-  SMT_CHECK_LAUNCH("lm_attention_fwd");
+  SMT_CHECK_ARG(qkv && ctx && lse, "%s: null pointer", name);
+  SMT_CHECK_ARG(heads >= 1 && lm_len_ok(len, heads), "%s: len * 3 * heads * 32 must be < 2^31 (len %d, heads %d)", name, len, heads);
+  SMT_CHECK_ARG((long long)batch * heads <= 65535, "%s: batch * heads must be <= 65535", name);
+  lm_attn_fwd_kernel<BF><<<dim3((len + 31) / 32, batch * heads), 256, 0, stream>>>(qkv, lens, ctx, lse, len, heads, causal, drop_key, drop_key_dev,
+                                                                               drop_thresh16, drop_scale);
+  SMT_CHECK_LAUNCH(BF ? "lm_attention_bf16_fwd" : "lm_attention_fwd");
   return 0;
 }
 
-extern "C" int smt_lm_attention_bwd(const float* qkv, const int* lens, const float* ctx, const float* lse, const float* dctx,
-                                    float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
-                                    const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream_) {
+template <bool BF>
+static int lm_attention_bwd_launch(const char* name, const float* qkv, const int* lens, const float* ctx, const float* lse, const float* dctx,
+                                   float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
+                                   const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (batch <= 0 || len <= 0) return 0;
-  SMT_CHECK_ARG(qkv && ctx && lse && dctx && dqkv && delta, "smt_lm_attention_bwd: null pointer");
-  SMT_CHECK_ARG(heads >= 1 && lm_len_ok(len, heads), "smt_lm_attention_bwd: len * 3 * heads * 32 must be < 2^31 (len %d, heads %d)", len, heads);
-  SMT_CHECK_ARG((long long)batch * heads <= 65535, "smt_lm_attention_bwd: batch * heads must be <= 65535");
+  SMT_CHECK_ARG(qkv && ctx && lse && dctx && dqkv && delta, "%s: null pointer", name);
+  SMT_CHECK_ARG(heads >= 1 && lm_len_ok(len, heads), "%s: len * 3 * heads * 32 must be < 2^31 (len %d, heads %d)", name, len, heads);
+  SMT_CHECK_ARG((long long)batch * heads <= 65535, "%s: batch * heads must be <= 65535", name);
   const dim3 grid((len + 31) / 32, batch * heads);
-  lm_attn_dq_kernel<<<grid, 256, 0, stream>>>(qkv, lens, ctx, lse, dctx, dqkv, delta, len, heads, causal, drop_key, drop_key_dev, drop_thresh16,
-                                            drop_scale);
-  SMT_CHECK_LAUNCH("lm_attention_dq");
-  lm_attn_dkv_kernel<<<grid, 256, 0, stream>>>(qkv, lens, lse, dctx, delta, dqkv, len, heads, causal, drop_key, drop_key_dev, drop_thresh16,
-                                             drop_scale);
-  SMT_CHECK_LAUNCH("lm_attention_dkv");
+  lm_attn_dq_kernel<BF><<<grid, 256, 0, stream>>>(qkv, lens, ctx, lse, dctx, dqkv, delta, len, heads, causal, drop_key, drop_key_dev, drop_thresh16,
+                                                drop_scale);
+  SMT_CHECK_LAUNCH(BF ? "lm_attention_bf16_dq" : "lm_attention_dq");
+  lm_attn_dkv_kernel<BF><<<grid, 256, 0, stream>>>(qkv, lens, lse, dctx, delta, dqkv, len, heads, causal, drop_key, drop_key_dev, drop_thresh16,
+                                                 drop_scale);
+  SMT_CHECK_LAUNCH(BF ? "lm_attention_bf16_dkv" : "lm_attention_dkv");
   return 0;
+}
+
+extern "C" int smt_lm_attention_fwd(const float* qkv, const int* lens, float* ctx, float* lse, int batch, int len, int heads,
+                                    int causal, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream) {
+  return lm_attention_fwd_launch<false>("smt_lm_attention_fwd", qkv, lens, ctx, lse, batch, len, heads, causal, drop_key, drop_key_dev,
+                                        drop_thresh16, drop_scale, stream);
+}
+extern "C" int smt_lm_attention_bf16_fwd(const float* qkv, const int* lens, float* ctx, float* lse, int batch, int len, int heads,
+                                         int causal, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale,
+                                         smt_stream_t stream) {
+  return lm_attention_fwd_launch<true>("smt_lm_attention_bf16_fwd", qkv, lens, ctx, lse, batch, len, heads, causal, drop_key, drop_key_dev,
+                                       drop_thresh16, drop_scale, stream);
+}
+extern "C" int smt_lm_attention_bwd(const float* qkv, const int* lens, const float* ctx, const float* lse, const float* dctx,
+                                    float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
+                                    const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream) {
+  return lm_attention_bwd_launch<false>("smt_lm_attention_bwd", qkv, lens, ctx, lse, dctx, dqkv, delta, batch, len, heads, causal, drop_key,
+                                        drop_key_dev, drop_thresh16, drop_scale, stream);
+}
+extern "C" int smt_lm_attention_bf16_bwd(const float* qkv, const int* lens, const float* ctx, const float* lse, const float* dctx,
+                                         float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
+                                         const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream) {
+  return lm_attention_bwd_launch<true>("smt_lm_attention_bf16_bwd", qkv, lens, ctx, lse, dctx, dqkv, delta, batch, len, heads, causal, drop_key,
+                                       drop_key_dev, drop_thresh16, drop_scale, stream);
 }
 
 extern "C" int smt_lm_add_ln_fwd(const float* x, const float* h, const float* h_bias, const float* gamma, const float* beta, float* y,

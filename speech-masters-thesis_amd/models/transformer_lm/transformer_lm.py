@@ -4,7 +4,7 @@ Same constructor keys, parameter names (a reference state_dict loads as is), ``f
 ``reconstruct`` / ``load_vqvae`` surface and loss definition as the reference, which builds the stack from
 ``torch.nn.TransformerEncoder``.  Here a layer is its dense projections (``smt_amd.lm.linear``: library GEMMs in fp32, or with
 ``model.compute_dtype: bf16`` the native bf16-operand GEMMs of csrc/lm_linear.hip) with everything between them in the HIP kernels
-of csrc/lm.hip (attention core, add + dropout + LayerNorm, bias + ReLU + dropout, embedding, the three losses); activations
+of csrc/lm.hip (attention core -- with ``model.attention_dtype: bf16`` its products on bf16 MFMAs --, add + dropout + LayerNorm, bias + ReLU + dropout, embedding, the three losses); activations
 are batch-major [B, L, d] instead of the reference's [L, B, d].  ``model.norm_first`` and ``model.activation`` are
 nn.TransformerEncoderLayer's arguments of those names: pre-norm layers run their residual adds fused with the NEXT LayerNorm
 (``smt_amd.lm.residual_layer_norm``), ``gelu`` is the exact form (``smt_amd.lm.bias_gelu_dropout``).  Dropout uses the
@@ -62,9 +62,11 @@ class _EncoderLayer(nn.Module):
     """Encoder layer with nn.TransformerEncoderLayer's parameter names; post-norm (`forward`, `prefill`) or pre-norm
     (`forward_pre`, `prefill_pre`: the encoder calls the pair that matches its norm_first), ReLU or exact-GELU feed-forward."""
 
-    def __init__(self, d_model, nhead, dim_feedforward, dropout, layer_norm_eps=1e-5, compute_dtype=torch.float32, activation="relu"):
+    def __init__(self, d_model, nhead, dim_feedforward, dropout, layer_norm_eps=1e-5, compute_dtype=torch.float32, activation="relu",
+                 attention_dtype=torch.float32):
         super().__init__()
         self.compute_dtype = compute_dtype      # of the four projections' operands (smt_amd.lm.linear)
+        self.attention_dtype = attention_dtype  # of the attention core's products (smt_amd.lm.attention)
         self.act = ACTIVATIONS[activation]
         self.self_attn = _SelfAttention(d_model, nhead)
         self.linear1 = nn.Linear(d_model, dim_feedforward)
@@ -83,7 +85,7 @@ class _EncoderLayer(nn.Module):
     def forward(self, x, lens, causal, seed, site0, kd=None):
         sa, tr, p, cd = self.self_attn, self.training, self.p, self.compute_dtype
         qkv = K.linear(x, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=cd)
-        ctx = K.attention(qkv, lens, sa.num_heads, causal, K.Drop(p, tr, seed, site0, kd))
+        ctx = K.attention(qkv, lens, sa.num_heads, causal, K.Drop(p, tr, seed, site0, kd), compute_dtype=self.attention_dtype)
         a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)    # its bias is added (and differentiated) inside add_layer_norm
         x = K.add_layer_norm(x, a, self.norm1.weight, self.norm1.bias, self.norm1.eps, K.Drop(p, tr, seed, site0 + 1, kd),
                              h_bias=sa.out_proj.bias)
@@ -98,7 +100,7 @@ class _EncoderLayer(nn.Module):
         residual add runs fused with the norm after it, so a layer is the same four launches as the post-norm one."""
         sa, tr, p, cd = self.self_attn, self.training, self.p, self.compute_dtype
         qkv = K.linear(y, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=cd)
-        ctx = K.attention(qkv, lens, sa.num_heads, causal, K.Drop(p, tr, seed, site0, kd))
+        ctx = K.attention(qkv, lens, sa.num_heads, causal, K.Drop(p, tr, seed, site0, kd), compute_dtype=self.attention_dtype)
         a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)    # its bias is added (and differentiated) inside residual_layer_norm
         s, y = K.residual_layer_norm(s, a, self.norm2.weight, self.norm2.bias, self.norm2.eps, K.Drop(p, tr, seed, site0 + 1, kd),
                                      h_bias=sa.out_proj.bias)
@@ -115,7 +117,7 @@ class _EncoderLayer(nn.Module):
         K.decode_prefill_kv(qkv, k_cache, v_cache)
         if last:
             return None
-        ctx = K.attention(qkv, None, sa.num_heads, True)
+        ctx = K.attention(qkv, None, sa.num_heads, True, compute_dtype=self.attention_dtype)
         a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)
         x = K.add_layer_norm(x, a, self.norm1.weight, self.norm1.bias, self.norm1.eps, h_bias=sa.out_proj.bias)
         f = self._ff_inner(x)
@@ -129,7 +131,7 @@ class _EncoderLayer(nn.Module):
         K.decode_prefill_kv(qkv, k_cache, v_cache)
         if last:
             return None
-        ctx = K.attention(qkv, None, sa.num_heads, True)
+        ctx = K.attention(qkv, None, sa.num_heads, True, compute_dtype=self.attention_dtype)
         a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)
         s, y = K.residual_layer_norm(s, a, self.norm2.weight, self.norm2.bias, self.norm2.eps, h_bias=sa.out_proj.bias)
         f = K.linear(self._ff_inner(y), self.linear2.weight, compute_dtype=cd)
@@ -173,11 +175,18 @@ class TransformerLM(TokenToWaveformModel):
             for key, mult in (("d_model", 32), ("dim_feedforward", 32), ("vocab_size", 16)):
                 if m[key] % mult:
                     raise ValueError(f"model.compute_dtype bf16: {key}={m[key]} must be a multiple of {mult} (the GEMM kernels' limit)")
+        # operands of the attention core's products, independent of compute_dtype: fp32 = f32-input MFMAs, bf16 = bf16 MFMAs
+        # (smt_lm_attention_bf16_*); the one-token decoding attention stays fp32 either way
+        name = m.get("attention_dtype", "fp32")
+        if name not in COMPUTE_DTYPES:
+            raise ValueError(f"model.attention_dtype must be fp32 or bf16 (got {name!r})")
+        self.attention_dtype = COMPUTE_DTYPES[name]
         self.d_model = m.d_model
         self.embedding = nn.Embedding(m.vocab_size + TransformerLM.OFFSET, m.embed_dim, padding_idx=TransformerLM.PAD)
         self.pos_encoding = PositionalEncoding(m.d_model, m.dropout, m.max_len)
         # the reference's layers keep nn.TransformerEncoderLayer's default eps; only the final norm takes the config's
-        layer = _EncoderLayer(m.d_model, m.nhead, m.dim_feedforward, m.dropout, compute_dtype=self.compute_dtype, activation=activation)
+        layer = _EncoderLayer(m.d_model, m.nhead, m.dim_feedforward, m.dropout, compute_dtype=self.compute_dtype, activation=activation,
+                              attention_dtype=self.attention_dtype)
         self.transformer = _Encoder(layer, m.num_layers, nn.LayerNorm(m.d_model, eps=float(m.layer_norm_eps)))
         self.classifier = nn.Linear(m.d_model, m.vocab_size)
         self.vqvae = TransformerLM.load_vqvae(m.vqvae.log_dir, m.vqvae.ckpt_num)

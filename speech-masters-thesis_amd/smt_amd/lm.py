@@ -89,43 +89,54 @@ def _attn_flops(b, heads, l, causal, matmuls):
     return b * heads * pairs * 64 * matmuls
 
 
+# compute_dtype of `attention` -> (forward entry, backward entry, profiler region, profiler dtype)
+_ATTN_ENTRIES = {torch.float32: ("smt_lm_attention_fwd", "smt_lm_attention_bwd", "lm_attention", "f32"),
+                 torch.bfloat16: ("smt_lm_attention_bf16_fwd", "smt_lm_attention_bf16_bwd", "lm_attention_bf16", "bf16")}
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, lens, heads, causal, drop):
+    def forward(ctx, qkv, lens, heads, causal, drop, compute_dtype=torch.float32):
+        fwd, _, region, dtype = _ATTN_ENTRIES[compute_dtype]
         b, l, d3 = qkv.shape
         d = d3 // 3
         assert d == heads * 32, "the attention kernel is built for head dim 32"
         qkv = _f32(qkv)
         out = torch.empty(b, l, d, device=qkv.device, dtype=torch.float32)
         lse = torch.empty(b, heads, l, device=qkv.device, dtype=torch.float32)
-        with profiler.region("lm_attention:fwd", flops=_attn_flops(b, heads, l, causal, 2), bound="mfma", dtype="f32"):
-            N.check(N.lib().smt_lm_attention_fwd(N.ptr(qkv), N.ptr(lens), N.ptr(out), N.ptr(lse), b, l, heads, int(causal),
-                                                 drop.key, N.ptr(drop.key_dev), drop.thresh, drop.scale, N.stream_ptr()), "smt_lm_attention_fwd")
+        with profiler.region(region + ":fwd", flops=_attn_flops(b, heads, l, causal, 2), bound="mfma", dtype=dtype):
+            N.check(getattr(N.lib(), fwd)(N.ptr(qkv), N.ptr(lens), N.ptr(out), N.ptr(lse), b, l, heads, int(causal),
+                                          drop.key, N.ptr(drop.key_dev), drop.thresh, drop.scale, N.stream_ptr()), fwd)
         ctx.save_for_backward(qkv, lens, out, lse)
-        ctx.meta = (heads, int(causal), drop)
+        ctx.meta = (heads, int(causal), drop, compute_dtype)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, lens, out, lse = ctx.saved_tensors
-        heads, causal, drop = ctx.meta
+        heads, causal, drop, compute_dtype = ctx.meta
+        _, bwd, region, dtype = _ATTN_ENTRIES[compute_dtype]
         b, l, _ = qkv.shape
         dqkv = torch.empty_like(qkv)
         delta = torch.empty_like(lse)
         dout = _f32(dout)
-        with profiler.region("lm_attention:bwd", flops=_attn_flops(b, heads, l, causal, 5), bound="mfma", dtype="f32"):
-            N.check(N.lib().smt_lm_attention_bwd(N.ptr(qkv), N.ptr(lens), N.ptr(out), N.ptr(lse), N.ptr(dout), N.ptr(dqkv),
-                                                 N.ptr(delta), b, l, heads, causal, drop.key, N.ptr(drop.key_dev), drop.thresh, drop.scale,
-                                                 N.stream_ptr()), "smt_lm_attention_bwd")
-        return dqkv, None, None, None, None
+        with profiler.region(region + ":bwd", flops=_attn_flops(b, heads, l, causal, 5), bound="mfma", dtype=dtype):
+            N.check(getattr(N.lib(), bwd)(N.ptr(qkv), N.ptr(lens), N.ptr(out), N.ptr(lse), N.ptr(dout), N.ptr(dqkv),
+                                          N.ptr(delta), b, l, heads, causal, drop.key, N.ptr(drop.key_dev), drop.thresh, drop.scale,
+                                          N.stream_ptr()), bwd)
+        return dqkv, None, None, None, None, None
 
 
-def attention(qkv, lens, heads, causal=True, drop=NO_DROP):
+def attention(qkv, lens, heads, causal=True, drop=NO_DROP, *, compute_dtype=torch.float32):
     """Self-attention core: qkv [batch, len, 3 dim] -> [batch, len, dim]; lens [batch] int32 (keys >= lens[b] masked) or
-    None; causal adds the triu(-inf, 1) mask of the reference's forward (:111)."""
+    None; causal adds the triu(-inf, 1) mask of the reference's forward (:111).  compute_dtype is the operand type of the
+    products: torch.float32, or torch.bfloat16 for the kernels on bf16 MFMAs (smt_lm_attention_bf16_*: tensors stay fp32,
+    the rounding points are listed in include/smt_hip.h)."""
+    if compute_dtype not in _ATTN_ENTRIES:
+        raise ValueError(f"attention: compute_dtype must be torch.float32 or torch.bfloat16 (got {compute_dtype!r})")
     if lens is not None:
         assert lens.dtype == torch.int32 and lens.is_cuda
-    return _Attention.apply(qkv, lens, heads, causal, drop)
+    return _Attention.apply(qkv, lens, heads, causal, drop, compute_dtype)
 
 
 class _AddLayerNorm(torch.autograd.Function):
