@@ -622,6 +622,21 @@ int smt_lm_attention_bf16_bwd(const float* qkv, const int* lens, const float* ct
                               float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
                               const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream);
 
+/* The attention core at head dim 32 or 64 (the reference's `nhead` with d_model / nhead = 64): the arguments of
+ * smt_lm_attention_fwd / _bwd, then head_dim and bf16 (0: the f32 products, non-zero: the bf16 products above).  Every
+ * "32" of the two descriptions above reads head_dim: qkv [batch, len, 3*heads*head_dim], head h at channel h*head_dim of
+ * each third, ctx [batch, len, heads*head_dim], scale 1/sqrt(head_dim), len * 3 * heads * head_dim < 2^31.  Masks,
+ * dropout indices and keys, lse, delta and the rounding points of the bf16 form do not depend on the head dim.
+ * head_dim = 32 is exactly the launches of the four entries above (which are calls of these two); any head_dim other than
+ * 32 or 64 is an argument error, with no launch. */
+int smt_lm_attention_hd_fwd(const float* qkv, const int* lens, float* ctx, float* lse, int batch, int len, int heads,
+                            int causal, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale,
+                            int head_dim, int bf16, smt_stream_t stream);
+int smt_lm_attention_hd_bwd(const float* qkv, const int* lens, const float* ctx, const float* lse, const float* dctx,
+                            float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
+                            const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, int head_dim, int bf16,
+                            smt_stream_t stream);
+
 /* y = LayerNorm(x + dropout(h + h_bias)) * gamma + beta over the last dim (TransformerEncoderLayer, norm_first = False):
  * h is the bias-free output of out_proj / linear2 and h_bias [dim] that projection's bias (NULL = none), so that the
  * bias gradient falls out of this kernel's backward instead of a separate reduction; with h = NULL the plain final
@@ -748,7 +763,7 @@ int smt_lm_linear_wgrad(const float* x, int64_t ld_x, const float* dy, int64_t l
                         int64_t rows, int n_in, int n_out, void* workspace, size_t workspace_bytes, smt_stream_t stream);
 
 /* Incremental decoding (TransformerLM.sample(causal=True)): one new token per step against a key/value cache.  fp32, eval
- * mode (no dropout), head dim 32, batch 1..32.  What changes from step to step -- the position, the tokens, the uniforms --
+ * mode (no dropout), head dim 32 (the _hd entries: 32 or 64), batch 1..32.  What changes from step to step -- the position, the tokens, the uniforms --
  * lives in device memory, so a step is a fixed sequence of launches with fixed arguments.  Like the dropout keys above,
  * the position comes twice: `pos` by value and `pos_dev`, a DEVICE pointer that overrides it when non-NULL.  A by-value
  * position outside the buffers is an argument error; with a device position the kernels return without touching memory.
@@ -772,6 +787,14 @@ int smt_lm_decode_linear(const float* x, const float* w, const float* bias, floa
 size_t smt_lm_decode_attention_workspace_bytes(int batch, int heads, int l_max);
 int smt_lm_decode_attention(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace, size_t workspace_bytes,
                             int batch, int heads, int l_max, int pos, const int* pos_dev, smt_stream_t stream);
+
+/* The same at head dim 32 or 64: qkv [batch, 3*heads*head_dim], caches [batch, heads, l_max, head_dim], ctx
+ * [batch, heads*head_dim], scale 1/sqrt(head_dim); the workspace holds 4 + head_dim floats per (batch, head, chunk), so its
+ * size depends on the head dim.  pos / pos_dev as above.  head_dim = 32 is the entry above; any other value than 32 or 64
+ * is an argument error (and a workspace size of 0). */
+size_t smt_lm_decode_attention_hd_workspace_bytes(int batch, int heads, int l_max, int head_dim);
+int smt_lm_decode_attention_hd(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace, size_t workspace_bytes,
+                               int batch, int heads, int l_max, int head_dim, int pos, const int* pos_dev, smt_stream_t stream);
 
 /* Inverse-CDF draw: p_i = exp((logits[b, i] - max_i) * inv_sigma), S = sum p_i, k = the smallest index whose cumulative sum
  * exceeds uniforms[pos, b] * S (if rounding leaves none: the last k with p_k > 0).  logits [batch, vocab], uniforms
@@ -798,6 +821,10 @@ int smt_lm_decode_sample_filtered(const float* logits, const float* uniforms, in
  * 1 <= len <= l_max; batch, heads and l_max bounded as in smt_lm_decode_attention. */
 int smt_lm_decode_prefill_kv(const float* qkv, float* k_cache, float* v_cache, int batch, int len, int heads, int l_max,
                              smt_stream_t stream);
+
+/* The same at head dim 32 or 64 (qkv [batch, len, 3*heads*head_dim], caches [batch, heads, l_max, head_dim]). */
+int smt_lm_decode_prefill_kv_hd(const float* qkv, float* k_cache, float* v_cache, int batch, int len, int heads, int l_max,
+                                int head_dim, smt_stream_t stream);
 
 /* pos_dev[0] += 1: the last launch of a step. */
 int smt_lm_decode_advance(int* pos_dev, smt_stream_t stream);

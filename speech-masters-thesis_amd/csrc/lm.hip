@@ -13,7 +13,7 @@
 //   lm_ce           masked mean cross-entropy + accuracy over the next-token logits              (transformer_lm.py:121-128)
 //   lm_focal/lm_mmi the other two losses of the config (loss_type focal | mmi), same conventions as lm_ce     (losses.py:8-103)
 //
-// Activations are [B, L, C] fp32 rows (the fp32 parity path; head dim 32, any L with L * 3 * heads * 32 < 2^31).  Dropout masks come from the
+// Activations are [B, L, C] fp32 rows (the fp32 parity path; head dim 32 or 64, any L with L * 3 * heads * dh < 2^31).  Dropout masks come from the
 // counter-based generator of include/smt_hip.h ("dropout"): keep(i) of the element's linear index under a per-site key,
 // so the backward kernels recompute them.
 #include <algorithm>
@@ -57,14 +57,14 @@ __global__ __launch_bounds__(256) void lm_embed_bwd_kernel(const long long* __re
 // ------------------------------------------------------------------------------------------------ attention
 // qkv [B, L, 3 d] (q | k | v, heads side by side inside each), ctx [B, L, d], lse [B, H, L] (log-sum-exp of the scaled,
 // masked scores).  Key j is visible to query i iff (j <= i or not causal) and j < lens[b].  Attention-weight dropout:
-// element index ((b H + h) L + i) L + j.  Head dim 32.  (Two earlier generations of these kernels ran on the VALU: K / V
-// staged in LDS with four lanes per query row was bound by the 128 B/clk LDS pipe -- every lane pulling the same 256 bytes
-// per key -- at 48 / 50 / 58 us for forward / dq / dkv at 8 x 16 x 258; broadcasting the rows through scalar loads instead
-// was bound by the scalar cache's miss latency, 70 / 50 / 63 us.)
-constexpr int LM_DH = 32;
+// element index ((b H + h) L + i) L + j.  Head dim DH = 32 NC, NC = 1 or 2 chunks of 32 channels.
+// (Two earlier generations of these kernels ran on the VALU: K / V staged in LDS with four lanes per query row was bound
+// by the 128 B/clk LDS pipe -- every lane pulling the same 256 bytes per key -- at 48 / 50 / 58 us for forward / dq / dkv
+// at 8 x 16 x 258; broadcasting the rows through scalar loads instead was bound by the scalar cache's miss latency,
+// 70 / 50 / 63 us.)
 // Longest sequence: the kernels walk the keys / queries in 32-row blocks (online softmax), so the only limit is the 32-bit
-// element offset inside one batch item's qkv block, len * 3 * heads * 32 < 2^31 (the reference's max_len is 5000).
-static inline bool lm_len_ok(int len, int heads) { return (long long)len * 3 * heads * LM_DH < (1ll << 31); }
+// element offset inside one batch item's qkv block, len * 3 * heads * dh < 2^31 (the reference's max_len is 5000).
+static inline bool lm_len_ok(int len, int heads, int dh) { return (long long)len * 3 * heads * dh < (1ll << 31); }
 
 // The attention kernels run on the f32-input matrix pipe (v_mfma_f32_32x32x2_f32: exact f32 products and sums at the
 // VALU's FLOP rate, but one operand register per 32 FMAs instead of one LDS read per FMA).  A workgroup owns 32 rows of
@@ -78,6 +78,11 @@ static inline bool lm_len_ok(int len, int heads) { return (long long)len * 3 * h
 // "row" = 16 consecutive channels [16 hh, 16 hh + 16) of row `col` (the contraction runs over channels), "column" =
 // channel `col` of the 16 rows at_acc_row(t, hh) (the contraction runs over rows).  Offsets are 32-bit element counts
 // from a wave-uniform base (64-bit per-lane address arithmetic cost more than the MFMAs in a first version).
+// Head dim 64 (NC = 2) keeps all of this and handles the channels in two chunks of 32: a contraction over channels (the
+// scores, dPd) takes two row fragments per operand -- channels [32 c + 16 hh, 32 c + 16 hh + 16) -- into ONE accumulator;
+// an output whose channels are the accumulator rows (ctx^T, dq^T, dk^T, dv^T) becomes two accumulators, fed by the column
+// fragments at channel col and col + 32 and merged one after the other.  With NC = 1 every chunk loop is one pass: the
+// head dim 32 kernels.
 typedef float f32x16v __attribute__((ext_vector_type(16)));
 constexpr int AT_W = 4;
 __device__ __forceinline__ int at_acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
@@ -99,6 +104,18 @@ __device__ __forceinline__ void at_col_frag(float (&r)[16], const float* __restr
     const int k = (t & 3) + 8 * (t >> 2);                     // compile time: k * pitch is a scalar
     r[t] = mat[first + k <= last ? base_off + (unsigned)k * pitch : last_off];
   }
+}
+template <int NC>
+__device__ __forceinline__ void at_row_frags(float (&r)[NC][16], const float* __restrict__ mat, unsigned pitch, int row, int last, int hh,
+                                             float mul) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) at_row_frag(r[c], mat + 32 * c, pitch, row, last, hh, mul);
+}
+template <int NC>
+__device__ __forceinline__ void at_col_frags(float (&r)[NC][16], const float* __restrict__ mat, unsigned pitch, int row0, int last, int col,
+                                             int hh) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) at_col_frag(r[c], mat, pitch, row0, last, col + 32 * c, hh);
 }
 __device__ __forceinline__ f32x16v at_mfma16(const float (&a)[16], const float (&b)[16], f32x16v c) {
 #pragma unroll
@@ -130,11 +147,19 @@ __device__ __forceinline__ f32x16v at_prod(const float (&a)[16], const float (&b
     return at_mfma16(a, b, c);
   }
 }
-// The scores a . b in base-2 units, s2 = log2(e) / sqrt(32): the f32 kernels fold s2 into one operand as they load it, the
+// a . b over all NC chunks of channels, into one accumulator
+template <bool BF, int NC>
+__device__ __forceinline__ f32x16v at_dot(const float (&a)[NC][16], const float (&b)[NC][16]) {
+  f32x16v acc = at_zero16();
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc = at_prod<BF>(a[c], b[c], acc);
+  return acc;
+}
+// The scores a . b in base-2 units, s2 = log2(e) / sqrt(dh): the f32 kernels fold s2 into one operand as they load it, the
 // bf16 kernels load both unscaled and multiply the f32 accumulator.
-template <bool BF>
-__device__ __forceinline__ f32x16v at_scores(const float (&a)[16], const float (&b)[16], float s2) {
-  f32x16v st = at_prod<BF>(a, b, at_zero16());
+template <bool BF, int NC>
+__device__ __forceinline__ f32x16v at_scores(const float (&a)[NC][16], const float (&b)[NC][16], float s2) {
+  f32x16v st = at_dot<BF, NC>(a, b);
   if constexpr (BF) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) st[i] *= s2;
@@ -142,11 +167,12 @@ __device__ __forceinline__ f32x16v at_scores(const float (&a)[16], const float (
   return st;
 }
 // Arithmetic of the bf16 instantiations (smt_lm_attention_bf16_*; include/smt_hip.h lists the rounding points): q, k, v and
-// dctx are rounded as loaded, unscaled, so that a bf16-representable input is used exactly; 1/sqrt(32) and log2(e)
+// dctx are rounded as loaded, unscaled, so that a bf16-representable input is used exactly; 1/sqrt(dh) and log2(e)
 // multiply the f32 score accumulator instead of the operand.  m, z, lse, delta, the rescales and every accumulator are
 // f32; p keep dscale and dS are rounded once, where they become an operand.
 // Sum the four waves' transposed accumulators (each scaled by its own `scale`) through LDS red [4][16][64]; wave w then
-// stores channel group w -- channels 8 w + 4 hh + {0..3} -- of the row this lane's column stands for, times mul.
+// stores channel group w -- channels 8 w + 4 hh + {0..3} -- of the row this lane's column stands for, times mul.  (One
+// call per 32-channel chunk, dst advanced by 32: the trailing barrier frees red for the next.)
 __device__ __forceinline__ void at_merge_store(float* red, const f32x16v& o, float scale, int w, int lane, int hh, float mul, bool live,
                                                float* __restrict__ dst) {
 #pragma unroll
@@ -184,7 +210,7 @@ __device__ __forceinline__ void at_keep16(float (&kf)[16], unsigned long long e_
 }
 constexpr float LM_LOG2E = 1.4426950408889634f;
 
-template <bool BF>
+template <bool BF, int NC>
 __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restrict__ qkv, const int* __restrict__ lens,
                                                           float* __restrict__ ctx, float* __restrict__ lse, int L, int H,
                                                           int causal, unsigned key, const unsigned* __restrict__ key_dev, unsigned thr, float dscale) {
@@ -192,26 +218,29 @@ __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restric
   __shared__ float red[AT_W * 16 * 64];
   __shared__ float red_m[AT_W][64], red_z[AT_W][64];
   const int qb = gridDim.x - 1 - blockIdx.x;                  // longest (last) query blocks first
-  const int b = blockIdx.y / H, h = blockIdx.y % H, d = H * LM_DH;
+  constexpr int DH = 32 * NC;
+  const int b = blockIdx.y / H, h = blockIdx.y % H, d = H * DH;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, col = lane & 31, hh = lane >> 5;
   const unsigned pitch = 3u * d;
-  const float* qm = qkv + (size_t)b * L * pitch + h * LM_DH;
+  const float* qm = qkv + (size_t)b * L * pitch + h * DH;
   const float* km = qm + d;
   const float* vm = qm + 2 * d;
   const int len = lens ? max(0, min(lens[b], L)) : L;
   const int q0 = qb * 32, qi = q0 + col, qc = min(qi, L - 1);
   const int kend = causal ? min(len, min(L, q0 + 32)) : len;  // keys any query of this block can see
-  const float s2 = rsqrtf((float)LM_DH) * LM_LOG2E;           // scores in base-2 units: exp2 is ONE instruction
-  float qf[16];
-  at_row_frag(qf, qm, pitch, qi, L - 1, hh, BF ? 1.f : s2);
-  f32x16v o = at_zero16();
+  const float s2 = rsqrtf((float)DH) * LM_LOG2E;              // scores in base-2 units: exp2 is ONE instruction
+  float qf[NC][16];
+  at_row_frags<NC>(qf, qm, pitch, qi, L - 1, hh, BF ? 1.f : s2);
+  f32x16v o[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) o[c] = at_zero16();
   float m = -INFINITY, z = 0.f;
   const unsigned long long e0 = (((unsigned long long)b * H + h) * L + qc) * L;
   for (int k0 = 32 * w; k0 < kend; k0 += 32 * AT_W) {
-    float kf[16], vf[16];
-    at_row_frag(kf, km, pitch, k0 + col, L - 1, hh, 1.f);
-    at_col_frag(vf, vm, pitch, k0, L - 1, col, hh);
-    f32x16v st = at_scores<BF>(kf, qf, s2);
+    float kf[NC][16], vf[NC][16];
+    at_row_frags<NC>(kf, km, pitch, k0 + col, L - 1, hh, 1.f);
+    at_col_frags<NC>(vf, vm, pitch, k0, L - 1, col, hh);
+    f32x16v st = at_scores<BF, NC>(kf, qf, s2);
     float mloc = -INFINITY;
     if (k0 + 32 <= kend && (!causal || k0 + 31 <= q0)) {      // uniform: every key of the block visible to every query
 #pragma unroll
@@ -229,7 +258,9 @@ __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restric
     const float corr = __builtin_amdgcn_exp2f(m - ms);        // m = -inf: 0
     z *= corr;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) o[i] *= corr;
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) o[c][i] *= corr;
     m = mn;
     float pk[16];
     at_keep16(pk, e0 + k0, hh, key, thr, dscale);
@@ -239,7 +270,8 @@ __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restric
       z += p;
       pk[i] *= p;
     }
-    o = at_prod<BF>(vf, pk, o);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) o[c] = at_prod<BF>(vf[c], pk, o[c]);
   }
   // merge the four waves' partial softmaxes (m is per query = the same in both lane halves; z is a per-half partial)
   red_m[w][lane] = m; red_z[w][lane] = z;
@@ -251,8 +283,10 @@ __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restric
     zz += red_m[k][lane] == -INFINITY ? 0.f : red_z[k][lane] * __builtin_amdgcn_exp2f(red_m[k][lane] - mm);
   zz += __shfl_xor(zz, 32, 64);
   const bool any = mm != -INFINITY;                           // at least one visible key
-  at_merge_store(red, o, (m == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m - mm), w, lane, hh, any ? 1.f / zz : 0.f, qi < L,
-                 ctx + ((size_t)b * L + qc) * d + h * LM_DH);
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    at_merge_store(red, o[c], (m == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m - mm), w, lane, hh, any ? 1.f / zz : 0.f, qi < L,
+                   ctx + ((size_t)b * L + qc) * d + h * DH + 32 * c);
   // lse is kept in BASE-2 units (log2 of the sum of 2^score): it is scratch between this kernel and the backward ones
   if (w == 0 && hh == 0 && qi < L) lse[((size_t)b * H + h) * L + qi] = any ? mm + __builtin_amdgcn_logf(zz) : 0.f;
 }
@@ -261,7 +295,7 @@ __global__ __launch_bounds__(256) void lm_attn_fwd_kernel(const float* __restric
 // dS_ij = P_ij (keep_ij dPd_ij - delta_i); dq_i = sum_j dS_ij k_j / sqrt(dh); dk_j = sum_i dS_ij q_i / sqrt(dh);
 // dv_j = sum_i P_ij keep_ij dctx_i.
 // dq: 32 queries per workgroup (the accumulator column): S^T = K Q^T, dPd^T = V dctx^T, dq^T += K^T dS^T; leaves delta.
-template <bool BF>
+template <bool BF, int NC>
 __global__ __launch_bounds__(256) void lm_attn_dq_kernel(const float* __restrict__ qkv, const int* __restrict__ lens,
                                                          const float* __restrict__ ctx, const float* __restrict__ lse,
                                                          const float* __restrict__ dctx, float* __restrict__ dqkv,
@@ -270,38 +304,43 @@ __global__ __launch_bounds__(256) void lm_attn_dq_kernel(const float* __restrict
   if (key_dev) key = *key_dev;                                // device-resident key (graph replay): overrides the by-value one
   __shared__ float red[AT_W * 16 * 64];
   const int qb = gridDim.x - 1 - blockIdx.x;
-  const int b = blockIdx.y / H, h = blockIdx.y % H, d = H * LM_DH;
+  constexpr int DH = 32 * NC;
+  const int b = blockIdx.y / H, h = blockIdx.y % H, d = H * DH;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, col = lane & 31, hh = lane >> 5;
   const unsigned pitch = 3u * d;
-  const float* qm = qkv + (size_t)b * L * pitch + h * LM_DH;
+  const float* qm = qkv + (size_t)b * L * pitch + h * DH;
   const float* km = qm + d;
   const float* vm = qm + 2 * d;
   const int len = lens ? max(0, min(lens[b], L)) : L;
   const int q0 = qb * 32, qi = q0 + col, qc = min(qi, L - 1);
   const int kend = causal ? min(len, min(L, q0 + 32)) : len;
-  const float sc = rsqrtf((float)LM_DH);
-  float qf[16], gf[16];
-  at_row_frag(qf, qm, pitch, qi, L - 1, hh, BF ? 1.f : sc * LM_LOG2E);   // base-2 scores, as in the forward (lse is base-2)
-  at_row_frag(gf, dctx + (size_t)b * L * d + h * LM_DH, d, qi, L - 1, hh, 1.f);
+  const float sc = rsqrtf((float)DH);
+  float qf[NC][16], gf[NC][16];
+  at_row_frags<NC>(qf, qm, pitch, qi, L - 1, hh, BF ? 1.f : sc * LM_LOG2E);   // base-2 scores, as in the forward (lse is base-2)
+  at_row_frags<NC>(gf, dctx + (size_t)b * L * d + h * DH, d, qi, L - 1, hh, 1.f);
   float dl = 0.f;
   {
-    float cf[16];
-    at_row_frag(cf, ctx + (size_t)b * L * d + h * LM_DH, d, qi, L - 1, hh, 1.f);
+    float cf[NC][16];
+    at_row_frags<NC>(cf, ctx + (size_t)b * L * d + h * DH, d, qi, L - 1, hh, 1.f);
 #pragma unroll
-    for (int t = 0; t < 16; ++t) dl = fmaf(gf[t], cf[t], dl);
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int t = 0; t < 16; ++t) dl = fmaf(gf[c][t], cf[c][t], dl);
     dl += __shfl_xor(dl, 32, 64);
   }
   if (w == 0 && hh == 0 && qi < L) delta[((size_t)b * H + h) * L + qi] = dl;
   const float li = lse[((size_t)b * H + h) * L + qc];
   const unsigned long long e0 = (((unsigned long long)b * H + h) * L + qc) * L;
-  f32x16v dq = at_zero16();
+  f32x16v dq[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) dq[c] = at_zero16();
   for (int k0 = 32 * w; k0 < kend; k0 += 32 * AT_W) {
-    float kf[16], vf[16], kc[16];
-    at_row_frag(kf, km, pitch, k0 + col, L - 1, hh, 1.f);
-    at_row_frag(vf, vm, pitch, k0 + col, L - 1, hh, 1.f);
-    at_col_frag(kc, km, pitch, k0, L - 1, col, hh);
-    const f32x16v st = at_scores<BF>(kf, qf, sc * LM_LOG2E);
-    const f32x16v dp = at_prod<BF>(vf, gf, at_zero16());
+    float kf[NC][16], vf[NC][16], kc[NC][16];
+    at_row_frags<NC>(kf, km, pitch, k0 + col, L - 1, hh, 1.f);
+    at_row_frags<NC>(vf, vm, pitch, k0 + col, L - 1, hh, 1.f);
+    at_col_frags<NC>(kc, km, pitch, k0, L - 1, col, hh);
+    const f32x16v st = at_scores<BF, NC>(kf, qf, sc * LM_LOG2E);
+    const f32x16v dp = at_dot<BF, NC>(vf, gf);
     float ds[16];
     at_keep16(ds, e0 + k0, hh, key, thr, dscale);
     if (k0 + 32 <= kend && (!causal || k0 + 31 <= q0)) {      // uniform: no mask inside the block
@@ -315,14 +354,17 @@ __global__ __launch_bounds__(256) void lm_attn_dq_kernel(const float* __restrict
         ds[i] = p * (ds[i] * dp[i] - dl);
       }
     }
-    dq = at_prod<BF>(kc, ds, dq);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) dq[c] = at_prod<BF>(kc[c], ds, dq[c]);
   }
-  at_merge_store(red, dq, 1.f, w, lane, hh, sc, qi < L, dqkv + ((size_t)b * L + qc) * pitch + h * LM_DH);
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    at_merge_store(red, dq[c], 1.f, w, lane, hh, sc, qi < L, dqkv + ((size_t)b * L + qc) * pitch + h * DH + 32 * c);
 }
 
 // dk, dv: 32 keys per workgroup (the accumulator column): S = Q K^T and dPd = dctx V^T with the queries in the accumulator
 // rows, then dv^T += dctx^T (P keep), dk^T += Q^T dS.  lse and delta of the 16 query rows a lane holds are loaded per block.
-template <bool BF>
+template <bool BF, int NC>
 __global__ __launch_bounds__(256) void lm_attn_dkv_kernel(const float* __restrict__ qkv, const int* __restrict__ lens,
                                                           const float* __restrict__ lse, const float* __restrict__ dctx,
                                                           const float* __restrict__ delta, float* __restrict__ dqkv, int L,
@@ -330,30 +372,33 @@ __global__ __launch_bounds__(256) void lm_attn_dkv_kernel(const float* __restric
   if (key_dev) key = *key_dev;                                // device-resident key (graph replay): overrides the by-value one
   __shared__ float red[AT_W * 16 * 64];
   const int kb = blockIdx.x;                                  // first key blocks see the most queries: longest first
-  const int b = blockIdx.y / H, h = blockIdx.y % H, d = H * LM_DH;
+  constexpr int DH = 32 * NC;
+  const int b = blockIdx.y / H, h = blockIdx.y % H, d = H * DH;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, col = lane & 31, hh = lane >> 5;
   const unsigned pitch = 3u * d;
-  const float* qm = qkv + (size_t)b * L * pitch + h * LM_DH;
-  const float* gm = dctx + (size_t)b * L * d + h * LM_DH;
+  const float* qm = qkv + (size_t)b * L * pitch + h * DH;
+  const float* gm = dctx + (size_t)b * L * d + h * DH;
   const float* lrow = lse + ((size_t)b * H + h) * L;
   const float* drow = delta + ((size_t)b * H + h) * L;
   const int len = lens ? max(0, min(lens[b], L)) : L;
   const int kj = kb * 32 + col, kc = min(kj, L - 1);
-  const float sc = rsqrtf((float)LM_DH);
-  float kf[16], vf[16];
-  at_row_frag(kf, qm + d, pitch, kj, L - 1, hh, BF ? 1.f : sc * LM_LOG2E);   // f32: 1/sqrt(dh) and the base-2 conversion folded into the key
-  at_row_frag(vf, qm + 2 * d, pitch, kj, L - 1, hh, 1.f);
-  f32x16v dk = at_zero16(), dv = at_zero16();
+  const float sc = rsqrtf((float)DH);
+  float kf[NC][16], vf[NC][16];
+  at_row_frags<NC>(kf, qm + d, pitch, kj, L - 1, hh, BF ? 1.f : sc * LM_LOG2E);   // f32: 1/sqrt(dh) and the base-2 conversion folded into the key
+  at_row_frags<NC>(vf, qm + 2 * d, pitch, kj, L - 1, hh, 1.f);
+  f32x16v dk[NC], dv[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) { dk[c] = at_zero16(); dv[c] = at_zero16(); }
   const unsigned long long e0 = ((unsigned long long)b * H + h) * L;
   if (kb * 32 < len) {                                        // uniform: any visible key in this block at all?
     for (int q0 = (causal ? kb * 32 : 0) + 32 * w; q0 < L; q0 += 32 * AT_W) {
-      float qa[16], ga[16], qc[16], gc[16];
-      at_row_frag(qa, qm, pitch, q0 + col, L - 1, hh, 1.f);
-      at_row_frag(ga, gm, d, q0 + col, L - 1, hh, 1.f);
-      at_col_frag(qc, qm, pitch, q0, L - 1, col, hh);
-      at_col_frag(gc, gm, d, q0, L - 1, col, hh);
-      const f32x16v st = at_scores<BF>(qa, kf, sc * LM_LOG2E);
-      const f32x16v dp = at_prod<BF>(ga, vf, at_zero16());
+      float qa[NC][16], ga[NC][16], qc[NC][16], gc[NC][16];
+      at_row_frags<NC>(qa, qm, pitch, q0 + col, L - 1, hh, 1.f);
+      at_row_frags<NC>(ga, gm, d, q0 + col, L - 1, hh, 1.f);
+      at_col_frags<NC>(qc, qm, pitch, q0, L - 1, col, hh);
+      at_col_frags<NC>(gc, gm, d, q0, L - 1, col, hh);
+      const f32x16v st = at_scores<BF, NC>(qa, kf, sc * LM_LOG2E);
+      const f32x16v dp = at_dot<BF, NC>(ga, vf);
       float pk[16], ds[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
@@ -362,13 +407,18 @@ __global__ __launch_bounds__(256) void lm_attn_dkv_kernel(const float* __restric
         pk[i] = p * lm_keep((e0 + qrc) * L + kc, key, thr, dscale);
         ds[i] = pk[i] * dp[i] - p * drow[qrc];
       }
-      dv = at_prod<BF>(gc, pk, dv);
-      dk = at_prod<BF>(qc, ds, dk);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        dv[c] = at_prod<BF>(gc[c], pk, dv[c]);
+        dk[c] = at_prod<BF>(qc[c], ds, dk[c]);
+      }
     }
   }
-  float* dst = dqkv + ((size_t)b * L + kc) * pitch + h * LM_DH;
-  at_merge_store(red, dk, 1.f, w, lane, hh, sc, kj < L, dst + d);
-  at_merge_store(red, dv, 1.f, w, lane, hh, 1.f, kj < L, dst + 2 * d);
+  float* dst = dqkv + ((size_t)b * L + kc) * pitch + h * DH;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) at_merge_store(red, dk[c], 1.f, w, lane, hh, sc, kj < L, dst + d + 32 * c);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) at_merge_store(red, dv[c], 1.f, w, lane, hh, 1.f, kj < L, dst + 2 * d + 32 * c);
 }
 
 // ------------------------------------------------------------------------------------------------ add + LayerNorm
@@ -883,62 +933,86 @@ extern "C" int smt_lm_embed_bwd(const int64_t* tokens, const float* dout, float*
   return 0;
 }
 
-// One launcher per pass for both operand types: the argument checks, the grid and the kernels' arguments are the same.
-template <bool BF>
+// One launcher per pass for every operand type and head dim: the argument checks, the grid and the kernels' arguments are the same.
+template <bool BF, int NC>
 static int lm_attention_fwd_launch(const char* name, const float* qkv, const int* lens, float* ctx, float* lse, int batch, int len, int heads,
                                    int causal, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (batch <= 0 || len <= 0) return 0;
-  SMT_CHECK_ARG(qkv && ctx && lse, "%s: null pointer", name);
-  SMT_CHECK_ARG(heads >= 1 && lm_len_ok(len, heads), "%s: len * 3 * heads * 32 must be < 2^31 (len %d, heads %d)", name, len, heads);
+  SMT_CHECK_ARG(heads >= 1 && lm_len_ok(len, heads, 32 * NC), "%s: len * 3 * heads * %d must be < 2^31 (len %d, heads %d)", name, 32 * NC, len, heads);
   SMT_CHECK_ARG((long long)batch * heads <= 65535, "%s: batch * heads must be <= 65535", name);
-  lm_attn_fwd_kernel<BF><<<dim3((len + 31) / 32, batch * heads), 256, 0, stream>>>(qkv, lens, ctx, lse, len, heads, causal, drop_key, drop_key_dev,
-                                                                               drop_thresh16, drop_scale);
+  lm_attn_fwd_kernel<BF, NC><<<dim3((len + 31) / 32, batch * heads), 256, 0, stream>>>(qkv, lens, ctx, lse, len, heads, causal, drop_key, drop_key_dev,
+                                                                                   drop_thresh16, drop_scale);
   SMT_CHECK_LAUNCH(BF ? "lm_attention_bf16_fwd" : "lm_attention_fwd");
   return 0;
 }
 
-template <bool BF>
+template <bool BF, int NC>
 static int lm_attention_bwd_launch(const char* name, const float* qkv, const int* lens, const float* ctx, const float* lse, const float* dctx,
                                    float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
                                    const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (batch <= 0 || len <= 0) return 0;
-  SMT_CHECK_ARG(qkv && ctx && lse && dctx && dqkv && delta, "%s: null pointer", name);
-  SMT_CHECK_ARG(heads >= 1 && lm_len_ok(len, heads), "%s: len * 3 * heads * 32 must be < 2^31 (len %d, heads %d)", name, len, heads);
+  SMT_CHECK_ARG(heads >= 1 && lm_len_ok(len, heads, 32 * NC), "%s: len * 3 * heads * %d must be < 2^31 (len %d, heads %d)", name, 32 * NC, len, heads);
   SMT_CHECK_ARG((long long)batch * heads <= 65535, "%s: batch * heads must be <= 65535", name);
   const dim3 grid((len + 31) / 32, batch * heads);
-  lm_attn_dq_kernel<BF><<<grid, 256, 0, stream>>>(qkv, lens, ctx, lse, dctx, dqkv, delta, len, heads, causal, drop_key, drop_key_dev, drop_thresh16,
-                                                drop_scale);
+  lm_attn_dq_kernel<BF, NC><<<grid, 256, 0, stream>>>(qkv, lens, ctx, lse, dctx, dqkv, delta, len, heads, causal, drop_key, drop_key_dev, drop_thresh16,
+                                                    drop_scale);
   SMT_CHECK_LAUNCH(BF ? "lm_attention_bf16_dq" : "lm_attention_dq");
-  lm_attn_dkv_kernel<BF><<<grid, 256, 0, stream>>>(qkv, lens, lse, dctx, delta, dqkv, len, heads, causal, drop_key, drop_key_dev, drop_thresh16,
-                                                 drop_scale);
+  lm_attn_dkv_kernel<BF, NC><<<grid, 256, 0, stream>>>(qkv, lens, lse, dctx, delta, dqkv, len, heads, causal, drop_key, drop_key_dev, drop_thresh16,
+                                                     drop_scale);
   SMT_CHECK_LAUNCH(BF ? "lm_attention_bf16_dkv" : "lm_attention_dkv");
   return 0;
 }
 
+extern "C" int smt_lm_attention_hd_fwd(const float* qkv, const int* lens, float* ctx, float* lse, int batch, int len, int heads,
+                                       int causal, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale,
+                                       int head_dim, int bf16, smt_stream_t stream) {
+  const char* name = "smt_lm_attention_hd_fwd";
+  SMT_CHECK_ARG(head_dim == 32 || head_dim == 64, "%s: head dim must be 32 or 64 (got %d)", name, head_dim);
+  if (batch <= 0 || len <= 0) return 0;
+  SMT_CHECK_ARG(qkv && ctx && lse, "%s: null pointer", name);
+#define LM_ATTN_FWD(BF, NC) \
+  lm_attention_fwd_launch<BF, NC>(name, qkv, lens, ctx, lse, batch, len, heads, causal, drop_key, drop_key_dev, drop_thresh16, drop_scale, stream)
+  if (head_dim == 32) return bf16 ? LM_ATTN_FWD(true, 1) : LM_ATTN_FWD(false, 1);
+  return bf16 ? LM_ATTN_FWD(true, 2) : LM_ATTN_FWD(false, 2);
+#undef LM_ATTN_FWD
+}
+extern "C" int smt_lm_attention_hd_bwd(const float* qkv, const int* lens, const float* ctx, const float* lse, const float* dctx,
+                                       float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
+                                       const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, int head_dim, int bf16,
+                                       smt_stream_t stream) {
+  const char* name = "smt_lm_attention_hd_bwd";
+  SMT_CHECK_ARG(head_dim == 32 || head_dim == 64, "%s: head dim must be 32 or 64 (got %d)", name, head_dim);
+  if (batch <= 0 || len <= 0) return 0;
+  SMT_CHECK_ARG(qkv && ctx && lse && dctx && dqkv && delta, "%s: null pointer", name);
+#define LM_ATTN_BWD(BF, NC)                                                                                                              \
+  lm_attention_bwd_launch<BF, NC>(name, qkv, lens, ctx, lse, dctx, dqkv, delta, batch, len, heads, causal, drop_key, drop_key_dev, drop_thresh16, \
+                                  drop_scale, stream)
+  if (head_dim == 32) return bf16 ? LM_ATTN_BWD(true, 1) : LM_ATTN_BWD(false, 1);
+  return bf16 ? LM_ATTN_BWD(true, 2) : LM_ATTN_BWD(false, 2);
+#undef LM_ATTN_BWD
+}
+
+// the head dim 32 entries: the same launches through the entries above
 extern "C" int smt_lm_attention_fwd(const float* qkv, const int* lens, float* ctx, float* lse, int batch, int len, int heads,
                                     int causal, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream) {
-  return lm_attention_fwd_launch<false>("smt_lm_attention_fwd", qkv, lens, ctx, lse, batch, len, heads, causal, drop_key, drop_key_dev,
-                                        drop_thresh16, drop_scale, stream);
+  return smt_lm_attention_hd_fwd(qkv, lens, ctx, lse, batch, len, heads, causal, drop_key, drop_key_dev, drop_thresh16, drop_scale, 32, 0, stream);
 }
 extern "C" int smt_lm_attention_bf16_fwd(const float* qkv, const int* lens, float* ctx, float* lse, int batch, int len, int heads,
                                          int causal, uint32_t drop_key, const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale,
                                          smt_stream_t stream) {
-  return lm_attention_fwd_launch<true>("smt_lm_attention_bf16_fwd", qkv, lens, ctx, lse, batch, len, heads, causal, drop_key, drop_key_dev,
-                                       drop_thresh16, drop_scale, stream);
+  return smt_lm_attention_hd_fwd(qkv, lens, ctx, lse, batch, len, heads, causal, drop_key, drop_key_dev, drop_thresh16, drop_scale, 32, 1, stream);
 }
 extern "C" int smt_lm_attention_bwd(const float* qkv, const int* lens, const float* ctx, const float* lse, const float* dctx,
                                     float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
                                     const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream) {
-  return lm_attention_bwd_launch<false>("smt_lm_attention_bwd", qkv, lens, ctx, lse, dctx, dqkv, delta, batch, len, heads, causal, drop_key,
-                                        drop_key_dev, drop_thresh16, drop_scale, stream);
+  return smt_lm_attention_hd_bwd(qkv, lens, ctx, lse, dctx, dqkv, delta, batch, len, heads, causal, drop_key, drop_key_dev, drop_thresh16, drop_scale,
+                                 32, 0, stream);
 }
 extern "C" int smt_lm_attention_bf16_bwd(const float* qkv, const int* lens, const float* ctx, const float* lse, const float* dctx,
                                          float* dqkv, float* delta, int batch, int len, int heads, int causal, uint32_t drop_key,
                                          const uint32_t* drop_key_dev, uint32_t drop_thresh16, float drop_scale, smt_stream_t stream) {
-  return lm_attention_bwd_launch<true>("smt_lm_attention_bf16_bwd", qkv, lens, ctx, lse, dctx, dqkv, delta, batch, len, heads, causal, drop_key,
-                                       drop_key_dev, drop_thresh16, drop_scale, stream);
+  return smt_lm_attention_hd_bwd(qkv, lens, ctx, lse, dctx, dqkv, delta, batch, len, heads, causal, drop_key, drop_key_dev, drop_thresh16, drop_scale,
+                                 32, 1, stream);
 }
 
 extern "C" int smt_lm_add_ln_fwd(const float* x, const float* h, const float* h_bias, const float* gamma, const float* beta, float* y,

@@ -1,9 +1,9 @@
 // Incremental decoding of the causal TransformerLM (TransformerLM.sample(causal=True)): one new token per step against a
-// key/value cache, batch 1..32, fp32, eval mode (no dropout anywhere).
+// key/value cache, batch 1..32, fp32, eval mode (no dropout anywhere), head dim 32 or 64.
 //
 //   lm_decode_embed      emb[tokens[b, pos]] * sqrt(d) + pe[pos]
 //   lm_decode_linear     out[B, N] = x[B, K] W[N, K]^T (+ bias) (ReLU): the weights are streamed once, B <= 32 rows ride along
-//   lm_decode_attention  this step's k / v rows into the cache, softmax(q K[0..pos]^T / sqrt(32)) V[0..pos]
+//   lm_decode_attention  this step's k / v rows into the cache, softmax(q K[0..pos]^T / sqrt(dh)) V[0..pos]
 //   lm_decode_sample     inverse-CDF draw from softmax(logits / sigma) with a uniform number from device memory
 //   lm_decode_sample_filtered  the same draw over the top-k / nucleus (top-p) prefix of the codes ordered by logit
 //   lm_decode_prefill_kv the keys / values of a whole prompt (batched in-projection) into cache rows 0..len-1
@@ -20,9 +20,9 @@
 
 namespace smt {
 
-constexpr int DEC_DH = 32;                   // head dim, as in lm.hip
 constexpr int DEC_CHUNK = 256;               // cache rows per workgroup of the attention kernel
-constexpr int DEC_PART = 36;                 // floats per partial softmax: m, z, 2 unused, o[32] (16-byte aligned)
+constexpr int dec_part(int dh) { return 4 + dh; }   // floats per partial softmax: m, z, 2 unused, o[dh] (16-byte aligned)
+static inline bool dec_dh_ok(int dh) { return dh == 32 || dh == 64; }   // head dims, as in lm.hip
 constexpr int DEC_ROWS = 8;                  // output columns per workgroup of the linear kernel
 constexpr int DEC_KW = 128;                  // contraction elements per wave of the linear kernel (two per lane)
 constexpr int DEC_KMAX = 16 * DEC_KW;        // ... and per launch (16 waves)
@@ -116,13 +116,17 @@ __global__ __launch_bounds__(MAXT) void lm_decode_linear_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------ attention over the cache
-// One (batch, head) scans contiguous 128-byte rows of K and V [B, H, l_max, 32].  Workgroup (s, bh) takes cache rows
-// [256 s, 256 s + 256) up to pos; eight lanes share a row (16 bytes each: a wave loads 8 rows = 1 KiB per instruction, four
-// K and four V loads in flight), so a score costs three shuffles and the V row needs none; every lane group keeps its own
-// running maximum / sum / four output channels, merged over the eight groups of a wave by shuffles, over the four waves
-// through LDS in wave order, and over the workgroups by lm_decode_attn_merge_kernel in chunk order.  The step's own k / v
-// rows come from qkv (one wave stores them to the cache; no value read from cache row pos is used in this launch), rows
-// beyond pos are never read.
+// One (batch, head) scans contiguous rows of K and V [B, H, l_max, DH] (128 bytes at DH = 32, 256 at 64).  Workgroup (s, bh)
+// takes cache rows [256 s, 256 s + 256) up to pos; LPR = DH / 4 lanes share a row, 16 bytes each, so a wave loads
+// G = 64 / LPR rows = 1 KiB per instruction whatever the head dim, and takes 32 rows per trip: U = 32 / G K loads and as
+// many V loads in flight (4 + 4 at DH = 32, 8 + 8 at 64).  A score costs log2 LPR shuffles and the V row needs none; every
+// lane group keeps its own running maximum / sum / four output channels, merged over the G groups of a wave by shuffles,
+// over the four waves through LDS in wave order, and over the workgroups by lm_decode_attn_merge_kernel in chunk order.
+// (DH = 64 with 8 lanes per row and two f32x4 each would keep the shuffle counts of DH = 32, but a lane would then read
+// 32 bytes at a 256-byte stride and carry eight output channels through every merge; 16 lanes keep the per-lane state,
+// the 16-byte contiguous-per-lane load and the 1 KiB per instruction, for one more score shuffle and one fewer group merge.)
+// The step's own k / v rows come from qkv (one wave stores them to the cache; no value read from cache row pos is used in
+// this launch), rows beyond pos are never read.
 struct DecAcc { float m, z; f32x4 o; };
 __device__ __forceinline__ void dec_merge(DecAcc& a, float m2, float z2, const f32x4& o2) {
   const float mn = fmaxf(a.m, m2), ms = (mn == -INFINITY) ? 0.f : mn;
@@ -132,47 +136,48 @@ __device__ __forceinline__ void dec_merge(DecAcc& a, float m2, float z2, const f
   a.m = mn;
 }
 
+template <int DH>
 __global__ __launch_bounds__(256) void lm_decode_attn_kernel(const float* __restrict__ qkv, float* kcache, float* vcache,
                                                              float* __restrict__ ctx, float* __restrict__ part, int H, int l_max,
                                                              int nsplit, int pos, const int* __restrict__ pos_dev) {
+  constexpr int LPR = DH / 4, G = 64 / LPR, U = 32 / G;        // lanes per row, rows per load instruction, loads per trip
   if (pos_dev) pos = *pos_dev;
   if (pos < 0 || pos >= l_max) return;
-  const int s = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H, d = H * DEC_DH;
+  const int s = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H, d = H * DH;
   const int c0 = s * DEC_CHUNK;
   if (c0 > pos) return;                                       // uniform: no visible row in this chunk (the merge skips it too)
-  __shared__ float red[4][8][6];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 3, c = lane & 7;
-  const float* qrow = qkv + (size_t)b * 3 * d + h * DEC_DH + 4 * c;
-  const f32x4 q = *(const f32x4*)qrow * (rsqrtf((float)DEC_DH) * DEC_LOG2E);   // base-2 scores: exp2 is one instruction
+  __shared__ float red[4][LPR][6];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane / LPR, c = lane % LPR;
+  const float* qrow = qkv + (size_t)b * 3 * d + h * DH + 4 * c;
+  const f32x4 q = *(const f32x4*)qrow * (rsqrtf((float)DH) * DEC_LOG2E);   // base-2 scores: exp2 is one instruction
   const f32x4 kn = *(const f32x4*)(qrow + d), vn = *(const f32x4*)(qrow + 2 * d);
-  float* kb = kcache + (size_t)bh * l_max * DEC_DH + 4 * c;
-  float* vb = vcache + (size_t)bh * l_max * DEC_DH + 4 * c;
+  float* kb = kcache + (size_t)bh * l_max * DH + 4 * c;
+  float* vb = vcache + (size_t)bh * l_max * DH + 4 * c;
   if (pos - c0 < DEC_CHUNK && w == 0 && g == 0) {             // the chunk that holds row pos
-    *(f32x4*)(kb + (size_t)pos * DEC_DH) = kn;
-    *(f32x4*)(vb + (size_t)pos * DEC_DH) = vn;
+    *(f32x4*)(kb + (size_t)pos * DH) = kn;
+    *(f32x4*)(vb + (size_t)pos * DH) = vn;
   }
   const int end = min(pos, c0 + DEC_CHUNK - 1);               // last visible row of this chunk
   const int before = max(pos - 1, 0);
   DecAcc a{-INFINITY, 0.f, f32x4{0.f, 0.f, 0.f, 0.f}};
   for (int r0 = c0 + 32 * w; r0 <= end; r0 += 128) {
-    f32x4 kf[4], vf[4];
-    float sc[4];
+    f32x4 kf[U], vf[U];
+    float sc[U];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int row = min(r0 + 8 * u + g, end);
-      const size_t off = (size_t)(row == pos ? before : row) * DEC_DH;   // row pos: a load that is thrown away, from a row < pos (or row 0)
+    for (int u = 0; u < U; ++u) {
+      const int row = min(r0 + G * u + g, end);
+      const size_t off = (size_t)(row == pos ? before : row) * DH;   // row pos: a load that is thrown away, from a row < pos (or row 0)
       kf[u] = *(const f32x4*)(kb + off);
       vf[u] = *(const f32x4*)(vb + off);
       if (row == pos) { kf[u] = kn; vf[u] = vn; }
     }
     float mloc = -INFINITY;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
+    for (int u = 0; u < U; ++u) {
       float t = fmaf(q.x, kf[u].x, fmaf(q.y, kf[u].y, fmaf(q.z, kf[u].z, q.w * kf[u].w)));
-      t += __shfl_xor(t, 1, 64);
-      t += __shfl_xor(t, 2, 64);
-      t += __shfl_xor(t, 4, 64);
-      sc[u] = (r0 + 8 * u + g <= end) ? t : -INFINITY;
+#pragma unroll
+      for (int off = 1; off < LPR; off <<= 1) t += __shfl_xor(t, off, 64);
+      sc[u] = (r0 + G * u + g <= end) ? t : -INFINITY;
       mloc = fmaxf(mloc, sc[u]);
     }
     const float mn = fmaxf(a.m, mloc), ms = (mn == -INFINITY) ? 0.f : mn;
@@ -181,14 +186,14 @@ __global__ __launch_bounds__(256) void lm_decode_attn_kernel(const float* __rest
     a.o *= corr;
     a.m = mn;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
+    for (int u = 0; u < U; ++u) {
       const float p = __builtin_amdgcn_exp2f(sc[u] - ms);     // masked: exp2(-inf) = 0
       a.z += p;
       a.o += vf[u] * p;
     }
   }
 #pragma unroll
-  for (int off = 8; off < 64; off <<= 1) {
+  for (int off = LPR; off < 64; off <<= 1) {
     const float m2 = __shfl_xor(a.m, off, 64), z2 = __shfl_xor(a.z, off, 64);
     f32x4 o2;
     o2.x = __shfl_xor(a.o.x, off, 64); o2.y = __shfl_xor(a.o.y, off, 64);
@@ -206,9 +211,9 @@ __global__ __launch_bounds__(256) void lm_decode_attn_kernel(const float* __rest
     for (int ww = 1; ww < 4; ++ww)
       dec_merge(t, red[ww][c][0], red[ww][c][1], f32x4{red[ww][c][2], red[ww][c][3], red[ww][c][4], red[ww][c][5]});
     if (nsplit == 1) {
-      *(f32x4*)(ctx + (size_t)b * d + h * DEC_DH + 4 * c) = t.o * (1.f / t.z);    // row 0 is always visible: z > 0
+      *(f32x4*)(ctx + (size_t)b * d + h * DH + 4 * c) = t.o * (1.f / t.z);    // row 0 is always visible: z > 0
     } else {
-      float* dst = part + ((size_t)bh * nsplit + s) * DEC_PART;
+      float* dst = part + ((size_t)bh * nsplit + s) * dec_part(DH);
       if (c == 0) { dst[0] = t.m; dst[1] = t.z; }
       *(f32x4*)(dst + 4 + 4 * c) = t.o;
     }
@@ -216,23 +221,25 @@ __global__ __launch_bounds__(256) void lm_decode_attn_kernel(const float* __rest
 }
 
 // ctx = sum over the chunks 0 .. pos / 256, in chunk order, of the partial softmaxes; a thread per (batch, head, channel)
+template <int DH>
 __global__ __launch_bounds__(256) void lm_decode_attn_merge_kernel(const float* __restrict__ part, float* __restrict__ ctx, int BH,
                                                                    int l_max, int nsplit, int pos, const int* __restrict__ pos_dev) {
+  constexpr int PART = dec_part(DH);
   if (pos_dev) pos = *pos_dev;
   if (pos < 0 || pos >= l_max) return;
-  const int t = blockIdx.x * 256 + threadIdx.x, bh = t >> 5, c = t & 31;
+  const int t = blockIdx.x * 256 + threadIdx.x, bh = t / DH, c = t % DH;
   if (bh >= BH) return;
   const int ns = min(nsplit, pos / DEC_CHUNK + 1);
-  const float* p = part + (size_t)bh * nsplit * DEC_PART;
+  const float* p = part + (size_t)bh * nsplit * PART;
   float mm = -INFINITY;
-  for (int s = 0; s < ns; ++s) mm = fmaxf(mm, p[s * DEC_PART]);
+  for (int s = 0; s < ns; ++s) mm = fmaxf(mm, p[s * PART]);
   float z = 0.f, o = 0.f;
   for (int s = 0; s < ns; ++s) {
-    const float e = __builtin_amdgcn_exp2f(p[s * DEC_PART] - mm);
-    z = fmaf(p[s * DEC_PART + 1], e, z);
-    o = fmaf(p[s * DEC_PART + 4 + c], e, o);
+    const float e = __builtin_amdgcn_exp2f(p[s * PART] - mm);
+    z = fmaf(p[s * PART + 1], e, z);
+    o = fmaf(p[s * PART + 4 + c], e, o);
   }
-  ctx[(size_t)bh * DEC_DH + c] = o / z;                       // [B, H * 32]: (b H + h) * 32 + c
+  ctx[(size_t)bh * DH + c] = o / z;                           // [B, H * DH]: (b H + h) * DH + c
 }
 
 // ------------------------------------------------------------------------------------------------ sampler
@@ -407,16 +414,19 @@ __global__ __launch_bounds__(64) void lm_decode_sample_filtered_kernel(const flo
 }
 
 // ------------------------------------------------------------------------------------------------ prompt keys / values
-// The k and v thirds of qkv [B, L, 3 H 32] (what the batched in-projection of a prompt produces) into rows 0..L-1 of the caches
-// [B, H, l_max, 32]: a thread moves 16 bytes of k and 16 of v; consecutive threads write consecutive 16 bytes of a (batch,
-// head)'s cache rows (a wave stores 1 KiB contiguous) and read 128-byte pieces of the qkv rows.  Rows >= L are not touched.
+// The k and v thirds of qkv [B, L, 3 H DH] (what the batched in-projection of a prompt produces) into rows 0..L-1 of the caches
+// [B, H, l_max, DH]: a thread moves 16 bytes of k and 16 of v, DH / 4 threads a row; consecutive threads write consecutive
+// 16 bytes of a (batch, head)'s cache rows (a wave stores 1 KiB contiguous) and read 4 DH-byte pieces of the qkv rows.
+// Rows >= L are not touched.
+template <int DH>
 __global__ __launch_bounds__(256) void lm_decode_prefill_kv_kernel(const float* __restrict__ qkv, float* __restrict__ kcache,
                                                                    float* __restrict__ vcache, int L, int H, int l_max) {
-  const int t = blockIdx.x * 256 + threadIdx.x, row = t >> 3, c = t & 7;
+  constexpr int LPR = DH / 4;
+  const int t = blockIdx.x * 256 + threadIdx.x, row = t / LPR, c = t % LPR;
   if (row >= L) return;
-  const int bh = blockIdx.y, b = bh / H, h = bh % H, d = H * DEC_DH;
-  const float* src = qkv + ((size_t)b * L + row) * 3 * d + d + h * DEC_DH + 4 * c;
-  const size_t dst = ((size_t)bh * l_max + row) * DEC_DH + 4 * c;
+  const int bh = blockIdx.y, b = bh / H, h = bh % H, d = H * DH;
+  const float* src = qkv + ((size_t)b * L + row) * 3 * d + d + h * DH + 4 * c;
+  const size_t dst = ((size_t)bh * l_max + row) * DH + 4 * c;
   const f32x4 kk = *(const f32x4*)src, vv = *(const f32x4*)(src + d);
   *(f32x4*)(kcache + dst) = kk;
   *(f32x4*)(vcache + dst) = vv;
@@ -476,29 +486,46 @@ extern "C" int smt_lm_decode_linear(const float* x, const float* w, const float*
   return 0;
 }
 
+extern "C" size_t smt_lm_decode_attention_hd_workspace_bytes(int batch, int heads, int l_max, int head_dim) {
+  if (batch <= 0 || heads <= 0 || l_max <= 0 || !dec_dh_ok(head_dim) || dec_splits(l_max) == 1) return 0;
+  return (size_t)batch * heads * dec_splits(l_max) * dec_part(head_dim) * sizeof(float);
+}
 extern "C" size_t smt_lm_decode_attention_workspace_bytes(int batch, int heads, int l_max) {
-  if (batch <= 0 || heads <= 0 || l_max <= 0 || dec_splits(l_max) == 1) return 0;
-  return (size_t)batch * heads * dec_splits(l_max) * DEC_PART * sizeof(float);
+  return smt_lm_decode_attention_hd_workspace_bytes(batch, heads, l_max, 32);
 }
 
-extern "C" int smt_lm_decode_attention(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace,
-                                       size_t workspace_bytes, int batch, int heads, int l_max, int pos, const int* pos_dev,
-                                       smt_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SMT_CHECK_ARG(qkv && k_cache && v_cache && ctx, "smt_lm_decode_attention: null pointer");
-  SMT_CHECK_ARG(batch >= 1 && batch <= 32 && heads >= 1 && l_max >= 1, "smt_lm_decode_attention: batch must be 1..32, heads and l_max positive");
-  SMT_CHECK_ARG((long long)batch * heads <= 65535 && (long long)l_max * DEC_DH < (1ll << 31), "smt_lm_decode_attention: batch * heads <= 65535, l_max * 32 < 2^31");
-  SMT_CHECK_ARG(pos_dev || (pos >= 0 && pos < l_max), "smt_lm_decode_attention: pos %d outside the cache (%d rows)", pos, l_max);
-  const int nsplit = dec_splits(l_max);
-  SMT_CHECK_ARG(nsplit == 1 || (workspace && workspace_bytes >= smt_lm_decode_attention_workspace_bytes(batch, heads, l_max)),
-                "smt_lm_decode_attention: workspace too small");
-  lm_decode_attn_kernel<<<dim3(nsplit, batch * heads), 256, 0, stream>>>(qkv, k_cache, v_cache, ctx, (float*)workspace, heads, l_max, nsplit, pos, pos_dev);
+template <int DH>
+static int dec_attention_launch(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace, int batch, int heads,
+                                int l_max, int nsplit, int pos, const int* pos_dev, hipStream_t stream) {
+  lm_decode_attn_kernel<DH><<<dim3(nsplit, batch * heads), 256, 0, stream>>>(qkv, k_cache, v_cache, ctx, (float*)workspace, heads, l_max, nsplit, pos, pos_dev);
   SMT_CHECK_LAUNCH("lm_decode_attention");
   if (nsplit > 1) {
-    lm_decode_attn_merge_kernel<<<(batch * heads * DEC_DH + 255) / 256, 256, 0, stream>>>((const float*)workspace, ctx, batch * heads, l_max, nsplit, pos, pos_dev);
+    lm_decode_attn_merge_kernel<DH><<<(batch * heads * DH + 255) / 256, 256, 0, stream>>>((const float*)workspace, ctx, batch * heads, l_max, nsplit, pos, pos_dev);
     SMT_CHECK_LAUNCH("lm_decode_attention_merge");
   }
   return 0;
+}
+
+extern "C" int smt_lm_decode_attention_hd(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace,
+                                          size_t workspace_bytes, int batch, int heads, int l_max, int head_dim, int pos,
+                                          const int* pos_dev, smt_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(dec_dh_ok(head_dim), "smt_lm_decode_attention: head dim must be 32 or 64 (got %d)", head_dim);
+  SMT_CHECK_ARG(qkv && k_cache && v_cache && ctx, "smt_lm_decode_attention: null pointer");
+  SMT_CHECK_ARG(batch >= 1 && batch <= 32 && heads >= 1 && l_max >= 1, "smt_lm_decode_attention: batch must be 1..32, heads and l_max positive");
+  SMT_CHECK_ARG((long long)batch * heads <= 65535 && (long long)l_max * head_dim < (1ll << 31),
+                "smt_lm_decode_attention: batch * heads <= 65535, l_max * head dim < 2^31");
+  SMT_CHECK_ARG(pos_dev || (pos >= 0 && pos < l_max), "smt_lm_decode_attention: pos %d outside the cache (%d rows)", pos, l_max);
+  const int nsplit = dec_splits(l_max);
+  SMT_CHECK_ARG(nsplit == 1 || (workspace && workspace_bytes >= smt_lm_decode_attention_hd_workspace_bytes(batch, heads, l_max, head_dim)),
+                "smt_lm_decode_attention: workspace too small");
+  return head_dim == 32 ? dec_attention_launch<32>(qkv, k_cache, v_cache, ctx, workspace, batch, heads, l_max, nsplit, pos, pos_dev, stream)
+                        : dec_attention_launch<64>(qkv, k_cache, v_cache, ctx, workspace, batch, heads, l_max, nsplit, pos, pos_dev, stream);
+}
+extern "C" int smt_lm_decode_attention(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace,
+                                       size_t workspace_bytes, int batch, int heads, int l_max, int pos, const int* pos_dev,
+                                       smt_stream_t stream) {
+  return smt_lm_decode_attention_hd(qkv, k_cache, v_cache, ctx, workspace, workspace_bytes, batch, heads, l_max, 32, pos, pos_dev, stream);
 }
 
 extern "C" int smt_lm_decode_sample(const float* logits, const float* uniforms, int64_t* tokens, int64_t* codes, int batch, int vocab,
@@ -535,16 +562,24 @@ extern "C" int smt_lm_decode_sample_filtered(const float* logits, const float* u
   return 0;
 }
 
-extern "C" int smt_lm_decode_prefill_kv(const float* qkv, float* k_cache, float* v_cache, int batch, int len, int heads, int l_max,
-                                        smt_stream_t stream_) {
+extern "C" int smt_lm_decode_prefill_kv_hd(const float* qkv, float* k_cache, float* v_cache, int batch, int len, int heads, int l_max,
+                                           int head_dim, smt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  SMT_CHECK_ARG(dec_dh_ok(head_dim), "smt_lm_decode_prefill_kv: head dim must be 32 or 64 (got %d)", head_dim);
   SMT_CHECK_ARG(qkv && k_cache && v_cache, "smt_lm_decode_prefill_kv: null pointer");
   SMT_CHECK_ARG(batch >= 1 && batch <= 32 && heads >= 1 && l_max >= 1, "smt_lm_decode_prefill_kv: batch must be 1..32, heads and l_max positive");
-  SMT_CHECK_ARG((long long)batch * heads <= 65535 && (long long)l_max * DEC_DH < (1ll << 31), "smt_lm_decode_prefill_kv: batch * heads <= 65535, l_max * 32 < 2^31");
+  SMT_CHECK_ARG((long long)batch * heads <= 65535 && (long long)l_max * head_dim < (1ll << 31),
+                "smt_lm_decode_prefill_kv: batch * heads <= 65535, l_max * head dim < 2^31");
   SMT_CHECK_ARG(len >= 1 && len <= l_max, "smt_lm_decode_prefill_kv: len %d outside 1..l_max = %d", len, l_max);
-  lm_decode_prefill_kv_kernel<<<dim3((len * 8 + 255) / 256, batch * heads), 256, 0, stream>>>(qkv, k_cache, v_cache, len, heads, l_max);
+  const dim3 grid((unsigned)(((long long)len * (head_dim / 4) + 255) / 256), batch * heads);
+  if (head_dim == 32) lm_decode_prefill_kv_kernel<32><<<grid, 256, 0, stream>>>(qkv, k_cache, v_cache, len, heads, l_max);
+  else lm_decode_prefill_kv_kernel<64><<<grid, 256, 0, stream>>>(qkv, k_cache, v_cache, len, heads, l_max);
   SMT_CHECK_LAUNCH("lm_decode_prefill_kv");
   return 0;
+}
+extern "C" int smt_lm_decode_prefill_kv(const float* qkv, float* k_cache, float* v_cache, int batch, int len, int heads, int l_max,
+                                        smt_stream_t stream) {
+  return smt_lm_decode_prefill_kv_hd(qkv, k_cache, v_cache, batch, len, heads, l_max, 32, stream);
 }
 
 extern "C" int smt_lm_decode_advance(int* pos_dev, smt_stream_t stream_) {

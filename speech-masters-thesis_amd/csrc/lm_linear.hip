@@ -342,6 +342,14 @@ extern "C" int smt_lm_linear_wgrad(const float* x, int64_t ld_x, const float* dy
   if (ll_check(fn, ts, 3, rows, n_in, n_out)) return 1;
   SMT_CHECK_ARG(dbias == nullptr || ((uintptr_t)dbias & 15) == 0, "%s: dbias must be 16-byte aligned", fn);
   const size_t dw_bytes = (size_t)n_out * n_in * 4, db_bytes = (size_t)n_out * 4;
+  const size_t x_bytes = rows ? ll_span(ts[0], rows) : 0, dy_bytes = rows ? ll_span(ts[1], rows) : 0;
+  // dweight on an input is named before dbias inside dweight: a dweight pointer that sits on x or dy spans n_out * n_in
+  // floats from there, which may also cover a correctly placed dbias -- which of the two is reported must not depend on
+  // where the caller's allocator put the buffers
+  if (rows) {
+    if (ll_check_alias(fn, "dweight", dweight, dw_bytes, "x", x, x_bytes)) return 1;
+    if (ll_check_alias(fn, "dweight", dweight, dw_bytes, "dy", dy, dy_bytes)) return 1;
+  }
   SMT_CHECK_ARG(dbias == nullptr || !ll_overlap(dbias, db_bytes, dweight, dw_bytes), "%s: dbias must not alias dweight", fn);
   hipStream_t stream = (hipStream_t)stream_;
   if (rows == 0) {                      // the sum over nothing
@@ -351,9 +359,6 @@ extern "C" int smt_lm_linear_wgrad(const float* x, int64_t ld_x, const float* dy
     }
     return 0;
   }
-  const size_t x_bytes = ll_span(ts[0], rows), dy_bytes = ll_span(ts[1], rows);
-  if (ll_check_alias(fn, "dweight", dweight, dw_bytes, "x", x, x_bytes)) return 1;
-  if (ll_check_alias(fn, "dweight", dweight, dw_bytes, "dy", dy, dy_bytes)) return 1;
   if (dbias && ll_check_alias(fn, "dbias", dbias, db_bytes, "x", x, x_bytes)) return 1;
   if (dbias && ll_check_alias(fn, "dbias", dbias, db_bytes, "dy", dy, dy_bytes)) return 1;
   const int splits = ll_wgrad_splits(rows, n_in, n_out);

@@ -81,56 +81,66 @@ def embed(tokens, weight, pe, drop=NO_DROP, padding_idx=0):
     return _Embed.apply(tokens, weight, pe, math.sqrt(weight.shape[1]), drop, padding_idx)
 
 
-def _attn_flops(b, heads, l, causal, matmuls):
-    """Algorithmic FLOPs of `matmuls` 32-channel products over the visible (query, key) pairs (full lengths): forward 2
-    (scores, context), backward 5 (scores, dP, dq, dk, dv; the two backward kernels each recompute scores and dP, which
-    is not counted)."""
+def _attn_flops(b, heads, l, causal, matmuls, head_dim=32):
+    """Algorithmic FLOPs of `matmuls` head_dim-channel products over the visible (query, key) pairs (full lengths):
+    forward 2 (scores, context), backward 5 (scores, dP, dq, dk, dv; the two backward kernels each recompute scores and
+    dP, which is not counted)."""
     pairs = l * (l + 1) // 2 if causal else l * l
-    return b * heads * pairs * 64 * matmuls
+    return b * heads * pairs * 2 * head_dim * matmuls
 
 
-# compute_dtype of `attention` -> (forward entry, backward entry, profiler region, profiler dtype)
-_ATTN_ENTRIES = {torch.float32: ("smt_lm_attention_fwd", "smt_lm_attention_bwd", "lm_attention", "f32"),
-                 torch.bfloat16: ("smt_lm_attention_bf16_fwd", "smt_lm_attention_bf16_bwd", "lm_attention_bf16", "bf16")}
+HEAD_DIMS = (32, 64)          # what the attention kernels (csrc/lm.hip, csrc/lm_decode.hip) are built for
+
+
+def _head_dim(dim, heads):
+    dh = dim // heads if heads > 0 else 0
+    assert dh in HEAD_DIMS and dim == heads * dh, \
+        f"the attention kernels are built for head dim 32 or 64 (got {dim / heads if heads > 0 else dim:g})"
+    return dh
+
+
+# compute_dtype of `attention` -> (bf16 flag of smt_lm_attention_hd_fwd / _bwd, profiler region, profiler dtype)
+_ATTN_ENTRIES = {torch.float32: (0, "lm_attention", "f32"), torch.bfloat16: (1, "lm_attention_bf16", "bf16")}
 
 
 class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, lens, heads, causal, drop, compute_dtype=torch.float32):
-        fwd, _, region, dtype = _ATTN_ENTRIES[compute_dtype]
+        bf16, region, dtype = _ATTN_ENTRIES[compute_dtype]
         b, l, d3 = qkv.shape
         d = d3 // 3
-        assert d == heads * 32, "the attention kernel is built for head dim 32"
+        dh = _head_dim(d, heads)
         qkv = _f32(qkv)
         out = torch.empty(b, l, d, device=qkv.device, dtype=torch.float32)
         lse = torch.empty(b, heads, l, device=qkv.device, dtype=torch.float32)
-        with profiler.region(region + ":fwd", flops=_attn_flops(b, heads, l, causal, 2), bound="mfma", dtype=dtype):
-            N.check(getattr(N.lib(), fwd)(N.ptr(qkv), N.ptr(lens), N.ptr(out), N.ptr(lse), b, l, heads, int(causal),
-                                          drop.key, N.ptr(drop.key_dev), drop.thresh, drop.scale, N.stream_ptr()), fwd)
+        with profiler.region(region + ":fwd", flops=_attn_flops(b, heads, l, causal, 2, dh), bound="mfma", dtype=dtype):
+            N.check(N.lib().smt_lm_attention_hd_fwd(N.ptr(qkv), N.ptr(lens), N.ptr(out), N.ptr(lse), b, l, heads, int(causal),
+                                                    drop.key, N.ptr(drop.key_dev), drop.thresh, drop.scale, dh, bf16, N.stream_ptr()),
+                    "smt_lm_attention_hd_fwd")
         ctx.save_for_backward(qkv, lens, out, lse)
-        ctx.meta = (heads, int(causal), drop, compute_dtype)
+        ctx.meta = (heads, int(causal), drop, compute_dtype, dh)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, lens, out, lse = ctx.saved_tensors
-        heads, causal, drop, compute_dtype = ctx.meta
-        _, bwd, region, dtype = _ATTN_ENTRIES[compute_dtype]
+        heads, causal, drop, compute_dtype, dh = ctx.meta
+        bf16, region, dtype = _ATTN_ENTRIES[compute_dtype]
         b, l, _ = qkv.shape
         dqkv = torch.empty_like(qkv)
         delta = torch.empty_like(lse)
         dout = _f32(dout)
-        with profiler.region(region + ":bwd", flops=_attn_flops(b, heads, l, causal, 5), bound="mfma", dtype=dtype):
-            N.check(getattr(N.lib(), bwd)(N.ptr(qkv), N.ptr(lens), N.ptr(out), N.ptr(lse), N.ptr(dout), N.ptr(dqkv),
-                                          N.ptr(delta), b, l, heads, causal, drop.key, N.ptr(drop.key_dev), drop.thresh, drop.scale,
-                                          N.stream_ptr()), bwd)
+        with profiler.region(region + ":bwd", flops=_attn_flops(b, heads, l, causal, 5, dh), bound="mfma", dtype=dtype):
+            N.check(N.lib().smt_lm_attention_hd_bwd(N.ptr(qkv), N.ptr(lens), N.ptr(out), N.ptr(lse), N.ptr(dout), N.ptr(dqkv),
+                                                    N.ptr(delta), b, l, heads, causal, drop.key, N.ptr(drop.key_dev), drop.thresh,
+                                                    drop.scale, dh, bf16, N.stream_ptr()), "smt_lm_attention_hd_bwd")
         return dqkv, None, None, None, None, None
 
 
 def attention(qkv, lens, heads, causal=True, drop=NO_DROP, *, compute_dtype=torch.float32):
-    """Self-attention core: qkv [batch, len, 3 dim] -> [batch, len, dim]; lens [batch] int32 (keys >= lens[b] masked) or
-    None; causal adds the triu(-inf, 1) mask of the reference's forward (:111).  compute_dtype is the operand type of the
-    products: torch.float32, or torch.bfloat16 for the kernels on bf16 MFMAs (smt_lm_attention_bf16_*: tensors stay fp32,
+    """Self-attention core: qkv [batch, len, 3 dim] -> [batch, len, dim], head dim dim / heads = 32 or 64 (anything else
+    is an AssertionError); lens [batch] int32 (keys >= lens[b] masked) or None; causal adds the triu(-inf, 1) mask of the reference's forward (:111).  compute_dtype is the operand type of the
+    products: torch.float32, or torch.bfloat16 for the kernels on bf16 MFMAs (smt_lm_attention_hd_*, bf16 = 1: tensors stay fp32,
     the rounding points are listed in include/smt_hip.h)."""
     if compute_dtype not in _ATTN_ENTRIES:
         raise ValueError(f"attention: compute_dtype must be torch.float32 or torch.bfloat16 (got {compute_dtype!r})")
@@ -561,22 +571,24 @@ def decode_linear(x, weight, bias=None, out=None, relu=False, act=None):
     return out
 
 
-def decode_attention_workspace(batch, heads, l_max, device):
+def decode_attention_workspace(batch, heads, l_max, device, head_dim=32):
     """The partial-softmax buffer of `decode_attention` for caches of l_max rows (None when none is needed)."""
-    nbytes = N.lib().smt_lm_decode_attention_workspace_bytes(batch, heads, l_max)
+    assert head_dim in HEAD_DIMS, f"the attention kernels are built for head dim 32 or 64 (got {head_dim})"
+    nbytes = N.lib().smt_lm_decode_attention_hd_workspace_bytes(batch, heads, l_max, head_dim)
     return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
 
 
 def decode_attention(qkv, k_cache, v_cache, ctx, workspace=None, pos=0, pos_dev=None):
-    """qkv [batch, 3 * heads * 32] of the token at `pos`; k_cache / v_cache [batch, heads, l_max, 32] get its k / v rows at row
-    pos; ctx [batch, heads * 32] = softmax(q K[0..pos]^T / sqrt(32)) V[0..pos]."""
+    """qkv [batch, 3 * heads * dh] of the token at `pos`; k_cache / v_cache [batch, heads, l_max, dh] get its k / v rows at row
+    pos; ctx [batch, heads * dh] = softmax(q K[0..pos]^T / sqrt(dh)) V[0..pos].  dh, read from the caches, is 32 or 64."""
     b, h, l_max, dh = k_cache.shape
-    assert dh == 32 and v_cache.shape == k_cache.shape and qkv.shape == (b, 3 * h * 32) and ctx.shape == (b, h * 32)
+    assert dh in HEAD_DIMS, f"the attention kernels are built for head dim 32 or 64 (got {dh})"
+    assert v_cache.shape == k_cache.shape and qkv.shape == (b, 3 * h * dh) and ctx.shape == (b, h * dh)
     assert k_cache.dtype == v_cache.dtype == ctx.dtype == torch.float32
     p, pd = _pos_args(pos, pos_dev)
-    N.check(N.lib().smt_lm_decode_attention(N.ptr(_f32(qkv)), N.ptr(k_cache), N.ptr(v_cache), N.ptr(ctx), N.ptr(workspace),
-                                            0 if workspace is None else workspace.numel(), b, h, l_max, p, pd, N.stream_ptr()),
-            "smt_lm_decode_attention")
+    N.check(N.lib().smt_lm_decode_attention_hd(N.ptr(_f32(qkv)), N.ptr(k_cache), N.ptr(v_cache), N.ptr(ctx), N.ptr(workspace),
+                                               0 if workspace is None else workspace.numel(), b, h, l_max, dh, p, pd, N.stream_ptr()),
+            "smt_lm_decode_attention_hd")
     return ctx
 
 
@@ -610,13 +622,14 @@ def decode_sample_filtered(logits, uniforms, tokens, codes, sigma=1.0, top_k=Non
 
 
 def decode_prefill_kv(qkv, k_cache, v_cache):
-    """The k and v thirds of qkv [batch, len, 3 * heads * 32] (the batched in-projection of a prompt) into rows 0..len-1 of
-    k_cache / v_cache [batch, heads, l_max, 32]; rows from len on are left alone."""
+    """The k and v thirds of qkv [batch, len, 3 * heads * dh] (the batched in-projection of a prompt) into rows 0..len-1 of
+    k_cache / v_cache [batch, heads, l_max, dh]; rows from len on are left alone.  dh, read from the caches, is 32 or 64."""
     b, h, l_max, dh = k_cache.shape
-    assert dh == 32 and v_cache.shape == k_cache.shape and qkv.dim() == 3 and qkv.shape[0] == b and qkv.shape[2] == 3 * h * 32
+    assert dh in HEAD_DIMS, f"the attention kernels are built for head dim 32 or 64 (got {dh})"
+    assert v_cache.shape == k_cache.shape and qkv.dim() == 3 and qkv.shape[0] == b and qkv.shape[2] == 3 * h * dh
     assert k_cache.dtype == v_cache.dtype == torch.float32 and k_cache.is_contiguous() and v_cache.is_contiguous()
-    N.check(N.lib().smt_lm_decode_prefill_kv(N.ptr(_f32(qkv)), N.ptr(k_cache), N.ptr(v_cache), b, qkv.shape[1], h, l_max, N.stream_ptr()),
-            "smt_lm_decode_prefill_kv")
+    N.check(N.lib().smt_lm_decode_prefill_kv_hd(N.ptr(_f32(qkv)), N.ptr(k_cache), N.ptr(v_cache), b, qkv.shape[1], h, l_max, dh,
+                                                N.stream_ptr()), "smt_lm_decode_prefill_kv_hd")
 
 
 def decode_advance(pos_dev):
@@ -644,16 +657,16 @@ def decode_residual_layer_norm(x, h, h_bias, gamma, beta, eps, s_out, out, stats
 
 class DecodeState:
     """Every buffer of an incremental decoding loop (TransformerLM.sample(causal=True) / step_logits): the key/value cache
-    [layers, 2, batch, heads, l_max, 32], the token [batch, n_steps + 1] and code [batch, n_steps] buffers, the position
+    [layers, 2, batch, heads, l_max, dh] (dh = dim / heads, 32 or 64), the token [batch, n_steps + 1] and code [batch, n_steps] buffers, the position
     (``pos_dev`` on the device, mirrored by ``pos`` on the host), the uniforms [n_steps, batch], the kept-set sizes of the
     filtered sampler [n_steps, batch] int32 and the activations of one step.
     Nothing here comes from the grow-only workspace of smt_amd.native: captured launches keep pointing at these tensors."""
 
     def __init__(self, batch, n_steps, dim, heads, dim_ff, vocab, layers, device, first_token=1, uniforms=None):
-        assert dim == heads * 32, "the attention kernels are built for head dim 32"
+        dh = _head_dim(dim, heads)
         f32 = dict(device=device, dtype=torch.float32)
         self.batch, self.n_steps = batch, n_steps
-        self.kv = torch.empty(layers, 2, batch, heads, n_steps, 32, **f32)           # rows beyond pos are never read
+        self.kv = torch.empty(layers, 2, batch, heads, n_steps, dh, **f32)           # rows beyond pos are never read
         self.tokens = torch.zeros(batch, n_steps + 1, device=device, dtype=torch.int64)
         self.tokens[:, 0] = first_token
         self.codes = torch.zeros(batch, n_steps, device=device, dtype=torch.int64)
@@ -668,7 +681,7 @@ class DecodeState:
         self.f = torch.empty(batch, dim_ff, **f32)
         self.stats = torch.empty(batch, 2, **f32)
         self.logits = torch.empty(batch, vocab, **f32)
-        self.attn_ws = decode_attention_workspace(batch, heads, n_steps, device)
+        self.attn_ws = decode_attention_workspace(batch, heads, n_steps, device, dh)
 
     def advance(self):
         """pos += 1, on the device and in the host mirror."""

@@ -120,6 +120,9 @@ _SIGNATURES = {
     "smt_lm_attention_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_u32, c_ptr, c_u32, c_f32, c_ptr]),
     "smt_lm_attention_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_u32, c_ptr, c_u32, c_f32,
                                      c_ptr]),
+    "smt_lm_attention_hd_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_u32, c_ptr, c_u32, c_f32, c_int, c_int, c_ptr]),
+    "smt_lm_attention_hd_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_u32, c_ptr, c_u32, c_f32,
+                                        c_int, c_int, c_ptr]),
     "smt_lm_attention_bf16_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_u32, c_ptr, c_u32, c_f32, c_ptr]),
     "smt_lm_attention_bf16_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_u32, c_ptr, c_u32,
                                           c_f32, c_ptr]),
@@ -154,10 +157,13 @@ _SIGNATURES = {
     "smt_lm_decode_embed": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_f32, c_int, c_ptr, c_ptr]),
     "smt_lm_decode_linear": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "smt_lm_decode_attention_workspace_bytes": (c_size, [c_int, c_int, c_int]),
+    "smt_lm_decode_attention_hd_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int]),
+    "smt_lm_decode_attention_hd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "smt_lm_decode_attention": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "smt_lm_decode_sample": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_f32, c_int, c_int, c_ptr, c_ptr]),
     "smt_lm_decode_sample_filtered": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_f32, c_int, c_int, c_f32, c_ptr,
                                               c_int, c_ptr, c_ptr]),
+    "smt_lm_decode_prefill_kv_hd": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr]),
     "smt_lm_decode_prefill_kv": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "smt_lm_decode_advance": (c_int, [c_ptr, c_ptr]),
     "smt_glow_reduce_workspace_bytes": (c_size, [c_i64, c_int]),
