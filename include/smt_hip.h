@@ -796,6 +796,34 @@ size_t smt_lm_decode_attention_hd_workspace_bytes(int batch, int heads, int l_ma
 int smt_lm_decode_attention_hd(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace, size_t workspace_bytes,
                                int batch, int heads, int l_max, int head_dim, int pos, const int* pos_dev, smt_stream_t stream);
 
+/* Rotary positions (model.position: rotary; csrc/lm_rope.hip).  Head dim dh = 32 or 64.  Pair i in [0, dh/2) is
+ * channels (2i, 2i+1) of a head -- interleaved, so that a pair never crosses the 4 consecutive channels a lane of the decode
+ * attention owns -- in the q and k thirds of qkv [batch, len, 3*heads*dh]; v is untouched.  With theta_i = base^(-2i/dh),
+ * absolute position p and a = p * theta_i:
+ *     y[2i]   = x[2i] * cos a - x[2i+1] * sin a
+ *     y[2i+1] = x[2i] * sin a + x[2i+1] * cos a            (inverse: sin negated)
+ * cos a and sin a are read from the table rope [rope_rows, dh/2, 2] fp32 = (cos a, sin a), which the host computes in float64
+ * (theta_i = pow(base, -2i/dh), a = p * theta_i, both float64) and rounds once (smt_amd.lm.rope_table); the kernels call no
+ * transcendental, and equal inputs give equal bits.  Rounding: y = fma(x0, c, -(x1 * s)) resp. fma(x0, s, x1 * c), so
+ * |y - y64| <= 4 * 2^-24 * (|x[2i]| + |x[2i+1]|) against float64 with float64 angles.  The gradient of the rotation is the
+ * inverse rotation of the incoming gradient: inverse != 0 is the backward.
+ *
+ * In place on the q and k thirds of every row; row l uses table row pos0 + l; the v third is neither read nor written.  One
+ * launch, 16-byte accesses (qkv and rope 16-byte aligned), no atomics, no workspace; batch * len = 0 returns 0 without a
+ * launch.  Argument errors: null pointers, a head dim other than 32 or 64, pos0 < 0 or pos0 + len > rope_rows ("outside the
+ * rope table"), len * 3 * heads * head_dim >= 2^31. */
+int smt_lm_rope(float* qkv, const float* rope, int batch, int len, int heads, int head_dim, int rope_rows, int pos0, int inverse,
+                smt_stream_t stream);
+
+/* smt_lm_decode_attention_hd with rotary positions, in the same launches: the step's q and its own k row are rotated at
+ * position pos (table row pos of rope [rope_rows, head_dim/2, 2]) as they are loaded from qkv, before the scale and before the
+ * store to cache row pos.  The cache therefore holds rotated keys, cached rows are used as read, qkv is not modified; v is
+ * untouched.  Workspace: that of the _hd entry.  rope == NULL is exactly the _hd launch (rope_rows is then ignored).  A
+ * by-value pos >= rope_rows is an argument error; a *pos_dev outside the table or the cache makes the launch write nothing. */
+int smt_lm_decode_attention_rope(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace, size_t workspace_bytes,
+                                 int batch, int heads, int l_max, int head_dim, const float* rope, int rope_rows, int pos,
+                                 const int* pos_dev, smt_stream_t stream);
+
 /* Inverse-CDF draw: p_i = exp((logits[b, i] - max_i) * inv_sigma), S = sum p_i, k = the smallest index whose cumulative sum
  * exceeds uniforms[pos, b] * S (if rounding leaves none: the last k with p_k > 0).  logits [batch, vocab], uniforms
  * [n_steps, batch] in [0, 1); writes tokens[b, pos + 1] = k + token_offset (tokens [batch, tok_len] int64) and

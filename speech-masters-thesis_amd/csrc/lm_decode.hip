@@ -16,7 +16,7 @@
 // Sums are merged in fixed orders: no float atomics, the same inputs give the same bits.
 #include <algorithm>
 
-#include "smt_common.h"
+#include "lm_rope.h"
 
 namespace smt {
 
@@ -127,6 +127,9 @@ __global__ __launch_bounds__(MAXT) void lm_decode_linear_kernel(const float* __r
 // the 16-byte contiguous-per-lane load and the 1 KiB per instruction, for one more score shuffle and one fewer group merge.)
 // The step's own k / v rows come from qkv (one wave stores them to the cache; no value read from cache row pos is used in
 // this launch), rows beyond pos are never read.
+// ROPE (model.position: rotary): the step's q and k are rotated at position pos as they are loaded -- a lane's four channels
+// are two whole pairs, its (cos, sin, cos, sin) are 16 bytes of table row pos -- before the scale and before the store, so the
+// cache holds rotated keys and cached rows are used as read.  A position outside the table: nothing is written, as for l_max.
 struct DecAcc { float m, z; f32x4 o; };
 __device__ __forceinline__ void dec_merge(DecAcc& a, float m2, float z2, const f32x4& o2) {
   const float mn = fmaxf(a.m, m2), ms = (mn == -INFINITY) ? 0.f : mn;
@@ -136,21 +139,29 @@ __device__ __forceinline__ void dec_merge(DecAcc& a, float m2, float z2, const f
   a.m = mn;
 }
 
-template <int DH>
+template <int DH, bool ROPE>
 __global__ __launch_bounds__(256) void lm_decode_attn_kernel(const float* __restrict__ qkv, float* kcache, float* vcache,
                                                              float* __restrict__ ctx, float* __restrict__ part, int H, int l_max,
-                                                             int nsplit, int pos, const int* __restrict__ pos_dev) {
+                                                             int nsplit, const float* __restrict__ rope, int rope_rows, int pos,
+                                                             const int* __restrict__ pos_dev) {
   constexpr int LPR = DH / 4, G = 64 / LPR, U = 32 / G;        // lanes per row, rows per load instruction, loads per trip
   if (pos_dev) pos = *pos_dev;
   if (pos < 0 || pos >= l_max) return;
+  if (ROPE && pos >= rope_rows) return;
   const int s = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H, d = H * DH;
   const int c0 = s * DEC_CHUNK;
   if (c0 > pos) return;                                       // uniform: no visible row in this chunk (the merge skips it too)
   __shared__ float red[4][LPR][6];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane / LPR, c = lane % LPR;
   const float* qrow = qkv + (size_t)b * 3 * d + h * DH + 4 * c;
-  const f32x4 q = *(const f32x4*)qrow * (rsqrtf((float)DH) * DEC_LOG2E);   // base-2 scores: exp2 is one instruction
-  const f32x4 kn = *(const f32x4*)(qrow + d), vn = *(const f32x4*)(qrow + 2 * d);
+  f32x4 qn = *(const f32x4*)qrow, kn = *(const f32x4*)(qrow + d);
+  const f32x4 vn = *(const f32x4*)(qrow + 2 * d);
+  if (ROPE) {
+    const f32x4 cs = *(const f32x4*)(rope + (size_t)pos * DH + 4 * c);
+    qn = rope_rotate4(qn, cs, false);
+    kn = rope_rotate4(kn, cs, false);
+  }
+  const f32x4 q = qn * (rsqrtf((float)DH) * DEC_LOG2E);        // base-2 scores: exp2 is one instruction
   float* kb = kcache + (size_t)bh * l_max * DH + 4 * c;
   float* vb = vcache + (size_t)bh * l_max * DH + 4 * c;
   if (pos - c0 < DEC_CHUNK && w == 0 && g == 0) {             // the chunk that holds row pos
@@ -494,21 +505,28 @@ extern "C" size_t smt_lm_decode_attention_workspace_bytes(int batch, int heads, 
   return smt_lm_decode_attention_hd_workspace_bytes(batch, heads, l_max, 32);
 }
 
+// rope == NULL: the kernel without the rotation (the launch of smt_lm_decode_attention_hd).  The merge kernel uses its row
+// limit for nothing but the "write nothing" rule, so with a table it gets min(l_max, rope_rows).
 template <int DH>
 static int dec_attention_launch(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace, int batch, int heads,
-                                int l_max, int nsplit, int pos, const int* pos_dev, hipStream_t stream) {
-  lm_decode_attn_kernel<DH><<<dim3(nsplit, batch * heads), 256, 0, stream>>>(qkv, k_cache, v_cache, ctx, (float*)workspace, heads, l_max, nsplit, pos, pos_dev);
+                                int l_max, int nsplit, const float* rope, int rope_rows, int pos, const int* pos_dev, hipStream_t stream) {
+  const dim3 grid(nsplit, batch * heads);
+  if (rope)
+    lm_decode_attn_kernel<DH, true><<<grid, 256, 0, stream>>>(qkv, k_cache, v_cache, ctx, (float*)workspace, heads, l_max, nsplit, rope, rope_rows, pos, pos_dev);
+  else
+    lm_decode_attn_kernel<DH, false><<<grid, 256, 0, stream>>>(qkv, k_cache, v_cache, ctx, (float*)workspace, heads, l_max, nsplit, nullptr, 0, pos, pos_dev);
   SMT_CHECK_LAUNCH("lm_decode_attention");
   if (nsplit > 1) {
-    lm_decode_attn_merge_kernel<DH><<<(batch * heads * DH + 255) / 256, 256, 0, stream>>>((const float*)workspace, ctx, batch * heads, l_max, nsplit, pos, pos_dev);
+    const int limit = rope ? std::min(l_max, rope_rows) : l_max;
+    lm_decode_attn_merge_kernel<DH><<<(batch * heads * DH + 255) / 256, 256, 0, stream>>>((const float*)workspace, ctx, batch * heads, limit, nsplit, pos, pos_dev);
     SMT_CHECK_LAUNCH("lm_decode_attention_merge");
   }
   return 0;
 }
 
-extern "C" int smt_lm_decode_attention_hd(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace,
-                                          size_t workspace_bytes, int batch, int heads, int l_max, int head_dim, int pos,
-                                          const int* pos_dev, smt_stream_t stream_) {
+extern "C" int smt_lm_decode_attention_rope(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace,
+                                            size_t workspace_bytes, int batch, int heads, int l_max, int head_dim, const float* rope,
+                                            int rope_rows, int pos, const int* pos_dev, smt_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SMT_CHECK_ARG(dec_dh_ok(head_dim), "smt_lm_decode_attention: head dim must be 32 or 64 (got %d)", head_dim);
   SMT_CHECK_ARG(qkv && k_cache && v_cache && ctx, "smt_lm_decode_attention: null pointer");
@@ -516,11 +534,19 @@ extern "C" int smt_lm_decode_attention_hd(const float* qkv, float* k_cache, floa
   SMT_CHECK_ARG((long long)batch * heads <= 65535 && (long long)l_max * head_dim < (1ll << 31),
                 "smt_lm_decode_attention: batch * heads <= 65535, l_max * head dim < 2^31");
   SMT_CHECK_ARG(pos_dev || (pos >= 0 && pos < l_max), "smt_lm_decode_attention: pos %d outside the cache (%d rows)", pos, l_max);
+  SMT_CHECK_ARG(!rope || (rope_rows >= 1 && (uintptr_t)rope % 16 == 0), "smt_lm_decode_attention: the rope table needs rope_rows >= 1 and a 16-byte aligned address");
+  SMT_CHECK_ARG(!rope || pos_dev || pos < rope_rows, "smt_lm_decode_attention: pos %d outside the rope table (%d rows)", pos, rope_rows);
   const int nsplit = dec_splits(l_max);
   SMT_CHECK_ARG(nsplit == 1 || (workspace && workspace_bytes >= smt_lm_decode_attention_hd_workspace_bytes(batch, heads, l_max, head_dim)),
                 "smt_lm_decode_attention: workspace too small");
-  return head_dim == 32 ? dec_attention_launch<32>(qkv, k_cache, v_cache, ctx, workspace, batch, heads, l_max, nsplit, pos, pos_dev, stream)
-                        : dec_attention_launch<64>(qkv, k_cache, v_cache, ctx, workspace, batch, heads, l_max, nsplit, pos, pos_dev, stream);
+  return head_dim == 32 ? dec_attention_launch<32>(qkv, k_cache, v_cache, ctx, workspace, batch, heads, l_max, nsplit, rope, rope_rows, pos, pos_dev, stream)
+                        : dec_attention_launch<64>(qkv, k_cache, v_cache, ctx, workspace, batch, heads, l_max, nsplit, rope, rope_rows, pos, pos_dev, stream);
+}
+extern "C" int smt_lm_decode_attention_hd(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace,
+                                          size_t workspace_bytes, int batch, int heads, int l_max, int head_dim, int pos,
+                                          const int* pos_dev, smt_stream_t stream) {
+  return smt_lm_decode_attention_rope(qkv, k_cache, v_cache, ctx, workspace, workspace_bytes, batch, heads, l_max, head_dim, nullptr, 0, pos,
+                                      pos_dev, stream);
 }
 extern "C" int smt_lm_decode_attention(const float* qkv, float* k_cache, float* v_cache, float* ctx, void* workspace,
                                        size_t workspace_bytes, int batch, int heads, int l_max, int pos, const int* pos_dev,

@@ -25,6 +25,7 @@ from smt_amd import packing
 
 COMPUTE_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
 ACTIVATIONS = {"relu": K.ACT_RELU, "gelu": K.ACT_GELU}
+POSITIONS = ("sinusoidal", "rotary")
 
 
 class PositionalEncoding(nn.Module):
@@ -82,9 +83,15 @@ class _EncoderLayer(nn.Module):
             return K.bias_gelu_dropout(h, self.linear1.bias, drop)
         return K.bias_relu_dropout_(h, self.linear1.bias, drop)
 
-    def forward(self, x, lens, causal, seed, site0, kd=None):
+    def _in_proj(self, x, rope):
+        """The in-projection; with a rotary table its q and k thirds are rotated in place, row l at position l."""
+        sa = self.self_attn
+        qkv = K.linear(x, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=self.compute_dtype)
+        return qkv if rope is None else K.rope(qkv, rope, sa.num_heads)
+
+    def forward(self, x, lens, causal, seed, site0, kd=None, rope=None):
         sa, tr, p, cd = self.self_attn, self.training, self.p, self.compute_dtype
-        qkv = K.linear(x, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=cd)
+        qkv = self._in_proj(x, rope)
         ctx = K.attention(qkv, lens, sa.num_heads, causal, K.Drop(p, tr, seed, site0, kd), compute_dtype=self.attention_dtype)
         a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)    # its bias is added (and differentiated) inside add_layer_norm
         x = K.add_layer_norm(x, a, self.norm1.weight, self.norm1.bias, self.norm1.eps, K.Drop(p, tr, seed, site0 + 1, kd),
@@ -94,12 +101,12 @@ class _EncoderLayer(nn.Module):
         return K.add_layer_norm(x, f, self.norm2.weight, self.norm2.bias, self.norm2.eps, K.Drop(p, tr, seed, site0 + 3, kd),
                                 h_bias=self.linear2.bias)
 
-    def forward_pre(self, s, y, nxt, lens, causal, seed, site0, kd=None):
+    def forward_pre(self, s, y, nxt, lens, causal, seed, site0, kd=None, rope=None):
         """Pre-norm layer: s [B, L, d] is the residual stream, y = norm1(s) already formed by whoever produced s, `nxt` the
         LayerNorm that follows this layer (the next layer's norm1 or the encoder's final norm).  Returns (s', nxt(s')): each
         residual add runs fused with the norm after it, so a layer is the same four launches as the post-norm one."""
         sa, tr, p, cd = self.self_attn, self.training, self.p, self.compute_dtype
-        qkv = K.linear(y, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=cd)
+        qkv = self._in_proj(y, rope)
         ctx = K.attention(qkv, lens, sa.num_heads, causal, K.Drop(p, tr, seed, site0, kd), compute_dtype=self.attention_dtype)
         a = K.linear(ctx, sa.out_proj.weight, compute_dtype=cd)    # its bias is added (and differentiated) inside residual_layer_norm
         s, y = K.residual_layer_norm(s, a, self.norm2.weight, self.norm2.bias, self.norm2.eps, K.Drop(p, tr, seed, site0 + 1, kd),
@@ -108,12 +115,12 @@ class _EncoderLayer(nn.Module):
         f = K.linear(f, self.linear2.weight, compute_dtype=cd)
         return K.residual_layer_norm(s, f, nxt.weight, nxt.bias, nxt.eps, K.Drop(p, tr, seed, site0 + 3, kd), h_bias=self.linear2.bias)
 
-    def prefill(self, x, k_cache, v_cache, last):
+    def prefill(self, x, k_cache, v_cache, last, rope=None):
         """Eval-mode `forward` over a prompt x [B, P, d] (causal, no lengths, no dropout) that also writes the P key / value
         rows into the decoding cache; the last layer stops there (nothing reads its output: the next decoding step attends
         to the cache only) and returns None."""
         sa, cd = self.self_attn, self.compute_dtype
-        qkv = K.linear(x, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=cd)
+        qkv = self._in_proj(x, rope)                               # rotated before the copy: the cache holds rotated keys
         K.decode_prefill_kv(qkv, k_cache, v_cache)
         if last:
             return None
@@ -124,10 +131,10 @@ class _EncoderLayer(nn.Module):
         f = K.linear(f, self.linear2.weight, compute_dtype=cd)
         return K.add_layer_norm(x, f, self.norm2.weight, self.norm2.bias, self.norm2.eps, h_bias=self.linear2.bias)
 
-    def prefill_pre(self, s, y, nxt, k_cache, v_cache, last):
+    def prefill_pre(self, s, y, nxt, k_cache, v_cache, last, rope=None):
         """`prefill` of a pre-norm layer, on the (s, y) pair of `forward_pre`; returns the next pair, or None from the last layer."""
         sa, cd = self.self_attn, self.compute_dtype
-        qkv = K.linear(y, sa.in_proj_weight, sa.in_proj_bias, compute_dtype=cd)
+        qkv = self._in_proj(y, rope)
         K.decode_prefill_kv(qkv, k_cache, v_cache)
         if last:
             return None
@@ -181,6 +188,14 @@ class TransformerLM(TokenToWaveformModel):
         if name not in COMPUTE_DTYPES:
             raise ValueError(f"model.attention_dtype must be fp32 or bf16 (got {name!r})")
         self.attention_dtype = COMPUTE_DTYPES[name]
+        # where positions enter: sinusoidal = the reference's table added to the embedding; rotary = q and k rotated inside every
+        # layer (smt_amd.lm.rope, csrc/lm_rope.hip), nothing added to the embedding
+        self.position = m.get("position", "sinusoidal")
+        if self.position not in POSITIONS:
+            raise ValueError(f"model.position must be sinusoidal or rotary (got {self.position!r})")
+        self.rope_base = m.get("rope_base", 10000.0)
+        if isinstance(self.rope_base, bool) or not isinstance(self.rope_base, (int, float)) or not (math.isfinite(self.rope_base) and self.rope_base > 1):
+            raise ValueError(f"model.rope_base must be a finite number > 1 (got {self.rope_base!r})")
         self.d_model = m.d_model
         self.embedding = nn.Embedding(m.vocab_size + TransformerLM.OFFSET, m.embed_dim, padding_idx=TransformerLM.PAD)
         self.pos_encoding = PositionalEncoding(m.d_model, m.dropout, m.max_len)
@@ -189,6 +204,11 @@ class TransformerLM(TokenToWaveformModel):
                               attention_dtype=self.attention_dtype)
         self.transformer = _Encoder(layer, m.num_layers, nn.LayerNorm(m.d_model, eps=float(m.layer_norm_eps)))
         self.classifier = nn.Linear(m.d_model, m.vocab_size)
+        # rotary: the (cos, sin) table of every position is derived from the config, so it stays out of the state dict -- whose
+        # keys and shapes (pos_encoding.pe included) are the same for both settings
+        self.register_buffer("rope", K.rope_table(m.max_len, m.d_model // m.nhead, self.rope_base) if self.position == "rotary" else None,
+                             persistent=False)
+        self._zero_pe = None                            # rotary: the table the embedding kernel adds (all zeros), grown on demand
         self.vqvae = TransformerLM.load_vqvae(m.vqvae.log_dir, m.vqvae.ckpt_num)
         self.loss_type = m.loss_type
         # all three losses run in the native loss kernels (smt_amd.lm.cross_entropy / mmi_loss / focal_loss); `self.loss`
@@ -218,6 +238,16 @@ class TransformerLM(TokenToWaveformModel):
         self._seed_dev = torch.tensor([self._drop_seed & 0x7FFFFFFF], dtype=torch.int32, device=dev)
         self._keys_dev = torch.zeros(1 + 4 * len(self.transformer.layers), dtype=torch.int32, device=dev)
         K.make_keys(self._seed_dev, self._keys_dev)
+
+    def _embed_table(self, rows):
+        """The table the embedding kernels add, with at least `rows` rows: the sinusoidal one, or zeros with rotary positions
+        (x + 0 is exact; the kernels keep refusing a null table).  The zeros are kept and grown to the longest sequence seen."""
+        if self.position != "rotary":
+            return self.pos_encoding.table()
+        dev = self.embedding.weight.device
+        if self._zero_pe is None or self._zero_pe.shape[0] < rows or self._zero_pe.device != dev:
+            self._zero_pe = torch.zeros(rows, self.d_model, device=dev, dtype=torch.float32)
+        return self._zero_pe
 
     @staticmethod
     def load_vqvae(log_dir, ckpt_num):
@@ -249,8 +279,9 @@ class TransformerLM(TokenToWaveformModel):
     def logits(self, x, lens, causal=True):
         """tokens [B, L] int64 (+ int32 lengths or None) -> next-token logits [B, L, vocab]."""
         seed, tr, kd = self._drop_seed, self.training, self._keys_dev
-        h = K.embed(x, self.embedding.weight, self.pos_encoding.table(), K.Drop(self.pos_encoding.p, tr, seed, 0, kd),
+        h = K.embed(x, self.embedding.weight, self._embed_table(x.shape[1]), K.Drop(self.pos_encoding.p, tr, seed, 0, kd),
                     TransformerLM.PAD)
+        rope = self.rope
         layers, norm = self.transformer.layers, self.transformer.norm
         if self.norm_first:
             # layer 0's norm1 is the only LayerNorm on its own; every other one runs inside the residual add before it, the
@@ -258,10 +289,10 @@ class TransformerLM(TokenToWaveformModel):
             n1 = layers[0].norm1
             y = K.add_layer_norm(h, None, n1.weight, n1.bias, n1.eps)
             for i, layer in enumerate(layers):
-                h, y = layer.forward_pre(h, y, layers[i + 1].norm1 if i + 1 < len(layers) else norm, lens, causal, seed, 1 + 4 * i, kd)
+                h, y = layer.forward_pre(h, y, layers[i + 1].norm1 if i + 1 < len(layers) else norm, lens, causal, seed, 1 + 4 * i, kd, rope)
             return K.linear(y, self.classifier.weight, self.classifier.bias, compute_dtype=self.compute_dtype)
         for i, layer in enumerate(layers):
-            h = layer(h, lens, causal, seed, 1 + 4 * i, kd)
+            h = layer(h, lens, causal, seed, 1 + 4 * i, kd, rope)
         h = K.add_layer_norm(h, None, norm.weight, norm.bias, norm.eps)
         return K.linear(h, self.classifier.weight, self.classifier.bias, compute_dtype=self.compute_dtype)
 
@@ -300,20 +331,26 @@ class TransformerLM(TokenToWaveformModel):
         if n_steps < 1 or n_steps + 1 > self.pos_encoding.pe.shape[0]:
             raise ValueError(f"n_steps must be in 1..max_len - 1 = {self.pos_encoding.pe.shape[0] - 1} (got {n_steps})")
         layer = self.transformer.layers[0]
-        return K.DecodeState(batch_size, n_steps, self.d_model, layer.self_attn.num_heads, layer.linear1.out_features,
-                             self.classifier.out_features, len(self.transformer.layers), device, TransformerLM.BOS, uniforms)
+        st = K.DecodeState(batch_size, n_steps, self.d_model, layer.self_attn.num_heads, layer.linear1.out_features,
+                           self.classifier.out_features, len(self.transformer.layers), device, TransformerLM.BOS, uniforms)
+        if self.position == "rotary":
+            # what decode_embed adds instead of the sinusoidal table: zeros, one row per position the state can reach, owned
+            # by the state (captured launches keep pointing at them)
+            st.pe = torch.zeros(n_steps, self.d_model, device=device, dtype=torch.float32)
+        return st
 
     def _decode_logits(self, st):
         """The launches of one decoding step up to the classifier: the token at the state's position -> st.logits.  Fixed
         arguments only (the position is read from st.pos_dev), no allocation, no host synchronisation."""
         pd = st.pos_dev
-        K.decode_embed(st.tokens, self.embedding.weight, self.pos_encoding.table(), st.h, 0, pd)
+        K.decode_embed(st.tokens, self.embedding.weight, st.pe if self.position == "rotary" else self.pos_encoding.table(), st.h, 0, pd)
         if self.norm_first:
             return self._decode_logits_pre(st)
+        rope = self.rope
         for i, layer in enumerate(self.transformer.layers):
             sa, n1, n2 = layer.self_attn, layer.norm1, layer.norm2
             K.decode_linear(st.h, sa.in_proj_weight, sa.in_proj_bias, st.qkv)
-            K.decode_attention(st.qkv, st.kv[i, 0], st.kv[i, 1], st.ctx, st.attn_ws, 0, pd)
+            K.decode_attention(st.qkv, st.kv[i, 0], st.kv[i, 1], st.ctx, st.attn_ws, 0, pd, rope)
             K.decode_linear(st.ctx, sa.out_proj.weight, None, st.a)     # its bias goes through the LayerNorm kernel, as in forward
             K.decode_layer_norm(st.h, st.a, sa.out_proj.bias, n1.weight, n1.bias, n1.eps, st.h1, st.stats)
             K.decode_linear(st.h1, layer.linear1.weight, layer.linear1.bias, st.f, act=layer.act)
@@ -334,7 +371,7 @@ class TransformerLM(TokenToWaveformModel):
             sa, n2 = layer.self_attn, layer.norm2
             nxt = layers[i + 1].norm1 if i + 1 < len(layers) else norm
             K.decode_linear(st.h1, sa.in_proj_weight, sa.in_proj_bias, st.qkv)
-            K.decode_attention(st.qkv, st.kv[i, 0], st.kv[i, 1], st.ctx, st.attn_ws, 0, pd)
+            K.decode_attention(st.qkv, st.kv[i, 0], st.kv[i, 1], st.ctx, st.attn_ws, 0, pd, self.rope)
             K.decode_linear(st.ctx, sa.out_proj.weight, None, st.a)     # its bias goes through the LayerNorm kernel, as in forward
             K.decode_residual_layer_norm(st.h, st.a, sa.out_proj.bias, n2.weight, n2.bias, n2.eps, st.s, st.h1, st.stats)
             K.decode_linear(st.h1, layer.linear1.weight, layer.linear1.bias, st.f, act=layer.act)
@@ -382,17 +419,17 @@ class TransformerLM(TokenToWaveformModel):
             raise ValueError(f"prefill: the state holds {state.n_steps + 1} tokens, <bos> and {p} prompt codes do not fit")
         state.tokens[:, 1:p + 1] = codes + TransformerLM.OFFSET
         state.codes[:, :p] = codes
-        h = K.embed(state.tokens[:, :p].contiguous(), self.embedding.weight, self.pos_encoding.table(), K.NO_DROP, TransformerLM.PAD)
-        layers = self.transformer.layers
+        h = K.embed(state.tokens[:, :p].contiguous(), self.embedding.weight, self._embed_table(p), K.NO_DROP, TransformerLM.PAD)
+        layers, rope = self.transformer.layers, self.rope
         if self.norm_first:
             n1 = layers[0].norm1
             pair = (h, K.add_layer_norm(h, None, n1.weight, n1.bias, n1.eps))
             for i, layer in enumerate(layers):
                 last = i + 1 == len(layers)
-                pair = layer.prefill_pre(*pair, None if last else layers[i + 1].norm1, state.kv[i, 0], state.kv[i, 1], last)
+                pair = layer.prefill_pre(*pair, None if last else layers[i + 1].norm1, state.kv[i, 0], state.kv[i, 1], last, rope)
         else:
             for i, layer in enumerate(layers):
-                h = layer.prefill(h, state.kv[i, 0], state.kv[i, 1], i + 1 == len(layers))
+                h = layer.prefill(h, state.kv[i, 0], state.kv[i, 1], i + 1 == len(layers), rope)
         state.prefill_done(p)
 
     @torch.no_grad()

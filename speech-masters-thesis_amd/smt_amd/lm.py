@@ -149,6 +149,61 @@ def attention(qkv, lens, heads, causal=True, drop=NO_DROP, *, compute_dtype=torc
     return _Attention.apply(qkv, lens, heads, causal, drop, compute_dtype)
 
 
+# ------------------------------------------------------------------------------------------------ rotary positions
+# csrc/lm_rope.hip, include/smt_hip.h "Rotary positions".
+def rope_table(rows, head_dim, base=10000.0, device="cpu"):
+    """The (cos a, sin a) table [rows, head_dim / 2, 2] fp32 of the rotary rotation: a = p * theta_i, theta_i = base^(-2 i / head_dim),
+    for positions p = 0..rows-1 and pairs i = 0..head_dim/2-1, computed on the host in float64 and rounded once."""
+    assert head_dim in HEAD_DIMS, f"the attention kernels are built for head dim 32 or 64 (got {head_dim})"
+    base = float(base)
+    if not (math.isfinite(base) and base > 1.0):
+        raise ValueError(f"rope_table: base must be a finite number > 1 (got {base!r})")
+    i = torch.arange(head_dim // 2, dtype=torch.float64)
+    theta = torch.pow(torch.tensor(base, dtype=torch.float64), -2.0 * i / head_dim)
+    a = torch.arange(rows, dtype=torch.float64)[:, None] * theta[None, :]
+    return torch.stack([torch.cos(a), torch.sin(a)], dim=-1).to(torch.float32).to(device)
+
+
+def _rope_launch(qkv, table, heads, pos0, inverse):
+    b, l, d3 = qkv.shape
+    dh = _head_dim(d3 // 3, heads)
+    assert d3 == 3 * heads * dh and table.dim() == 3 and table.shape[1:] == (dh // 2, 2), \
+        f"rope: the table must be [rows, {dh // 2}, 2] for head dim {dh} (got {tuple(table.shape)})"
+    assert table.dtype == torch.float32 and table.is_cuda and table.is_contiguous()
+    with profiler.region("lm_rope:bwd" if inverse else "lm_rope:fwd", nbytes=2 * b * l * 2 * heads * dh * 4, bound="hbm"):
+        N.check(N.lib().smt_lm_rope(N.ptr(qkv), N.ptr(table), b, l, heads, dh, table.shape[0], int(pos0), int(inverse), N.stream_ptr()),
+                "smt_lm_rope")
+
+
+class _Rope(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, table, heads, pos0):
+        assert qkv.dtype == torch.float32 and qkv.is_cuda and qkv.dim() == 3 and qkv.is_contiguous(), \
+            "rope rotates a contiguous fp32 device tensor [batch, len, 3 dim] in place"
+        _rope_launch(qkv, table, heads, pos0, False)
+        ctx.mark_dirty(qkv)
+        ctx.save_for_backward(table)
+        ctx.meta = (heads, pos0)
+        return qkv
+
+    @staticmethod
+    def backward(ctx, dout):
+        (table,) = ctx.saved_tensors
+        heads, pos0 = ctx.meta
+        # an incoming gradient is not ours to modify: the inverse rotation runs in place on a copy, whose v third is the pass-through
+        dqkv = dout.clone(memory_format=torch.contiguous_format)
+        _rope_launch(dqkv, table, heads, pos0, True)
+        return dqkv, None, None, None
+
+
+def rope(qkv, table, heads, pos0=0):
+    """Rotary positions, IN PLACE: the q and k thirds of qkv [batch, len, 3 dim] (contiguous fp32, the output of the
+    in-projection) rotated pair by pair -- channels (2i, 2i+1) of every head by the angle of `table` row pos0 + l (`rope_table`);
+    the v third is not touched.  Returns qkv.  Backward: the inverse rotation of the gradient's q and k thirds, v passed through.
+    The projection that produced qkv must not need its own output for its backward (F.linear and `linear` below do not)."""
+    return _Rope.apply(qkv, table, heads, pos0)
+
+
 class _AddLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, h, h_bias, gamma, beta, eps, drop):
@@ -578,17 +633,26 @@ def decode_attention_workspace(batch, heads, l_max, device, head_dim=32):
     return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
 
 
-def decode_attention(qkv, k_cache, v_cache, ctx, workspace=None, pos=0, pos_dev=None):
+def decode_attention(qkv, k_cache, v_cache, ctx, workspace=None, pos=0, pos_dev=None, rope=None):
     """qkv [batch, 3 * heads * dh] of the token at `pos`; k_cache / v_cache [batch, heads, l_max, dh] get its k / v rows at row
-    pos; ctx [batch, heads * dh] = softmax(q K[0..pos]^T / sqrt(dh)) V[0..pos].  dh, read from the caches, is 32 or 64."""
+    pos; ctx [batch, heads * dh] = softmax(q K[0..pos]^T / sqrt(dh)) V[0..pos].  dh, read from the caches, is 32 or 64.
+    rope (a `rope_table` [rows, dh / 2, 2], or None): q and the step's k are rotated at position pos inside the same launch, so
+    the cache holds rotated keys; None is the launch without it."""
     b, h, l_max, dh = k_cache.shape
     assert dh in HEAD_DIMS, f"the attention kernels are built for head dim 32 or 64 (got {dh})"
     assert v_cache.shape == k_cache.shape and qkv.shape == (b, 3 * h * dh) and ctx.shape == (b, h * dh)
     assert k_cache.dtype == v_cache.dtype == ctx.dtype == torch.float32
     p, pd = _pos_args(pos, pos_dev)
-    N.check(N.lib().smt_lm_decode_attention_hd(N.ptr(_f32(qkv)), N.ptr(k_cache), N.ptr(v_cache), N.ptr(ctx), N.ptr(workspace),
-                                               0 if workspace is None else workspace.numel(), b, h, l_max, dh, p, pd, N.stream_ptr()),
-            "smt_lm_decode_attention_hd")
+    ws_bytes = 0 if workspace is None else workspace.numel()
+    if rope is None:
+        N.check(N.lib().smt_lm_decode_attention_hd(N.ptr(_f32(qkv)), N.ptr(k_cache), N.ptr(v_cache), N.ptr(ctx), N.ptr(workspace),
+                                                   ws_bytes, b, h, l_max, dh, p, pd, N.stream_ptr()), "smt_lm_decode_attention_hd")
+        return ctx
+    assert rope.dim() == 3 and rope.shape[1:] == (dh // 2, 2) and rope.dtype == torch.float32 and rope.is_cuda and rope.is_contiguous(), \
+        f"decode_attention: the rope table must be a contiguous fp32 device tensor [rows, {dh // 2}, 2]"
+    N.check(N.lib().smt_lm_decode_attention_rope(N.ptr(_f32(qkv)), N.ptr(k_cache), N.ptr(v_cache), N.ptr(ctx), N.ptr(workspace), ws_bytes,
+                                                 b, h, l_max, dh, N.ptr(rope), rope.shape[0], p, pd, N.stream_ptr()),
+            "smt_lm_decode_attention_rope")
     return ctx
 
 
@@ -682,6 +746,7 @@ class DecodeState:
         self.stats = torch.empty(batch, 2, **f32)
         self.logits = torch.empty(batch, vocab, **f32)
         self.attn_ws = decode_attention_workspace(batch, heads, n_steps, device, dh)
+        self.pe = None        # set by a model with rotary positions: the [n_steps, dim] zeros its decode_embed adds
 
     def advance(self):
         """pos += 1, on the device and in the host mirror."""

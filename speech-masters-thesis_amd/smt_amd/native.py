@@ -160,6 +160,9 @@ _SIGNATURES = {
     "smt_lm_decode_attention_hd_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int]),
     "smt_lm_decode_attention_hd": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "smt_lm_decode_attention": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
+    "smt_lm_rope": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr]),
+    "smt_lm_decode_attention_rope": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_int, c_int, c_int, c_int, c_ptr, c_int, c_int, c_ptr,
+                                             c_ptr]),
     "smt_lm_decode_sample": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_f32, c_int, c_int, c_ptr, c_ptr]),
     "smt_lm_decode_sample_filtered": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_f32, c_int, c_int, c_f32, c_ptr,
                                               c_int, c_ptr, c_ptr]),
