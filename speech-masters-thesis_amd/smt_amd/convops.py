@@ -649,12 +649,13 @@ class _ConvIn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, lens, stride, padding, out_dtype):
         b, t_in = x.shape
         c_out, _, k = weight.shape
-        t_out = (t_in + 2 * padding - k) // stride + 1
+        t_out = max(0, (t_in + 2 * padding - k) // stride + 1)       # an input shorter than the kernel gives no rows
         y = torch.empty(b, t_out, c_out, dtype=out_dtype, device=x.device)
         lens32 = _i32(lens)
         with profiler.region("conv_in_fwd", nbytes=x.numel() * 4 + y.numel() * y.element_size(), bound="hbm"):
-            N.check(N.lib().smt_conv_in_fwd(_p(x), _p(weight), _p(bias), _p(lens32), _p(y), _DT[out_dtype], b, t_in,
-                                            t_out, c_out, k, stride, padding, N.stream_ptr()), "smt_conv_in_fwd")
+            if y.numel():                                            # (an empty tensor has no storage to point the kernel at)
+                N.check(N.lib().smt_conv_in_fwd(_p(x), _p(weight), _p(bias), _p(lens32), _p(y), _DT[out_dtype], b, t_in,
+                                                t_out, c_out, k, stride, padding, N.stream_ptr()), "smt_conv_in_fwd")
         ctx.save_for_backward(x, weight, lens32 if lens32 is not None else torch.empty(0))
         ctx.cfg = (stride, padding, lens is not None)
         return y
@@ -667,6 +668,8 @@ class _ConvIn(torch.autograd.Function):
         b, t_in = x.shape
         c_out, _, k = weight.shape
         dy = dy.contiguous()
+        if dy.numel() == 0:                                          # no output rows: nothing to sum
+            return None, torch.zeros_like(weight), torch.zeros(c_out, dtype=torch.float32, device=x.device), None, None, None, None
         dw = torch.empty_like(weight)
         db = torch.empty(c_out, dtype=torch.float32, device=x.device)
         lib = N.lib()
